@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """Headline benchmark: env-steps/s of the AttentionModel construction rollout on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload W] [--batch B] [--strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload W] [--batch B] [--strong] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up (a few eager rollouts, then W steps), times the K steps and prints the result line (contract
+keys + `config`).  `--full` adds everything else listed below: HIP events per launch family in those eager rollouts
+behind the roofline keys, the strong-scaling split of a weak multi-GPU run, the parameter check of the training step and
+the CPU baseline (`--no-cpu-baseline` drops the last one).  `--dump-outputs DIR` writes what the last timed step
+returned (see dump_outputs).
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself: the parent process (which never
 touches the GPU) runs `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child and exits with its
@@ -16,10 +22,10 @@ rollout -> teacher-forced re-evaluation + backward -> ONE flat RCCL all-reduce -
 (eam_rl4co_amd.train.PolicyGradientStep, the reference's POMO.shared_step + trainer).
 Metric: env-steps/s = ranks * batch * starts * num_loc * K / wall time (max over ranks, barrier on both sides).
 Multi-GPU: independent instance batches per rank, no data-path collective ("weak": the batch is per GPU; `--strong`: the
-workload's batch is the GLOBAL batch, split over the ranks).  A weak run on N > 1 ranks also times the strong split of
-the same global batch and reports it under "strong_scaling".
+workload's batch is the GLOBAL batch, split over the ranks).  With `--full` a weak run on N > 1 ranks also times the
+strong split of the same global batch and reports it under "strong_scaling".
 
-Besides the contract keys the JSON line carries
+With `--full`, besides the contract keys the JSON line carries
   roofline         the launch family with the largest share of the step (today the encoder / cache GEMMs on fp32 MFMA):
                    algorithmic flops per step / its time measured with HIP events on the launch stream, against the
                    dense fp32 MFMA peak
@@ -286,6 +292,39 @@ def params_checksum(policy, torch):
     return tot
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out, policy, train, dump_dir, torch):
+    """`--dump-outputs DIR`: every tensor the last timed step returned (reward, actions, log-likelihoods, ...; for the
+    training step also the parameters it left behind, flattened) as DIR/<name>.npy.  Floats keep float64 or become
+    float32; integers and booleans become float32 (float64 where a value exceeds 2^24).  If the whole would exceed 64 MB,
+    every array keeps the same fixed, seeded sample of its rows (numpy default_rng(0), sorted), scaled to the limit."""
+    import numpy as np
+
+    arrays = {k: v.detach().cpu().numpy() for k, v in out.items() if isinstance(v, torch.Tensor)}
+    if train:
+        arrays["params"] = torch.cat([p.detach().reshape(-1) for p in policy.parameters()]).cpu().numpy()
+    for k, a in arrays.items():
+        if a.dtype == np.float64:
+            continue
+        if a.dtype.kind in "iub" and a.size and np.abs(a.astype(np.int64)).max() > 2 ** 24:
+            arrays[k] = a.astype(np.float64)
+        else:
+            arrays[k] = a.astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        for k, a in arrays.items():
+            if a.ndim == 0:
+                continue
+            keep = max(1, a.shape[0] * DUMP_LIMIT_BYTES // total)
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+            arrays[k] = np.ascontiguousarray(a[rows])
+    os.makedirs(dump_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dump_dir, f"{k}.npy"), a)
+
+
 def run_selftest(args, torch, dist, rank, world):
     """No GPU: N ranks over gloo run the collective half of the training step on synthetic per-rank gradients."""
     import eam_rl4co_amd as ea
@@ -330,12 +369,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="tsp100", choices=list(WORKLOADS))
     ap.add_argument("--batch", type=int, default=None, help="instances per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel eagerly instead of replaying a HIP graph")
     ap.add_argument("--strong", action="store_true",
                     help="strong scaling: the workload's batch is the GLOBAL batch, split over the ranks (default: weak, "
                          "the batch is per GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-family roofline passes, the strong-scaling split, the training step's parameter "
+                         "check and the CPU baseline (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
@@ -417,31 +463,35 @@ def main():
 
     one_step = make_step(tds)
 
-    # per launch family: HIP events around the calls on the launch stream, in eager passes before the timed region
-    ft = FamilyTimer(torch)
-    orig = {n: getattr(ops, n) for n in ("rollout", "linear", "matmul_right", "mha_encoder", "encoder_fused")}
+    # eager rollouts of the first batch before the timed region: the warm-up the headline figure has always had, and the
+    # same draws from torch's generator with or without --full (a sampling workload computes the same either way)
+    if args.full:
+        # per launch family: HIP events around the calls on the launch stream, in eager passes before the timed region
+        ft = FamilyTimer(torch)
+        orig = {n: getattr(ops, n) for n in ("rollout", "linear", "matmul_right", "mha_encoder", "encoder_fused")}
 
-    def fused_flops(a, r, k):   # per instance and layer: qkv + QK^T + PV + out_proj + FFN (algorithmic, unpadded)
-        if a[0] is not None:
-            Bq, Mq, Eq = a[0].shape
-        else:       # init embedding computed inside the kernel: shapes from the feature tensor and its weight
-            (Bq, Mq, _), Eq = k["init"]["feat"].shape, k["init"]["W"].shape[0]
-        per = 2.0 * Mq * Eq * 3 * Eq + 4.0 * Mq * Mq * Eq + 2.0 * Mq * Eq * Eq + 4.0 * Mq * Eq * a[3]
-        tot = per * Bq * len(a[1])
-        if k.get("cache") is not None:      # + the decoder cache projections done from LDS: (nproj + 1) x [M, E] x [E, E]
-            tot += 2.0 * Mq * Eq * Eq * (k["cache"][3] + 1) * Bq
-        return tot
+        def fused_flops(a, r, k):   # per instance and layer: qkv + QK^T + PV + out_proj + FFN (algorithmic, unpadded)
+            if a[0] is not None:
+                Bq, Mq, Eq = a[0].shape
+            else:       # init embedding computed inside the kernel: shapes from the feature tensor and its weight
+                (Bq, Mq, _), Eq = k["init"]["feat"].shape, k["init"]["W"].shape[0]
+            per = 2.0 * Mq * Eq * 3 * Eq + 4.0 * Mq * Mq * Eq + 2.0 * Mq * Eq * Eq + 4.0 * Mq * Eq * a[3]
+            tot = per * Bq * len(a[1])
+            if k.get("cache") is not None:      # + the decoder cache projections done from LDS: (nproj + 1) x [M, E] x [E, E]
+                tot += 2.0 * Mq * Eq * Eq * (k["cache"][3] + 1) * Bq
+            return tot
 
-    ops.encoder_fused = ft.wrap("encoder_fused", orig["encoder_fused"], fused_flops)
-    ops.rollout = ft.wrap("decode", orig["rollout"])
-    ops.linear = ft.wrap("gemm", orig["linear"], lambda a, r: 2.0 * a[0].numel() * r.shape[-1])
-    ops.matmul_right = ft.wrap("gemm", orig["matmul_right"], lambda a, r: 2.0 * a[0].numel() * r.shape[-1])
-    ops.mha_encoder = ft.wrap("attention", orig["mha_encoder"],
-                              lambda a, r: 4.0 * r.shape[0] * r.shape[1] * r.shape[1] * r.shape[2])
+        ops.encoder_fused = ft.wrap("encoder_fused", orig["encoder_fused"], fused_flops)
+        ops.rollout = ft.wrap("decode", orig["rollout"])
+        ops.linear = ft.wrap("gemm", orig["linear"], lambda a, r: 2.0 * a[0].numel() * r.shape[-1])
+        ops.matmul_right = ft.wrap("gemm", orig["matmul_right"], lambda a, r: 2.0 * a[0].numel() * r.shape[-1])
+        ops.mha_encoder = ft.wrap("attention", orig["mha_encoder"],
+                                  lambda a, r: 4.0 * r.shape[0] * r.shape[1] * r.shape[1] * r.shape[2])
+
     n_pass, skip = (3, 1) if train else (5, 2)
     rollout_ms = []
     for i in range(n_pass):
-        if i == skip:
+        if args.full and i == skip:
             ft.clear()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -450,11 +500,12 @@ def main():
         e1.record()
         rollout_ms.append((e0, e1))
     torch.cuda.synchronize()
-    for n, f in orig.items():
-        setattr(ops, n, f)
-    passes = n_pass - skip
-    rollout_only_ms = float(np.mean([a.elapsed_time(b) for a, b in rollout_ms[skip:]]))
-    fam_ms = {f: ft.ms(f, passes) for f in ("gemm", "attention", "decode", "encoder_fused")}
+    if args.full:
+        for n, f in orig.items():
+            setattr(ops, n, f)
+        passes = n_pass - skip
+        rollout_only_ms = float(np.mean([a.elapsed_time(b) for a, b in rollout_ms[skip:]]))
+        fam_ms = {f: ft.ms(f, passes) for f in ("gemm", "attention", "decode", "encoder_fused")}
 
     def timed(step_fn, steps, warmup):
         out = None
@@ -479,16 +530,18 @@ def main():
         return el, out, nsteps
 
     elapsed, out, decode_steps = timed(one_step, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, policy, train, args.dump_outputs, torch)
 
     strong = None
-    if world > 1 and not args.strong and not train and batch % world == 0:
+    if args.full and world > 1 and not args.strong and not train and batch % world == 0:
         # the same GLOBAL batch as the 1-GPU run, split over the ranks (north_star: strong scaling)
         el_s, _, _ = timed(make_step([t_[: batch // world] for t_ in tds]), args.steps, max(1, args.warmup))
         strong = {"global_batch": batch, "batch_per_gpu": batch // world, "ms_per_step": round(el_s / args.steps * 1e3, 4),
                   "value": round(batch * S * num_loc * args.steps / el_s, 1), "unit": "env-steps/s"}
 
     identical = None
-    if train:
+    if args.full and train:
         cs = params_checksum(policy, torch)
         lo, hi = cs.clone(), cs.clone()
         if world > 1:
@@ -501,70 +554,74 @@ def main():
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = world * batch * S * num_loc * args.steps / elapsed
-        kern = fam_ms["decode"]
         T = float(np.mean(decode_steps)) - (1 if S > 1 else 0)
-        # ---- decode loop: the bound it sits on ----------------------------------------------------------------
-        step_api_bytes = algorithmic_bytes_per_decode_step(env_name, M, S=S) * batch * T
-        step_api = {"achieved_GBs": round(step_api_bytes / (kern * 1e-3) / 1e9, 1),
-                    "frac_of_hbm_peak": round(step_api_bytes / (kern * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                    "note": "step-at-a-time API bytes (SURVEY 8d: K, V, L re-read every step); > 1 means the kernel does not "
-                            "re-read them"}
-        traffic = measured_traffic(args.workload.replace("_train", ""), batch)
-        if M <= 128:
-            rb = resident_bytes_per_rollout(env_name, M, T, S=S, sampling="sampling" in decode_type) * batch
-            flops = executed_flops_per_query_step(M) * batch * S * T
-            tf = flops / (kern * 1e-3) / 1e12
-            roofline_decode = {
-                "kernel": ("k_rollout_ms_mfma (decode loop of all starts of an instance on fp32 MFMA, K/V/Lp as register fragments)"
-                           if S > 1 and env_name in ("tsp", "cvrp") and M <= 112 else
-                           "k_rollout_resident (decode loop, K/V/Lp read once per rollout into VGPRs)"),
-                "bound": "hbm", "achieved": round(rb / (kern * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(rb / (kern * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), "traffic": traffic,
-                "algorithmic_bytes_per_launch": int(rb), "kernel_ms": round(kern, 4),
-                "issue_bound": {"bound": "mfma" if S > 1 and env_name in ("tsp", "cvrp") and M <= 112 else "fp32 valu issue",
-                                "achieved": round(tf, 2), "peak": F32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                                "frac": round(tf / F32_PEAK_TFLOPS, 4),
-                                "note": "the kernel is instruction-issue / latency bound, not HBM bound (DESIGN.md 4): executed "
-                                        "flops 6*M*E per query-step against the fp32 peak (the 6*E*E context / output "
-                                        "projections of SURVEY 8d are folded into the cache and counted in the encoder launch)",
-                                "counters": measured_counters(args.workload.replace("_train", ""),
-                                                              "k_rollout_ms_mfma" if S > 1 and env_name in ("tsp", "cvrp") and M <= 112
-                                                              else "k_rollout_resident")},
-                "step_api_view": step_api}
-        else:
-            ach = (traffic or step_api_bytes) / (kern * 1e-3) / 1e9
-            roofline_decode = {
-                "kernel": "k_rollout_stream (decode loop, K/V/Lp re-read every step; masked rows skipped)",
-                "bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": traffic, "kernel_ms": round(kern, 4),
-                "basis": "measured HBM traffic (PMC)" if traffic else "algorithmic bytes (no PMC pass for this workload)",
-                "algorithmic_bytes_per_launch": int(step_api_bytes), "step_api_view": step_api}
-        # ---- the family with the largest share of the step ------------------------------------------------------
-        gemm_tf = ft.flops.get("gemm", 0.0) / passes / (fam_ms["gemm"] * 1e-3) / 1e12 if fam_ms["gemm"] else 0.0
-        att_tf = ft.flops.get("attention", 0.0) / passes / (fam_ms["attention"] * 1e-3) / 1e12 if fam_ms["attention"] else 0.0
-        roofline_gemm = {"kernel": "k_linear_mfma (encoder + cache nn.Linear launches, v_mfma_f32_32x32x2_f32)",
-                         "bound": "mfma", "achieved": round(gemm_tf, 2), "peak": F32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(gemm_tf / F32_PEAK_TFLOPS, 4), "traffic": None,
-                         "ms_per_step": round(fam_ms["gemm"], 4), "launches_per_step": ft.launches("gemm", passes),
-                         "algorithmic_flops_per_step": int(ft.flops.get("gemm", 0.0) / passes)}
-        roofline_att = {"kernel": "k_mha_encoder (encoder self-attention)", "bound": "mfma", "achieved": round(att_tf, 2),
-                        "peak": F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(att_tf / F32_PEAK_TFLOPS, 4),
-                        "ms_per_step": round(fam_ms["attention"], 4), "launches_per_step": ft.launches("attention", passes)}
-        enc_tf = (ft.flops.get("encoder_fused", 0.0) / passes / (fam_ms["encoder_fused"] * 1e-3) / 1e12
-                  if fam_ms["encoder_fused"] else 0.0)
-        roofline_enc = {"kernel": "k_encoder_fused (all encoder layers of an instance in one workgroup, v_mfma_f32_16x16x4_f32)",
-                        "bound": "mfma", "achieved": round(enc_tf, 2), "peak": F32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                        "frac": round(enc_tf / F32_PEAK_TFLOPS, 4),
-                        "traffic": measured_traffic(args.workload.replace("_train", ""), batch, "_encoder_fused"),
-                        "kernel_ms": round(fam_ms["encoder_fused"], 4), "launches_per_step": ft.launches("encoder_fused", passes),
-                        "algorithmic_flops_per_launch": int(ft.flops.get("encoder_fused", 0.0) / passes),
-                        "counters": measured_counters(args.workload.replace("_train", ""), "k_encoder_fused")}
-        dominant = max(fam_ms, key=lambda f: fam_ms[f])
-        roofline = dict(roofline_enc if dominant == "encoder_fused" else roofline_gemm if dominant == "gemm" else
-                        roofline_decode["issue_bound"] | {"kernel": roofline_decode["kernel"], "kernel_ms": round(kern, 4)}
-                        if (dominant == "decode" and M <= 128) else roofline_decode if dominant == "decode" else roofline_att)
-        roofline["share_of_step"] = {f: round(v / rollout_only_ms, 3) for f, v in fam_ms.items()}
-        roofline["dominant_family"] = dominant
+        full = {}
+        if args.full:
+            kern = fam_ms["decode"]
+            # ---- decode loop: the bound it sits on ----------------------------------------------------------------
+            step_api_bytes = algorithmic_bytes_per_decode_step(env_name, M, S=S) * batch * T
+            step_api = {"achieved_GBs": round(step_api_bytes / (kern * 1e-3) / 1e9, 1),
+                        "frac_of_hbm_peak": round(step_api_bytes / (kern * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                        "note": "step-at-a-time API bytes (SURVEY 8d: K, V, L re-read every step); > 1 means the kernel does not "
+                                "re-read them"}
+            traffic = measured_traffic(args.workload.replace("_train", ""), batch)
+            if M <= 128:
+                rb = resident_bytes_per_rollout(env_name, M, T, S=S, sampling="sampling" in decode_type) * batch
+                flops = executed_flops_per_query_step(M) * batch * S * T
+                tf = flops / (kern * 1e-3) / 1e12
+                roofline_decode = {
+                    "kernel": ("k_rollout_ms_mfma (decode loop of all starts of an instance on fp32 MFMA, K/V/Lp as register fragments)"
+                               if S > 1 and env_name in ("tsp", "cvrp") and M <= 112 else
+                               "k_rollout_resident (decode loop, K/V/Lp read once per rollout into VGPRs)"),
+                    "bound": "hbm", "achieved": round(rb / (kern * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(rb / (kern * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), "traffic": traffic,
+                    "algorithmic_bytes_per_launch": int(rb), "kernel_ms": round(kern, 4),
+                    "issue_bound": {"bound": "mfma" if S > 1 and env_name in ("tsp", "cvrp") and M <= 112 else "fp32 valu issue",
+                                    "achieved": round(tf, 2), "peak": F32_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                    "frac": round(tf / F32_PEAK_TFLOPS, 4),
+                                    "note": "the kernel is instruction-issue / latency bound, not HBM bound (DESIGN.md 4): executed "
+                                            "flops 6*M*E per query-step against the fp32 peak (the 6*E*E context / output "
+                                            "projections of SURVEY 8d are folded into the cache and counted in the encoder launch)",
+                                    "counters": measured_counters(args.workload.replace("_train", ""),
+                                                                  "k_rollout_ms_mfma" if S > 1 and env_name in ("tsp", "cvrp") and M <= 112
+                                                                  else "k_rollout_resident")},
+                    "step_api_view": step_api}
+            else:
+                ach = (traffic or step_api_bytes) / (kern * 1e-3) / 1e9
+                roofline_decode = {
+                    "kernel": "k_rollout_stream (decode loop, K/V/Lp re-read every step; masked rows skipped)",
+                    "bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": traffic, "kernel_ms": round(kern, 4),
+                    "basis": "measured HBM traffic (PMC)" if traffic else "algorithmic bytes (no PMC pass for this workload)",
+                    "algorithmic_bytes_per_launch": int(step_api_bytes), "step_api_view": step_api}
+            # ---- the family with the largest share of the step ------------------------------------------------------
+            gemm_tf = ft.flops.get("gemm", 0.0) / passes / (fam_ms["gemm"] * 1e-3) / 1e12 if fam_ms["gemm"] else 0.0
+            att_tf = ft.flops.get("attention", 0.0) / passes / (fam_ms["attention"] * 1e-3) / 1e12 if fam_ms["attention"] else 0.0
+            roofline_gemm = {"kernel": "k_linear_mfma (encoder + cache nn.Linear launches, v_mfma_f32_32x32x2_f32)",
+                             "bound": "mfma", "achieved": round(gemm_tf, 2), "peak": F32_PEAK_TFLOPS, "unit": "TFLOP/s",
+                             "frac": round(gemm_tf / F32_PEAK_TFLOPS, 4), "traffic": None,
+                             "ms_per_step": round(fam_ms["gemm"], 4), "launches_per_step": ft.launches("gemm", passes),
+                             "algorithmic_flops_per_step": int(ft.flops.get("gemm", 0.0) / passes)}
+            roofline_att = {"kernel": "k_mha_encoder (encoder self-attention)", "bound": "mfma", "achieved": round(att_tf, 2),
+                            "peak": F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(att_tf / F32_PEAK_TFLOPS, 4),
+                            "ms_per_step": round(fam_ms["attention"], 4), "launches_per_step": ft.launches("attention", passes)}
+            enc_tf = (ft.flops.get("encoder_fused", 0.0) / passes / (fam_ms["encoder_fused"] * 1e-3) / 1e12
+                      if fam_ms["encoder_fused"] else 0.0)
+            roofline_enc = {"kernel": "k_encoder_fused (all encoder layers of an instance in one workgroup, v_mfma_f32_16x16x4_f32)",
+                            "bound": "mfma", "achieved": round(enc_tf, 2), "peak": F32_PEAK_TFLOPS, "unit": "TFLOP/s",
+                            "frac": round(enc_tf / F32_PEAK_TFLOPS, 4),
+                            "traffic": measured_traffic(args.workload.replace("_train", ""), batch, "_encoder_fused"),
+                            "kernel_ms": round(fam_ms["encoder_fused"], 4), "launches_per_step": ft.launches("encoder_fused", passes),
+                            "algorithmic_flops_per_launch": int(ft.flops.get("encoder_fused", 0.0) / passes),
+                            "counters": measured_counters(args.workload.replace("_train", ""), "k_encoder_fused")}
+            dominant = max(fam_ms, key=lambda f: fam_ms[f])
+            roofline = dict(roofline_enc if dominant == "encoder_fused" else roofline_gemm if dominant == "gemm" else
+                            roofline_decode["issue_bound"] | {"kernel": roofline_decode["kernel"], "kernel_ms": round(kern, 4)}
+                            if (dominant == "decode" and M <= 128) else roofline_decode if dominant == "decode" else roofline_att)
+            roofline["share_of_step"] = {f: round(v / rollout_only_ms, 3) for f, v in fam_ms.items()}
+            roofline["dominant_family"] = dominant
+            full = {"roofline": roofline, "roofline_decode": roofline_decode, "roofline_gemm": roofline_gemm,
+                    "roofline_attention": roofline_att, "roofline_encoder_fused": roofline_enc}
         cfg = {"workload": f"{env_name.upper()} num_loc={num_loc} batch={batch}/GPU "
                            + (f"x {S} starts POMO" if pomo else "AM") + f" {decode_type} "
                            + ("REINFORCE training step (rollout + re-evaluation + backward + flat all-reduce + clip + Adam)"
@@ -572,7 +629,7 @@ def main():
                "decode_steps": T, "reward_mean": round(float(out["reward"].mean()), 4),
                "global_batch": global_batch,
                "launch": "eager" if (args.no_graph or train) else "hipGraph replay"}
-        if train:
+        if train and args.full:
             cfg["rollout_ms"] = round(rollout_only_ms, 3)
             cfg["gradient_side_ms"] = round(ms_per_step - rollout_only_ms, 3)
         line = {
@@ -581,18 +638,18 @@ def main():
             "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
             "scaling": "strong" if args.strong else "weak", "vs_baseline": None, "dtype": "f32",
             "data": f"synthetic (uniform instances, {NBATCH} different batches in rotation; closed-form untrained weights)",
-            "config": cfg, "roofline": roofline, "roofline_decode": roofline_decode, "roofline_gemm": roofline_gemm,
-            "roofline_attention": roofline_att, "roofline_encoder_fused": roofline_enc,
+            "config": cfg, **full,
         }
         if strong is not None:
             line["strong_scaling"] = strong
-        # inputs of DESIGN.md 5's strong-scaling projection: this rank's share and how its step splits into the one-shot
-        # encoder and the sequential decode loop (the first real multi-GPU run can be compared with the per-share table)
-        line["per_gpu_share"] = {"batch_per_gpu": batch, "encoder_ms": round(fam_ms["encoder_fused"] + fam_ms["gemm"] + fam_ms["attention"], 4),
-                                 "decode_ms": round(fam_ms["decode"], 4), "rollout_ms_eager": round(rollout_only_ms, 4)}
+        if args.full:
+            # inputs of DESIGN.md 5's strong-scaling projection: this rank's share and how its step splits into the one-shot
+            # encoder and the sequential decode loop (the first real multi-GPU run can be compared with the per-share table)
+            line["per_gpu_share"] = {"batch_per_gpu": batch, "encoder_ms": round(fam_ms["encoder_fused"] + fam_ms["gemm"] + fam_ms["attention"], 4),
+                                     "decode_ms": round(fam_ms["decode"], 4), "rollout_ms_eager": round(rollout_only_ms, 4)}
         if identical is not None:
             line["params_identical"] = identical
-        if not args.no_cpu_baseline and world == 1:      # a reported baseline of the 1-GPU run only (the other ranks would wait)
+        if args.full and not args.no_cpu_baseline and world == 1:   # a reported baseline of the 1-GPU run only (the other ranks would wait)
             line["cpu_baseline"] = cpu_baseline(env_name, num_loc, decode_type, num_starts=S if S > 1 else 0, pomo=pomo)
             if train:
                 line["cpu_baseline"]["sample"] += " -- rollout part only (the oracle has no backward)"

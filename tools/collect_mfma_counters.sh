@@ -14,8 +14,8 @@ cd /tmp && export TMPDIR=/tmp
 for w in $WL; do
   extra="--no-graph"; case $w in *_train) extra="";; esac
   timeout -k 10 400 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_BUSY_CU_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES GRBM_GUI_ACTIVE \
-      --kernel-trace --output-format csv -d $OUT/pmc_mfma_$w -- python3 $R/bench.py --workload $w --steps 3 --warmup 1 --no-cpu-baseline $extra > $OUT/pmc_mfma_$w.log 2>&1 || echo "pmc mfma $w failed"
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$w -- python3 $R/bench.py --workload $w --steps 5 --warmup 1 --no-cpu-baseline $extra > $OUT/stats_$w.log 2>&1 || echo "stats $w failed"
+      --kernel-trace --output-format csv -d $OUT/pmc_mfma_$w -- python3 $R/bench.py --full --workload $w --steps 3 --warmup 1 --no-cpu-baseline $extra > $OUT/pmc_mfma_$w.log 2>&1 || echo "pmc mfma $w failed"
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$w -- python3 $R/bench.py --full --workload $w --steps 5 --warmup 1 --no-cpu-baseline $extra > $OUT/stats_$w.log 2>&1 || echo "stats $w failed"
   echo "$w done"
 done
 python3 $R/tools/summarize_counters.py $OUT > $OUT/counters.json && cat $OUT/counters.json

@@ -11,7 +11,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for w in $WL; do
   for c in FETCH_SIZE WRITE_SIZE; do
-    timeout -k 10 500 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmc_${w}_$c -- python3 $R/bench.py --workload $w --steps 2 --warmup 1 --no-cpu-baseline --no-graph > $OUT/pmc_${w}_$c.log 2>&1 || echo "pmc $w $c failed"
+    timeout -k 10 500 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmc_${w}_$c -- python3 $R/bench.py --full --workload $w --steps 2 --warmup 1 --no-cpu-baseline --no-graph > $OUT/pmc_${w}_$c.log 2>&1 || echo "pmc $w $c failed"
     echo "$w $c done"
   done
 done

@@ -8,7 +8,7 @@ timeout -k 10 900 python -m pytest tests -x -q -m gpu > $OUT/pytest_gpu.log 2>&1
 tail -5 $OUT/pytest_gpu.log
 [ $rc -eq 0 ] || exit 1
 for w in tsp100 tsp20 cvrp100 pomo100; do
-  timeout -k 10 300 python bench.py --workload $w --steps 20 --warmup 3 --no-cpu-baseline > $OUT/$w.json 2> $OUT/$w.err; echo "$w rc=$?"
+  timeout -k 10 300 python bench.py --full --workload $w --steps 20 --warmup 3 --no-cpu-baseline > $OUT/$w.json 2> $OUT/$w.err; echo "$w rc=$?"
 done
 python - <<PY
 import json

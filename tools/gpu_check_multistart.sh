@@ -7,4 +7,4 @@ timeout -k 10 900 python -m pytest tests -x -q -m gpu -k "start or multistart or
 [ $rc -eq 0 ] || exit 1
 timeout -k 10 300 python tools/kernel_bench.py train --iters 12 > $OUT/eam.log 2>&1; grep EAM $OUT/eam.log
 EAMRL_DEBUG_KEYS=13=1 timeout -k 10 300 python tools/kernel_bench.py train --iters 12 > $OUT/eam_nosplit.log 2>&1; grep EAM $OUT/eam_nosplit.log
-timeout -k 10 300 python bench.py --workload pomo100 --steps 10 --warmup 2 --no-cpu-baseline > $OUT/pomo100.json 2> $OUT/pomo100.err; python -c "import json; d=json.load(open('$OUT/pomo100.json')); print('pomo100', d['ms_per_step'])"
+timeout -k 10 300 python bench.py --full --workload pomo100 --steps 10 --warmup 2 --no-cpu-baseline > $OUT/pomo100.json 2> $OUT/pomo100.err; python -c "import json; d=json.load(open('$OUT/pomo100.json')); print('pomo100', d['ms_per_step'])"

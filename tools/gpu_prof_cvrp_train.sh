@@ -5,7 +5,7 @@ OUT=gpurun_out/cvrp_train
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/stats -- python3 $R/bench.py --workload pomo_cvrp100_train --steps 2 --warmup 1 --no-cpu-baseline > $R/$OUT/stats.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/stats -- python3 $R/bench.py --full --workload pomo_cvrp100_train --steps 2 --warmup 1 --no-cpu-baseline > $R/$OUT/stats.log 2>&1
 cd $R
 f=$(ls $OUT/stats/*/*kernel_stats.csv | head -1); cp $f $OUT/kernel_stats.csv
 python3 - <<'PY'

@@ -25,7 +25,7 @@ def family(name):
 
 def main(root):
     out = {"_how": "rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_BUSY_CU_CYCLES SQ_INSTS_VALU "
-                   "SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES GRBM_GUI_ACTIVE --kernel-trace -- python3 bench.py --workload W --steps 3 "
+                   "SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES GRBM_GUI_ACTIVE --kernel-trace -- python3 bench.py --full --workload W --steps 3 "
                    "--warmup 1 --no-cpu-baseline [--no-graph] (tools/collect_mfma_counters.sh); means per launch; durations "
                    "from the kernel trace of the same pass; clock = GRBM_GUI_ACTIVE / 8 / duration"}
     for d in sorted(glob.glob(os.path.join(root, "pmc_mfma_*"))):
