@@ -99,6 +99,10 @@ PROTOTYPES = {
     "eamrl_encoder_fused_supported": [_i32, _i32, _i32, _i32, _i32],
     "eamrl_encoder_fused": [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp],
     "eamrl_encoder_fused_init": [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp],
+    "eamrl_pack_linear_weight16": [_vp, _vp, _i32, _i32, _i32, _vp],
+    "eamrl_encoder_fused16_supported": [_i32, _i32, _i32, _i32, _i32, _i32],
+    "eamrl_encoder_fused16": [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _i32, _vp],
+    "eamrl_encoder_fused16_init": [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _i32, _vp],
     "eamrl_reeval_supported": [_i32, _i32, _i32],
     "eamrl_reeval_scratch_floats": [_i64, _i32, _i32],
     "eamrl_pack_mask_bits_chunked": [_vp, _vp, _i64, _i32, _i32, _i32, _vp],

@@ -390,6 +390,54 @@ __attribute__((visibility("default"))) int eamrl_encoder_fused_init(const eamrl_
     return launched(launch_encoder_fused(nullptr, h_out, B, M, nlayers, norm, eps, layers, cache, init, (hipStream_t)stream), what);
 }
 
+// ---- opt-in 16-bit fused encoder (encoder_fused16.hip): the layers of nn/graph/attnnet.py:16-103 and the cache of
+//      zoo/am/decoder.py:206-235 on 16-bit MFMA operands; argument rules of the fp32 entry points above
+
+static bool dtype16_ok(int dtype) { return dtype == EAMRL_DTYPE_F16 || dtype == EAMRL_DTYPE_BF16; }
+
+__attribute__((visibility("default"))) int eamrl_pack_linear_weight16(const float* W, uint16_t* Wp, int out_dim, int in_dim,
+                                                                     int dtype, void* stream)
+{
+    REQUIRE(W && Wp && out_dim > 0 && in_dim > 0 && out_dim % 16 == 0 && in_dim % 32 == 0 && dtype16_ok(dtype),
+            "eamrl_pack_linear_weight16");
+    return launched(launch_pack_mfma_b16(W, Wp, out_dim, in_dim, dtype, (hipStream_t)stream), "eamrl_pack_linear_weight16");
+}
+
+__attribute__((visibility("default"))) int eamrl_encoder_fused16_supported(int M, int E, int H, int ff_hidden, int nlayers, int dtype)
+{
+    return (dtype16_ok(dtype) && encoder_fused_supports(M, E, H, ff_hidden, nlayers)) ? 1 : 0;
+}
+
+__attribute__((visibility("default"))) int eamrl_encoder_fused16(const float* h_in, float* h_out, int64_t B, int M, int E, int H,
+                                                                int ff_hidden, int nlayers, int norm, float eps,
+                                                                const eamrl_encoder_layer* layers,
+                                                                const eamrl_encoder_cache* cache, int dtype, void* stream)
+{
+    const char* what = "eamrl_encoder_fused16";
+    REQUIRE(dtype16_ok(dtype), what);
+    if (int rc = check_encoder_fused(B, M, E, H, ff_hidden, nlayers, norm, layers, cache, what)) return rc;
+    REQUIRE(h_in && h_out, what);
+    REQUIRE(((uintptr_t)h_in % 16 == 0) && ((uintptr_t)h_out % 16 == 0), what);
+    return launched(launch_encoder_fused16(h_in, h_out, B, M, nlayers, norm, eps, layers, cache, nullptr, dtype, (hipStream_t)stream),
+                    what);
+}
+
+__attribute__((visibility("default"))) int eamrl_encoder_fused16_init(const eamrl_encoder_init* init, float* h_out, int64_t B,
+                                                                     int M, int E, int H, int ff_hidden, int nlayers, int norm,
+                                                                     float eps, const eamrl_encoder_layer* layers,
+                                                                     const eamrl_encoder_cache* cache, int dtype, void* stream)
+{
+    const char* what = "eamrl_encoder_fused16_init";
+    REQUIRE(dtype16_ok(dtype), what);
+    if (int rc = check_encoder_fused(B, M, E, H, ff_hidden, nlayers, norm, layers, cache, what)) return rc;
+    REQUIRE(init && init->feat && init->W && init->F >= 1 && init->F <= 8, what);
+    REQUIRE(!init->depot || (init->Wd && init->depot_ld >= 2), what);
+    REQUIRE(h_out || cache, what);
+    REQUIRE((!h_out || (uintptr_t)h_out % 16 == 0) && (!init->init_out || (uintptr_t)init->init_out % 16 == 0), what);
+    return launched(launch_encoder_fused16(nullptr, h_out, B, M, nlayers, norm, eps, layers, cache, init, dtype, (hipStream_t)stream),
+                    what);
+}
+
 static int check_reeval(const eamrl_reeval* p, const char* what, bool bwd)
 {
     REQUIRE(p, what);

@@ -47,6 +47,11 @@ int launch_encoder_fused(const float* h_in, float* h_out, int64_t B, int M, int 
                          const eamrl_encoder_layer* layers, const eamrl_encoder_cache* cache, const eamrl_encoder_init* init,
                          hipStream_t st);
 int launch_pack_mfma_b(const float* W, float* Wp, int N, int K, hipStream_t st);
+// opt-in 16-bit fused encoder (encoder_fused16.hip); dtype EAMRL_DTYPE_F16 / EAMRL_DTYPE_BF16
+int launch_pack_mfma_b16(const float* W, void* Wp, int N, int K, int dtype, hipStream_t st);
+int launch_encoder_fused16(const float* h_in, float* h_out, int64_t B, int M, int nlayers, int norm, float eps,
+                           const eamrl_encoder_layer* layers, const eamrl_encoder_cache* cache, const eamrl_encoder_init* init,
+                           int dtype, hipStream_t st);
 // BatchNorm-train backward and the tiny-K Linear weight gradient (train_norm.hip)
 int64_t batchnorm_backward_scratch(int64_t rows, int E);
 int launch_batchnorm_backward(const float* x, const float* dy, const float* mean, const float* var, const float* gamma, float eps,

@@ -324,6 +324,52 @@ def encoder_fused(h, layers, num_heads, ff_hidden, norm, eps, cache=None, init=N
     init (instead of h; struct eamrl_encoder_init) = dict(feat [B, M, F], W [E, F], b, depot [B, >= 2] or None, Wd, bd,
     want_init): the init embedding is computed inside the kernel; returns (hidden or None, init embeddings or None) then.
     store_hidden=False (with init and cache): the node embeddings never leave LDS."""
+    return _encoder_fused_call(h, layers, num_heads, ff_hidden, norm, eps, cache, init, store_hidden, None)
+
+
+# packed 16-bit weights: the torch dtype of the buffer names the operand type of the kernel
+DTYPE16 = {torch.float16: 1, torch.bfloat16: 2}      # EAMRL_DTYPE_F16, EAMRL_DTYPE_BF16
+
+
+def pack_linear_weight16(W, dtype, out=None):
+    """torch.nn.Linear.weight [out, in] (fp32) -> rounded to `dtype` (torch.float16 / torch.bfloat16, round to nearest
+    even) in the 16-bit MFMA fragment order of the 16-bit fused encoder (eamrl_pack_linear_weight16)."""
+    lib = _lib.load()
+    if dtype not in DTYPE16:
+        raise ValueError(f"pack_linear_weight16: dtype must be torch.float16 or torch.bfloat16, got {dtype}")
+    _chk(W, "weight", torch.float32)
+    N, K = W.shape
+    if N % 16 or K % 32:
+        raise ValueError("pack_linear_weight16: out_dim must be a multiple of 16 and in_dim of 32")
+    if out is None:
+        out = torch.empty(N * K, device=W.device, dtype=dtype)
+    _chk(out, "packed weight", dtype, (N * K,))
+    _lib.check(lib.eamrl_pack_linear_weight16(_ptr(W), _ptr(out), N, K, DTYPE16[dtype], _stream(W)), "eamrl_pack_linear_weight16")
+    return out
+
+
+def encoder_fused16_supported(M, E, H, ff_hidden, nlayers, dtype=torch.bfloat16) -> bool:
+    if dtype not in DTYPE16:
+        return False
+    return bool(_lib.load().eamrl_encoder_fused16_supported(int(M), int(E), int(H), int(ff_hidden), int(nlayers), DTYPE16[dtype]))
+
+
+def encoder_fused16(h, layers, num_heads, ff_hidden, norm, eps, dtype, cache=None, init=None, store_hidden=True):
+    """`encoder_fused` with 16-bit MFMA operands ("16-bit encoder"): the weights Wqkv / Wo / W1 / W2 of every
+    layer and the cache's Wc / WoutT are `pack_linear_weight16` buffers of `dtype` (torch.float16 / torch.bfloat16); all
+    other arguments, the inputs and the outputs are fp32 and as for `encoder_fused`.  No autograd."""
+    if dtype not in DTYPE16:
+        raise ValueError(f"encoder_fused16: dtype must be torch.float16 or torch.bfloat16, got {dtype}")
+    return _encoder_fused_call(h, layers, num_heads, ff_hidden, norm, eps, cache, init, store_hidden, dtype)
+
+
+_PACKED_FIELDS = ("Wqkv", "Wo", "W1", "W2")
+
+
+def _encoder_fused_call(h, layers, num_heads, ff_hidden, norm, eps, cache, init, store_hidden, dtype):
+    """encoder_fused (dtype None) / encoder_fused16 (dtype = the packed weights' torch dtype)."""
+    what = "encoder_fused" if dtype is None else "encoder_fused16"
+    wdt = torch.float32 if dtype is None else dtype
     lib = _lib.load()
     if init is not None:
         feat = init["feat"]
@@ -343,26 +389,27 @@ def encoder_fused(h, layers, num_heads, ff_hidden, norm, eps, cache=None, init=N
             t = d.get(name)
             if t is not None:
                 _need_gpu(t, name)
-                if t.dtype != torch.float32 or not t.is_contiguous():
-                    raise TypeError(f"encoder_fused: {name} must be contiguous fp32")
+                want = wdt if name in _PACKED_FIELDS else torch.float32
+                if t.dtype != want or not t.is_contiguous():
+                    raise TypeError(f"{what}: {name} must be contiguous {want}")
             setattr(arr[i], name, _ptr(t))
     out = torch.empty(B, M, E, dtype=torch.float32, device=dev) if (store_hidden or cache is None) else None
     cstruct = None
     if cache is not None:
         Wc, WoT, buf, nproj = cache[:4]
         Wg, gctx = cache[4:6] if len(cache) >= 6 else (None, None)
-        _chk(Wc, "packed cache weights", torch.float32, (nproj * E * E,))
-        _chk(WoT, "packed project_out^T", torch.float32, (E * E,))
+        _chk(Wc, "packed cache weights", wdt, (nproj * E * E,))
+        _chk(WoT, "packed project_out^T", wdt, (E * E,))
         _chk(buf, "decoder cache", torch.float32)
         if buf.dim() != 3 or buf.shape[0] != B or buf.shape[1] != M or buf.shape[2] < (nproj + 1) * E:
-            raise ValueError("encoder_fused: cache buffer must be [B, M, >= (nproj + 1) * E]")
+            raise ValueError(f"{what}: cache buffer must be [B, M, >= (nproj + 1) * E]")
         cs = _lib.EncoderCache()
         cs.Wc, cs.WoutT, cs.out, cs.ld, cs.nproj = _ptr(Wc), _ptr(WoT), _ptr(buf), buf.shape[2], int(nproj)
         if Wg is not None:
             _chk(Wg, "project_fixed_context.weight", torch.float32, (E, E))
             _chk(gctx, "graph context", torch.float32, (B, E))
             if Wg.data_ptr() % 16:
-                raise ValueError("encoder_fused: Wg must be 16-byte aligned")
+                raise ValueError(f"{what}: Wg must be 16-byte aligned")
             cs.Wg, cs.gctx = _ptr(Wg), _ptr(gctx)
         cstruct = C.byref(cs)
     if init is not None:
@@ -372,19 +419,29 @@ def encoder_fused(h, layers, num_heads, ff_hidden, norm, eps, cache=None, init=N
             if t is not None:
                 _need_gpu(t, name)
                 if t.dtype != torch.float32:
-                    raise TypeError(f"encoder_fused: {name} must be fp32")
+                    raise TypeError(f"{what}: {name} must be fp32")
         if depot is not None and (depot.dim() != 2 or depot.stride(1) != 1 or depot.shape[0] != B or Wd is None or not Wd.is_contiguous()):
-            raise ValueError("encoder_fused: depot must be [B, >= 2] with unit inner stride, Wd [E, 2] contiguous")
+            raise ValueError(f"{what}: depot must be [B, >= 2] with unit inner stride, Wd [E, 2] contiguous")
         init_out = torch.empty(B, M, E, dtype=torch.float32, device=dev) if init.get("want_init") else None
         ist.feat, ist.F, ist.W, ist.b = _ptr(feat), int(F), _ptr(W), _ptr(b)
         ist.depot, ist.depot_ld = _ptr(depot), (depot.stride(0) if depot is not None else 0)
         ist.Wd, ist.bd, ist.init_out = _ptr(Wd), _ptr(bd), _ptr(init_out)
-        _lib.check(lib.eamrl_encoder_fused_init(C.byref(ist), _ptr(out), B, M, E, int(num_heads), int(ff_hidden), len(layers),
-                                                int(norm), float(eps), C.cast(arr, C.c_void_p), cstruct, _stream(feat)),
-                   "eamrl_encoder_fused_init")
+        if dtype is None:
+            _lib.check(lib.eamrl_encoder_fused_init(C.byref(ist), _ptr(out), B, M, E, int(num_heads), int(ff_hidden), len(layers),
+                                                    int(norm), float(eps), C.cast(arr, C.c_void_p), cstruct, _stream(feat)),
+                       "eamrl_encoder_fused_init")
+        else:
+            _lib.check(lib.eamrl_encoder_fused16_init(C.byref(ist), _ptr(out), B, M, E, int(num_heads), int(ff_hidden),
+                                                      len(layers), int(norm), float(eps), C.cast(arr, C.c_void_p), cstruct,
+                                                      DTYPE16[dtype], _stream(feat)), "eamrl_encoder_fused16_init")
         return out, init_out
-    _lib.check(lib.eamrl_encoder_fused(_ptr(h), _ptr(out), B, M, E, int(num_heads), int(ff_hidden), len(layers), int(norm),
-                                       float(eps), C.cast(arr, C.c_void_p), cstruct, _stream(h)), "eamrl_encoder_fused")
+    if dtype is None:
+        _lib.check(lib.eamrl_encoder_fused(_ptr(h), _ptr(out), B, M, E, int(num_heads), int(ff_hidden), len(layers), int(norm),
+                                           float(eps), C.cast(arr, C.c_void_p), cstruct, _stream(h)), "eamrl_encoder_fused")
+    else:
+        _lib.check(lib.eamrl_encoder_fused16(_ptr(h), _ptr(out), B, M, E, int(num_heads), int(ff_hidden), len(layers), int(norm),
+                                             float(eps), C.cast(arr, C.c_void_p), cstruct, DTYPE16[dtype], _stream(h)),
+                   "eamrl_encoder_fused16")
     return out
 
 

@@ -28,6 +28,9 @@ log = logging.getLogger(__name__)
 
 DECODE_TYPES = ("greedy", "sampling", "multistart_greedy", "multistart_sampling", "evaluate")
 
+# AttentionModelPolicy(precision=...): Lightning's names -> the operand type of the fused encoder (None = fp32)
+PRECISIONS = {"32-true": None, "16-mixed": torch.float16, "bf16-mixed": torch.bfloat16}
+
 
 # envs that share kernels, embeddings and state layout with another one: SPCTSP is PCTSP whose collected prize is the
 # stochastic one (the policy sees the expected prize either way)
@@ -247,6 +250,7 @@ class GraphAttentionNetwork(nn.Module):
         super().__init__()
         self.layers = nn.Sequential(*(MultiHeadAttentionLayer(embed_dim, num_heads, feedforward_hidden, normalization)
                                       for _ in range(num_layers)))
+        self.dtype16 = None     # torch.float16 / torch.bfloat16: the fused kernel runs on 16-bit operands (policy.precision)
 
     def forward(self, x, mask=None, cache_spec=None, init=None, store_hidden=True, fused=None):
         """cache_spec (optional, from AttentionModelDecoder._fused_cache_spec): the fused kernel also fills the decoder cache
@@ -258,13 +262,18 @@ class GraphAttentionNetwork(nn.Module):
             assert init is None, "init= needs the fused kernel (check _fused_layers first)"
             fused = self._fused_layers(x)
         if fused is not None:       # all layers of an instance in one workgroup, activations resident in LDS
-            layers, H, ff, norm, eps = fused
+            layers, H, ff, norm, eps, dtype = fused
             cache = None
             if cache_spec is not None:
+                if cache_spec.get("dtype") != dtype:
+                    raise RuntimeError("fused encoder: the decoder cache spec was packed for another precision")
                 cache = (cache_spec["Wc"], cache_spec["WoT"], cache_spec["buf"], cache_spec["nproj"], cache_spec.get("Wg"),
                          cache_spec.get("gctx"))
-            out = ops.encoder_fused(None if init is not None else x.contiguous(), layers, H, ff, norm, eps, cache=cache,
-                                    init=init, store_hidden=store_hidden)
+            h = None if init is not None else x.contiguous()
+            if dtype is None:
+                out = ops.encoder_fused(h, layers, H, ff, norm, eps, cache=cache, init=init, store_hidden=store_hidden)
+            else:
+                out = ops.encoder_fused16(h, layers, H, ff, norm, eps, dtype, cache=cache, init=init, store_hidden=store_hidden)
             if cache_spec is not None:
                 cache_spec["filled"] = True
             return out
@@ -273,9 +282,12 @@ class GraphAttentionNetwork(nn.Module):
         return x
 
     def _fused_layers(self, x, shape=None):
-        """Arguments of `ops.encoder_fused` when the fused kernel covers this network (eval-mode batch norm or instance
-        norm, E = 128, 8 heads, one hidden layer of 512, graphs up to 112 nodes), else None.  The packed weights live in
-        persistent buffers refreshed in place when a parameter changes (a captured HIP graph keeps reading them)."""
+        """(layers, heads, ff_hidden, norm, eps, dtype): the arguments of `ops.encoder_fused` (dtype None) or
+        `ops.encoder_fused16` (dtype = self.dtype16) when the fused kernel covers this network (eval-mode batch norm or
+        instance norm, E = 128, 8 heads, one hidden layer of 512, graphs up to 112 nodes), else None.  The packed weights
+        live in persistent buffers refreshed in place when a parameter changes (a captured HIP graph keeps reading them);
+        16-bit packs have slots of their own per (layer, weight, dtype).  Outside that coverage (M > 112, batch norm in
+        training mode, EAMRL_FUSED_ENCODER=0) the fp32 layer-by-layer path runs, whatever dtype16 says."""
         if os.environ.get("EAMRL_FUSED_ENCODER", "1") == "0" or len(self.layers) == 0:
             return None
         first = self.layers[0]
@@ -297,6 +309,7 @@ class GraphAttentionNetwork(nn.Module):
         else:
             norm = ops.NORM_INSTANCE
         packed = self.__dict__.setdefault("_packed", {})
+        dtype = self.dtype16
         out = []
         for li, layer in enumerate(self.layers):
             mha, ffn = layer[0].module, layer[2].module
@@ -308,10 +321,13 @@ class GraphAttentionNetwork(nn.Module):
             for name, lin in (("Wqkv", mha.Wqkv), ("Wo", mha.out_proj), ("W1", ffn.lins[0]), ("W2", ffn.lins[1])):
                 w = lin.weight
                 key = (w.data_ptr(), w._version, w.device)
-                slot = packed.get((li, name))
+                slot = packed.get((li, name) if dtype is None else (li, name, dtype))
                 if slot is None or slot[0] != key:
                     buf = None if slot is None or slot[1].device != w.device else slot[1]
-                    packed[(li, name)] = slot = (key, ops.pack_linear_weight(w.detach().contiguous(), out=buf))
+                    if dtype is None:
+                        packed[(li, name)] = slot = (key, ops.pack_linear_weight(w.detach().contiguous(), out=buf))
+                    else:
+                        packed[(li, name, dtype)] = slot = (key, ops.pack_linear_weight16(w.detach().contiguous(), dtype, out=buf))
                 d[name] = slot[1]
             d.update(bqkv=mha.Wqkv.bias.detach(), bo=mha.out_proj.bias.detach(), b1=ffn.lins[0].bias.detach(),
                      b2=ffn.lins[1].bias.detach(), n1_gamma=n1.weight.detach(), n1_beta=n1.bias.detach(),
@@ -319,7 +335,7 @@ class GraphAttentionNetwork(nn.Module):
             if norm == ops.NORM_BATCH_EVAL:
                 d.update(n1_mean=n1.running_mean, n1_var=n1.running_var, n2_mean=n2.running_mean, n2_var=n2.running_var)
             out.append(d)
-        return out, H, ff, norm, n0.eps
+        return out, H, ff, norm, n0.eps, dtype
 
 
 class AttentionModelEncoder(nn.Module):
@@ -420,9 +436,10 @@ class AttentionModelDecoder(nn.Module):
         self.project_fixed_context = nn.Linear(embed_dim, embed_dim, bias=False)
         self.use_graph_context = use_graph_context
 
-    def _fused_cache_spec(self, B: int, M: int, device):
+    def _fused_cache_spec(self, B: int, M: int, device, dtype=None):
         """What the fused encoder kernel needs to fill the slot-major cache itself (K | V | L | Pa (| Pb) projections of the
-        final embeddings + Lp = L Wout), or None where that layout is not used (graphs above 128 nodes: plane-major)."""
+        final embeddings + Lp = L Wout), or None where that layout is not used (graphs above 128 nodes: plane-major).
+        dtype (torch.float16 / torch.bfloat16): Wc / WoT are the 16-bit packs of the 16-bit fused encoder."""
         if M > 128 or os.environ.get("EAMRL_FUSED_CACHE", "1") == "0":
             return None
         E = self.embed_dim
@@ -431,14 +448,25 @@ class AttentionModelDecoder(nn.Module):
         nproj = 5 if self.env_name == "tsp" else 4
         Wout = self.pointer.project_out.weight
         key = (self._wc_key, Wout.data_ptr(), Wout._version)
-        if getattr(self, "_fc_key", None) != key:
-            old = getattr(self, "_fc", None)
-            keep = old is not None and old[0].device == self._w_cache.device and old[0].numel() == self._w_cache.numel()
-            Wc = ops.pack_linear_weight(self._w_cache, out=old[0] if keep else None)
-            WoT = ops.pack_linear_weight(Wout.detach().t().contiguous(), out=old[1] if keep else None)
-            self._fc, self._fc_key = (Wc, WoT), key
+        if dtype is not None:       # 16-bit packs: slots of their own per dtype, refreshed in place like the fp32 ones
+            fc16 = self.__dict__.setdefault("_fc16", {})
+            old = fc16.get(dtype)
+            if old is None or old[0] != key:
+                keep = old is not None and old[1].device == self._w_cache.device and old[1].numel() == self._w_cache.numel()
+                Wc = ops.pack_linear_weight16(self._w_cache, dtype, out=old[1] if keep else None)
+                WoT = ops.pack_linear_weight16(Wout.detach().t().contiguous(), dtype, out=old[2] if keep else None)
+                fc16[dtype] = (key, Wc, WoT)
+            packs = fc16[dtype][1:]
+        else:
+            if getattr(self, "_fc_key", None) != key:
+                old = getattr(self, "_fc", None)
+                keep = old is not None and old[0].device == self._w_cache.device and old[0].numel() == self._w_cache.numel()
+                Wc = ops.pack_linear_weight(self._w_cache, out=old[0] if keep else None)
+                WoT = ops.pack_linear_weight(Wout.detach().t().contiguous(), out=old[1] if keep else None)
+                self._fc, self._fc_key = (Wc, WoT), key
+            packs = self._fc
         buf = torch.empty(B, M, len(slots) * E, device=device, dtype=torch.float32)
-        spec = {"buf": buf, "Wc": self._fc[0], "WoT": self._fc[1], "nproj": nproj, "filled": False}
+        spec = {"buf": buf, "Wc": packs[0], "WoT": packs[1], "nproj": nproj, "filled": False, "dtype": dtype}
         Wg = self.project_fixed_context.weight if self.use_graph_context else None
         if Wg is not None and Wg.is_contiguous() and Wg.data_ptr() % 16 == 0 and B > 0:     # the live parameter: nothing to refresh
             spec["Wg"], spec["gctx"] = Wg.detach(), torch.empty(B, E, device=device, dtype=torch.float32)
@@ -681,7 +709,7 @@ class AttentionModelPolicy(nn.Module):
                  mask_inner: bool = True, out_bias_pointer_attn: bool = False, check_nan: bool = True,
                  temperature: float = 1.0, tanh_clipping: float = 10.0, mask_logits: bool = True,
                  train_decode_type: str = "sampling", val_decode_type: str = "greedy",
-                 test_decode_type: str = "greedy", moe_kwargs: dict = None, **unused_kwargs):
+                 test_decode_type: str = "greedy", moe_kwargs: dict = None, precision: str = "32-true", **unused_kwargs):
         super().__init__()
         if unused_kwargs:
             log.error("Found %d unused kwargs: %s", len(unused_kwargs), unused_kwargs)
@@ -708,6 +736,31 @@ class AttentionModelPolicy(nn.Module):
         self.temperature, self.tanh_clipping, self.mask_logits = temperature, tanh_clipping, mask_logits
         self.train_decode_type, self.val_decode_type, self.test_decode_type = (
             train_decode_type, val_decode_type, test_decode_type)
+        self.precision = precision
+
+    @property
+    def precision(self) -> str:
+        """Operand precision of the fused encoder in rollouts that build no autograd graph, by Lightning's names:
+        "32-true" (default, fp32 MFMA, bit-exact), "16-mixed" (fp16 operands) or "bf16-mixed" (bf16 operands), fp32
+        accumulation either way.  A plain attribute: not in the state_dict, kept by copy.deepcopy.
+        Training (forward with autograd in phase "train") needs "32-true"."""
+        return self.__dict__["_precision"]
+
+    @precision.setter
+    def precision(self, value: str):
+        if value not in PRECISIONS:
+            raise ValueError(f"precision={value!r}: expected one of {sorted(PRECISIONS)}")
+        dtype = PRECISIONS[value]
+        net = getattr(self.encoder, "net", None)
+        if isinstance(net, GraphAttentionNetwork):
+            net.dtype16 = dtype
+        elif dtype is not None:
+            raise NotImplementedError("precision: 16-bit operands need the built-in GraphAttentionNetwork encoder")
+        self.__dict__["_precision"] = value
+
+    @property
+    def _dtype16(self):
+        return PRECISIONS[self.__dict__["_precision"]]
 
     def forward(self, td, env: Optional[str | RL4COEnvBase] = None, phase: str = "train", calc_reward: bool = True,
                 return_actions: bool = True, return_entropy: bool = False, return_hidden: bool = False,
@@ -726,6 +779,10 @@ class AttentionModelPolicy(nn.Module):
         test phases run under no_grad in the reference's trainers and are not re-evaluated here."""
         want_grad = (torch.is_grad_enabled() and phase == "train" and not torch.is_inference_mode_enabled()
                      and any(q.requires_grad for q in self._parameter_list()))
+        if want_grad and self._dtype16 is not None:
+            raise NotImplementedError(f"precision={self.precision!r}: 16-bit training is not built (the backward re-uses the "
+                                      "rollout's log-probabilities, which need the fp32 encoder); use precision='32-true', "
+                                      "or run the rollout under torch.no_grad()")
         self._want_heads = want_grad and os.environ.get("EAMRL_REEVAL_RECOMPUTE_HEADS", "0") != "1"
         own_shared = False
         try:
@@ -870,7 +927,7 @@ class AttentionModelPolicy(nn.Module):
         spec = None
         if isinstance(self.encoder, AttentionModelEncoder) and isinstance(self.decoder, AttentionModelDecoder):
             Bq, Mq = td["action_mask"].shape
-            spec = self.decoder._fused_cache_spec(Bq, Mq, td["action_mask"].device)
+            spec = self.decoder._fused_cache_spec(Bq, Mq, td["action_mask"].device, dtype=self._dtype16)
         shared, ekey, ent = getattr(self, "_shared_dt", None), None, None
         if shared is not None and spec is not None:     # train.shared_decoder_tensors: same instances, same parameters
             from .train import _graph_key
@@ -1318,6 +1375,7 @@ class GraphedRollout:
         self.kw.update(forward_kwargs)
         self.static_td = td_example.clone()
         self._training = policy.training
+        self._precision = policy.precision
         M = td_example["action_mask"].shape[1]
         self._embed_probe = torch.empty(1, M, policy.decoder.embed_dim, device=td_example["action_mask"].device)
         self._keys = [k for k, v in self.static_td.items() if isinstance(v, torch.Tensor)]
@@ -1346,6 +1404,9 @@ class GraphedRollout:
     def __call__(self, td) -> dict:
         if self.policy.training != self._training:
             raise RuntimeError("GraphedRollout: policy.train() / .eval() changed since capture (different launches)")
+        if self.policy.precision != self._precision:
+            raise RuntimeError(f"GraphedRollout: policy.precision changed since capture ({self._precision!r} -> "
+                               f"{self.policy.precision!r}: different kernels)")
         # weight-derived constants live in persistent buffers that the graph reads: refresh them in place when a
         # parameter changed (optimizer step, load_state_dict); everything else the graph reads are the live parameters.
         # One pass over the version counters decides whether anything has to be looked at.
@@ -1353,9 +1414,11 @@ class GraphedRollout:
         if sig != self._sig:
             self._sig = sig
             self.policy.decoder._weight_constants()
-            if hasattr(self.policy.decoder, "_fused_cache_spec") and getattr(self.policy.decoder, "_fc", None) is not None:
+            dec, dtype = self.policy.decoder, self.policy._dtype16
+            if hasattr(dec, "_fused_cache_spec") and (getattr(dec, "_fc", None) if dtype is None
+                                                      else getattr(dec, "_fc16", {}).get(dtype)) is not None:
                 M = self._embed_probe.shape[1]
-                self.policy.decoder._fused_cache_spec(0, M, self._embed_probe.device)     # re-packs in place when weights changed
+                dec._fused_cache_spec(0, M, self._embed_probe.device, dtype=dtype)    # re-packs in place when weights changed
             net = getattr(self.policy.encoder, "net", None)
             if hasattr(net, "_fused_layers"):
                 net._fused_layers(self._embed_probe)          # re-packs changed encoder weights into the buffers the graph reads

@@ -45,6 +45,9 @@ extern "C" {
 /* normalisation kinds  [rl4co/models/nn/ops.py:32-56] */
 #define EAMRL_NORM_BATCH_EVAL 0
 #define EAMRL_NORM_INSTANCE 1
+/* 16-bit operand types of the opt-in reduced-precision encoder (eamrl_encoder_fused16) */
+#define EAMRL_DTYPE_F16 1
+#define EAMRL_DTYPE_BF16 2
 
 /* host-side rejections */
 #define EAMRL_E_ARG (-1)     /* bad size / null pointer / unsupported shape */
@@ -297,6 +300,35 @@ int eamrl_encoder_fused(const float* h_in, float* h_out, int64_t B, int M, int E
 int eamrl_encoder_fused_init(const eamrl_encoder_init* init, float* h_out /* may be NULL */, int64_t B, int M, int E, int H,
                              int ff_hidden, int nlayers, int norm, float eps, const eamrl_encoder_layer* layers,
                              const eamrl_encoder_cache* cache /* may be NULL */, void* stream);
+
+/* ---- opt-in 16-bit fused encoder (no-grad rollouts; DESIGN.md 2 "16-bit encoder") ------------------------------------ */
+
+/* Wp = W [out_dim][in_dim] rounded to fp16 / bf16 (dtype EAMRL_DTYPE_F16 / EAMRL_DTYPE_BF16, round to nearest even) and
+ * re-ordered for eamrl_encoder_fused16: block (ct, u) of 512 elements holds, for lane l = 16 g + j of a wavefront, the
+ * 8 values { W[16 ct + j][32 u + 8 g + e] : e = 0..7 } -- the weight operand of one v_mfma_f32_16x16x32 k-step.
+ * out_dim a multiple of 16, in_dim of 32; Wp holds out_dim * in_dim 16-bit values.  Redo after every weight update.
+ * Replaces, for the 16-bit path, the fp32 packing of eamrl_pack_linear_weight (the weights of nn/graph/attnnet.py:16-57 and
+ * zoo/am/decoder.py:206-235). */
+int eamrl_pack_linear_weight16(const float* W, uint16_t* Wp, int out_dim, int in_dim, int dtype, void* stream);
+
+/* 1 if eamrl_encoder_fused16 handles this shape and dtype (the shapes of eamrl_encoder_fused_supported). */
+int eamrl_encoder_fused16_supported(int M, int E, int H, int ff_hidden, int nlayers, int dtype);
+
+/* GraphAttentionNetwork.forward  [nn/graph/attnnet.py:94-103; zoo/am/encoder.py:88-89] and the optional decoder cache
+ * [zoo/am/decoder.py:206-235] as eamrl_encoder_fused, with every Linear (encoder and cache projections) and the attention
+ * products on 16-bit MFMA operands: the layer's Wqkv / Wo / W1 / W2 and the cache's Wc / WoutT point at
+ * eamrl_pack_linear_weight16 buffers of the same dtype; biases, normalisation parameters, Wg, inputs and outputs are fp32.
+ * Accumulation, softmax, residuals and normalisation are fp32.  Not bit-identical to eamrl_encoder_fused.
+ * fp16 has no loss scaling: an activation outside the fp16 range gives inf / NaN. */
+int eamrl_encoder_fused16(const float* h_in, float* h_out, int64_t B, int M, int E, int H, int ff_hidden, int nlayers, int norm,
+                          float eps, const eamrl_encoder_layer* layers, const eamrl_encoder_cache* cache /* may be NULL */,
+                          int dtype, void* stream);
+
+/* AttentionModelEncoder.forward in one launch  [zoo/am/encoder.py:70-91] with the 16-bit layers of eamrl_encoder_fused16.
+ * The init embedding (and init_out) and the graph context are computed in fp32 exactly as by eamrl_encoder_fused_init. */
+int eamrl_encoder_fused16_init(const eamrl_encoder_init* init, float* h_out /* may be NULL */, int64_t B, int M, int E, int H,
+                               int ff_hidden, int nlayers, int norm, float eps, const eamrl_encoder_layer* layers,
+                               const eamrl_encoder_cache* cache /* may be NULL */, int dtype, void* stream);
 
 /* out[b][e] = (sum_n emb[b][n][e]) / M   (embeddings.mean(1), zoo/am/decoder.py:225-227) */
 int eamrl_mean_nodes(const float* emb, float* out, int64_t B, int M, int E, void* stream);
