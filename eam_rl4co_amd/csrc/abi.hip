@@ -342,8 +342,15 @@ __attribute__((visibility("default"))) int eamrl_augment_xy(const float* xy, con
     return launched(launch_augment_xy(xy, cs, code, out, R, B, N, offset, (hipStream_t)stream), "eamrl_augment_xy");
 }
 
-static int check_encoder_fused(int64_t B, int M, int E, int H, int ff_hidden, int nlayers, int norm,
-                               const eamrl_encoder_layer* layers, const eamrl_encoder_cache* cache, const char* what)
+static bool dtype16_ok(int dtype) { return dtype == EAMRL_DTYPE_F16 || dtype == EAMRL_DTYPE_BF16; }
+
+// The argument checks and the launch of the four fused-encoder entry points: from h_in (init == nullptr) or from the init
+// embedding's inputs (with_init).  dtype: DTYPE_F32 from the fp32 entry points, a 16-bit EAMRL_DTYPE_* that the 16-bit
+// entry points have already checked (a caller's dtype must never select the fp32 kernel: it would read 16-bit packed
+// weights as fp32 fragments, twice their size)
+static int encoder_fused_entry(const float* h_in, const eamrl_encoder_init* init, bool with_init, float* h_out, int64_t B, int M,
+                               int E, int H, int ff_hidden, int nlayers, int norm, float eps, const eamrl_encoder_layer* layers,
+                               const eamrl_encoder_cache* cache, int dtype, void* stream, const char* what)
 {
     if (cache) {
         REQUIRE(cache->Wc && cache->WoutT && cache->out && cache->nproj >= 3 && cache->nproj <= 5, what);
@@ -361,7 +368,17 @@ static int check_encoder_fused(int64_t B, int M, int E, int H, int ff_hidden, in
                     ((uintptr_t)s.W2 % 16 == 0), what);
         if (norm == EAMRL_NORM_BATCH_EVAL) REQUIRE(s.n1_mean && s.n1_var && s.n2_mean && s.n2_var, what);
     }
-    return 0;
+    if (with_init) {
+        REQUIRE(init && init->feat && init->W && init->F >= 1 && init->F <= 8, what);
+        REQUIRE(!init->depot || (init->Wd && init->depot_ld >= 2), what);
+        REQUIRE(h_out || cache, what);          // something must leave the kernel
+        REQUIRE((!h_out || (uintptr_t)h_out % 16 == 0) && (!init->init_out || (uintptr_t)init->init_out % 16 == 0), what);
+    } else {
+        REQUIRE(h_in && h_out, what);
+        REQUIRE(((uintptr_t)h_in % 16 == 0) && ((uintptr_t)h_out % 16 == 0), what);
+    }
+    return launched(launch_encoder_fused(h_in, h_out, B, M, nlayers, norm, eps, layers, cache, init, dtype, (hipStream_t)stream),
+                    what);
 }
 
 __attribute__((visibility("default"))) int eamrl_encoder_fused(const float* h_in, float* h_out, int64_t B, int M, int E, int H,
@@ -369,11 +386,8 @@ __attribute__((visibility("default"))) int eamrl_encoder_fused(const float* h_in
                                                               const eamrl_encoder_layer* layers,
                                                               const eamrl_encoder_cache* cache, void* stream)
 {
-    if (int rc = check_encoder_fused(B, M, E, H, ff_hidden, nlayers, norm, layers, cache, "eamrl_encoder_fused")) return rc;
-    REQUIRE(h_in && h_out, "eamrl_encoder_fused");
-    REQUIRE(((uintptr_t)h_in % 16 == 0) && ((uintptr_t)h_out % 16 == 0), "eamrl_encoder_fused");
-    return launched(launch_encoder_fused(h_in, h_out, B, M, nlayers, norm, eps, layers, cache, nullptr, (hipStream_t)stream),
-                    "eamrl_encoder_fused");
+    return encoder_fused_entry(h_in, nullptr, false, h_out, B, M, E, H, ff_hidden, nlayers, norm, eps, layers, cache, DTYPE_F32,
+                               stream, "eamrl_encoder_fused");
 }
 
 __attribute__((visibility("default"))) int eamrl_encoder_fused_init(const eamrl_encoder_init* init, float* h_out, int64_t B, int M,
@@ -381,19 +395,12 @@ __attribute__((visibility("default"))) int eamrl_encoder_fused_init(const eamrl_
                                                                    const eamrl_encoder_layer* layers,
                                                                    const eamrl_encoder_cache* cache, void* stream)
 {
-    const char* what = "eamrl_encoder_fused_init";
-    if (int rc = check_encoder_fused(B, M, E, H, ff_hidden, nlayers, norm, layers, cache, what)) return rc;
-    REQUIRE(init && init->feat && init->W && init->F >= 1 && init->F <= 8, what);
-    REQUIRE(!init->depot || (init->Wd && init->depot_ld >= 2), what);
-    REQUIRE(h_out || cache, what);          // something must leave the kernel
-    REQUIRE((!h_out || (uintptr_t)h_out % 16 == 0) && (!init->init_out || (uintptr_t)init->init_out % 16 == 0), what);
-    return launched(launch_encoder_fused(nullptr, h_out, B, M, nlayers, norm, eps, layers, cache, init, (hipStream_t)stream), what);
+    return encoder_fused_entry(nullptr, init, true, h_out, B, M, E, H, ff_hidden, nlayers, norm, eps, layers, cache, DTYPE_F32,
+                               stream, "eamrl_encoder_fused_init");
 }
 
 // ---- opt-in 16-bit fused encoder (encoder_fused16.hip): the layers of nn/graph/attnnet.py:16-103 and the cache of
 //      zoo/am/decoder.py:206-235 on 16-bit MFMA operands; argument rules of the fp32 entry points above
-
-static bool dtype16_ok(int dtype) { return dtype == EAMRL_DTYPE_F16 || dtype == EAMRL_DTYPE_BF16; }
 
 __attribute__((visibility("default"))) int eamrl_pack_linear_weight16(const float* W, uint16_t* Wp, int out_dim, int in_dim,
                                                                      int dtype, void* stream)
@@ -413,13 +420,9 @@ __attribute__((visibility("default"))) int eamrl_encoder_fused16(const float* h_
                                                                 const eamrl_encoder_layer* layers,
                                                                 const eamrl_encoder_cache* cache, int dtype, void* stream)
 {
-    const char* what = "eamrl_encoder_fused16";
-    REQUIRE(dtype16_ok(dtype), what);
-    if (int rc = check_encoder_fused(B, M, E, H, ff_hidden, nlayers, norm, layers, cache, what)) return rc;
-    REQUIRE(h_in && h_out, what);
-    REQUIRE(((uintptr_t)h_in % 16 == 0) && ((uintptr_t)h_out % 16 == 0), what);
-    return launched(launch_encoder_fused16(h_in, h_out, B, M, nlayers, norm, eps, layers, cache, nullptr, dtype, (hipStream_t)stream),
-                    what);
+    REQUIRE(dtype16_ok(dtype), "eamrl_encoder_fused16");
+    return encoder_fused_entry(h_in, nullptr, false, h_out, B, M, E, H, ff_hidden, nlayers, norm, eps, layers, cache, dtype, stream,
+                               "eamrl_encoder_fused16");
 }
 
 __attribute__((visibility("default"))) int eamrl_encoder_fused16_init(const eamrl_encoder_init* init, float* h_out, int64_t B,
@@ -427,15 +430,9 @@ __attribute__((visibility("default"))) int eamrl_encoder_fused16_init(const eamr
                                                                      float eps, const eamrl_encoder_layer* layers,
                                                                      const eamrl_encoder_cache* cache, int dtype, void* stream)
 {
-    const char* what = "eamrl_encoder_fused16_init";
-    REQUIRE(dtype16_ok(dtype), what);
-    if (int rc = check_encoder_fused(B, M, E, H, ff_hidden, nlayers, norm, layers, cache, what)) return rc;
-    REQUIRE(init && init->feat && init->W && init->F >= 1 && init->F <= 8, what);
-    REQUIRE(!init->depot || (init->Wd && init->depot_ld >= 2), what);
-    REQUIRE(h_out || cache, what);
-    REQUIRE((!h_out || (uintptr_t)h_out % 16 == 0) && (!init->init_out || (uintptr_t)init->init_out % 16 == 0), what);
-    return launched(launch_encoder_fused16(nullptr, h_out, B, M, nlayers, norm, eps, layers, cache, init, dtype, (hipStream_t)stream),
-                    what);
+    REQUIRE(dtype16_ok(dtype), "eamrl_encoder_fused16_init");
+    return encoder_fused_entry(nullptr, init, true, h_out, B, M, E, H, ff_hidden, nlayers, norm, eps, layers, cache, dtype, stream,
+                               "eamrl_encoder_fused16_init");
 }
 
 static int check_reeval(const eamrl_reeval* p, const char* what, bool bwd)

@@ -31,39 +31,31 @@
 //   h1 = norm1(h + out_proj) -> HB
 //   for chunk c in 0..3 (128 hidden units):  P4 hidden = relu(h1 W1_c^T + b1) -> HID;  P5 ffn2 accumulators += hidden x W2_c^T
 //   h2 = norm2(h1 + ffn2) -> HB
-#include "kernels.hpp"
+#include "encoder_fused.hpp"
 
 namespace eamrl {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int FE = 128;          // embed dim
-constexpr int FH = 8;            // heads
-constexpr int FF = 512;          // feed-forward hidden
 constexpr int SA = 140;          // row stride of the K = 128 A-layout buffers (HB, HID)
 constexpr int GA = 34;           // their g-stride: (SA, GA) = (140, 34) gives conflict-free ds_read_b64 A fragments AND 2-way (free)
                                  // ds_write_b32 from the C layout; (130, 32) reads as well but stores 4-way (measured: +6 % time)
 constexpr int SQ = 66;           // row stride of the 64-column head-group buffers (QA, KB)
-constexpr int MAX_FUSED_LAYERS = 8;
-constexpr int NCST = 9 * FE + FF;     // floats of per-layer constants staged in LDS
 
-struct FusedLayer {
-    const float* Wqkv; const float* bqkv; const float* Wo; const float* bo;      // packed weights (pack_mfma_b), biases
-    const float* W1; const float* b1; const float* W2; const float* b2;
-    const float* n1g; const float* n1b; const float* n1m; const float* n1v;       // norm 1: gamma, beta, running mean / var
-    const float* n2g; const float* n2b; const float* n2m; const float* n2v;
-};
-struct FusedArgs {
-    const float* h_in; float* h_out; int M; int nlayers; int norm; float eps;
-    // optional decoder cache (AttentionModelDecoder._precompute_cache) computed from the final embeddings while they are
-    // still in LDS: slots 0 .. nproj-1 = h Wc_s^T (K | V | L | Pa (| Pb)), slot nproj = Lp = L Wout
-    const float* Wc; const float* WoT; float* cache; int64_t ld; int nproj;
-    // optional graph context: gctx[inst] = mean_n(h) Wg^T (embeddings.mean(1) -> project_fixed_context, no bias)
-    const float* Wg; float* gctx;
-    // optional init embedding (h_in == nullptr): h[n] = Linear(feat[n]) computed straight into LDS (eamrl_encoder_init)
-    const float* feat; int F; const float* Wi; const float* bi; const float* depot; int64_t depot_ld; const float* Wd; const float* bd;
-    float* init_out;
-    FusedLayer L[MAX_FUSED_LAYERS];
+// h in the A layout, for the shared stages of encoder_fused.hpp
+struct ALayout {
+    float* HB;
+    static constexpr int S = SA;
+    __device__ float* col(int c) const { return HB + (c & 3) * GA + (c >> 2); }
+    __device__ void store4(int row, int q4, float4 v) const
+    {
+        float* p = HB + row * SA + q4;
+        p[0] = v.x; p[GA] = v.y; p[2 * GA] = v.z; p[3 * GA] = v.w;
+    }
+    __device__ float4 load4(int row, int q4) const
+    {
+        const float* p = HB + row * SA + q4;
+        return make_float4(p[0], p[GA], p[2 * GA], p[3 * GA]);
+    }
+    __device__ void mirror(int, int, float) const {}
 };
 
 #ifdef EAMRL_STAMPS   // development build only (tools/build_stamps.sh): per-phase cycle sums over all wavefronts
@@ -192,26 +184,6 @@ __device__ __forceinline__ void residual_norm_store(const f32x4 (&acc)[RTW][2], 
     }
 }
 
-// InstanceNorm1d(affine) in place on HB: thread = channel, sequential over the M nodes (the order of k_norm_instance).
-__device__ __forceinline__ void instance_norm_lds(float* HB, int M, float eps, const float* cst /* LDS: gamma [E] | beta [E] */)
-{
-    const int c = threadIdx.x;
-    if (c < FE) {
-        float* col = HB + (c & 3) * GA + (c >> 2);
-        float s = 0.0f;
-        for (int n = 0; n < M; ++n) s = s + col[n * SA];
-        const float mean = s / (float)M;
-        float v = 0.0f;
-        for (int n = 0; n < M; ++n) { const float d = col[n * SA] - mean; v = fma_(d, d, v); }
-        const float inv = 1.0f / __builtin_sqrtf(v / (float)M + eps);
-        const float g = cst[c], bt = cst[FE + c];
-        for (int n = 0; n < M; ++n) {
-            const float d = col[n * SA] - mean;
-            col[n * SA] = fma_(d * inv, g, bt);
-        }
-    }
-}
-
 template <int RTT>
 __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
 {
@@ -227,8 +199,7 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
     float* HID = QA;                            // [ROWS][SA]   FFN hidden chunk (aliases QA | KB | VT, which are dead then)
     float* CST = VT + 64 * SV;                  // [NCST]       the layer's biases and normalisation constants
     static_assert(ROWS * SA <= 2 * ROWS * SQ + 64 * SV, "HID must fit QA | KB | VT");
-    // CST: bqkv [3E] | bo [E] | b1 [F] | b2 [E] | norm1 (scale | shift, or gamma | beta) [2E] | norm2 [2E]
-    constexpr int C_BQKV = 0, C_BO = 3 * FE, C_B1 = 4 * FE, C_B2 = 4 * FE + FF, C_N1 = 5 * FE + FF, C_N2 = 7 * FE + FF;
+    const ALayout L{HB};
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave-uniform (SGPR): branches on it are scalar branches
@@ -243,77 +214,13 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
 #endif
 
     // ---- h into the A layout; rows >= M are zero ---------------------------------------------------------------------
-    if (a.h_in) {
-        // from HBM (row-major): all of a thread's loads are issued before the first LDS store (a load-store loop pays the HBM
-        // latency once per trip: 7 trips = 27 k of the kernel's 900 k cycles, profiles/r03b_stamps_encoder_fused.txt)
-        constexpr int NLD = (ROWS * (FE / 4) + 511) / 512;
-        const float* src = a.h_in + inst * (int64_t)M * FE;
-        float4 v[NLD];
-#pragma unroll
-        for (int u = 0; u < NLD; ++u) {
-            const int idx = tid + u * 512;
-            const int row = idx / (FE / 4), q4 = idx % (FE / 4);
-            v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (row < M) v[u] = *reinterpret_cast<const float4*>(src + (int64_t)row * FE + 4 * q4);
-        }
-#pragma unroll
-        for (int u = 0; u < NLD; ++u) {
-            const int idx = tid + u * 512;
-            const int row = idx / (FE / 4), q4 = idx % (FE / 4);
-            if (row < ROWS) {
-                float* p = HB + row * SA + q4;
-                p[0] = v[u].x; p[GA] = v[u].y; p[2 * GA] = v[u].z; p[3 * GA] = v[u].w;
-            }
-        }
-    } else {
-        // init embedding computed in place (nn/env_embeddings/init.py: Linear(F -> E) of the node features; depot envs: row 0
-        // is Linear(2 -> E) of the depot coordinates): each output is chain_k(x[k], W[c][k], F, bias[c]), the order of
-        // eamrl_linear.  Thread = (row, four adjacent columns); the weights of its columns stay in registers over the rows.
-        const int q4 = tid % (FE / 4), r0 = tid / (FE / 4);          // 32 column groups x 16 row phases
-        const int F = a.F;
-        float w[4][8], wd[4][2], bb[4], bdv[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            bb[c] = a.bi ? a.bi[4 * q4 + c] : 0.0f;
-            bdv[c] = (a.depot && a.bd) ? a.bd[4 * q4 + c] : 0.0f;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) w[c][k] = (k < F) ? a.Wi[(4 * q4 + c) * F + k] : 0.0f;
-#pragma unroll
-            for (int k = 0; k < 2; ++k) wd[c][k] = a.depot ? a.Wd[(4 * q4 + c) * 2 + k] : 0.0f;
-        }
-        const float* fsrc = a.feat + inst * (int64_t)M * F;
-        float* iout = a.init_out ? a.init_out + inst * (int64_t)M * FE : nullptr;
-        for (int row = r0; row < ROWS; row += 16) {
-            float y[4] = {0.f, 0.f, 0.f, 0.f};
-            if (row < M) {
-                if (a.depot && row == 0) {
-                    const float x0 = a.depot[inst * a.depot_ld], x1 = a.depot[inst * a.depot_ld + 1];
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) y[c] = fma_(x1, wd[c][1], fma_(x0, wd[c][0], bdv[c]));
-                } else {
-                    float x[8];
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) x[k] = (k < F) ? fsrc[(int64_t)row * F + k] : 0.0f;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        float acc = bb[c];
-#pragma unroll
-                        for (int k = 0; k < 8; ++k)
-                            if (k < F) acc = fma_(x[k], w[c][k], acc);
-                        y[c] = acc;
-                    }
-                }
-                if (iout) *reinterpret_cast<float4*>(iout + (int64_t)row * FE + 4 * q4) = make_float4(y[0], y[1], y[2], y[3]);
-            }
-            float* p = HB + row * SA + q4;
-            p[0] = y[0]; p[GA] = y[1]; p[2 * GA] = y[2]; p[3 * GA] = y[3];
-        }
-    }
+    if (a.h_in) load_h<ROWS>(a.h_in, M, L);
+    else init_embedding<ROWS>(a.init, M, L);
     __syncthreads();
     ESTAMP(0);
 
     for (int layer = 0; layer < a.nlayers; ++layer) {
-        const FusedLayer& Ly = a.L[layer];
+        const eamrl_encoder_layer& Ly = a.L[layer];
         // ---- the layer's biases and normalisation constants -> LDS (one exposed L2 latency per layer instead of one per
         //      pass: every accumulator is initialised with its bias before the first MFMA can issue) ------------------------
         for (int i = tid; i < NCST; i += blockDim.x) {
@@ -326,11 +233,11 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
                 const bool second = i >= C_N2;
                 const int k = (i - (second ? C_N2 : C_N1));
                 const int c = k & (FE - 1);
-                const float* gam = second ? Ly.n2g : Ly.n1g;
-                const float* bet = second ? Ly.n2b : Ly.n1b;
+                const float* gam = second ? Ly.n2_gamma : Ly.n1_gamma;
+                const float* bet = second ? Ly.n2_beta : Ly.n1_beta;
                 if (a.norm == EAMRL_NORM_BATCH_EVAL) {
-                    const float* mean = second ? Ly.n2m : Ly.n1m;
-                    const float* var = second ? Ly.n2v : Ly.n1v;
+                    const float* mean = second ? Ly.n2_mean : Ly.n1_mean;
+                    const float* var = second ? Ly.n2_var : Ly.n1_var;
                     const float sc = gam[c] / __builtin_sqrtf(var[c] + a.eps);
                     const float ms = mean[c] * sc;
                     v = k < FE ? sc : bet[c] - ms;
@@ -409,7 +316,7 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
                 }
                 float vf[4 * RTT];
                 const int NT = (M + 3) >> 2;             // value k-steps (4 keys each)
-                constexpr int FULLT = RTT == 7 ? 4 : RTT == 4 ? 2 : 0;       // launch_encoder_fused: M > 64 / M > 32 / any
+                constexpr int FULLT = RTT == 7 ? 4 : RTT == 4 ? 2 : 0;       // launch_fused: M > 64 / M > 32 / any
 #pragma unroll
                 for (int t = 0; t < 4 * RTT; ++t) vf[t] = (t < NT) ? VT[(16 * cw + j) * SV + 4 * t + G] : 0.0f;
                 for (int q = 0; q < nrt; ++q) {
@@ -489,7 +396,7 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
         residual_norm_store<RTW>(acc_o, HB, row0, nrt, cw, j, G, a.norm, CST + C_N1);
         __syncthreads();
         if (a.norm == EAMRL_NORM_INSTANCE) {
-            instance_norm_lds(HB, M, a.eps, CST + C_N1);
+            instance_norm(L, M, a.eps, CST + C_N1);
             __syncthreads();
         }
         ESTAMP(7);
@@ -552,57 +459,27 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
         residual_norm_store<RTW>(acc_f, HB, row0, nrt, cw, j, G, a.norm, CST + C_N2);
         __syncthreads();
         if (a.norm == EAMRL_NORM_INSTANCE) {
-            instance_norm_lds(HB, M, a.eps, CST + C_N2);
+            instance_norm(L, M, a.eps, CST + C_N2);
             __syncthreads();
         }
         ESTAMP(12);
     }
-    // ---- store h (row-major, float4 per thread); skipped when the caller keeps only the decoder cache -----------------------
-    if (a.h_out) {
-        float* dst = a.h_out + inst * (int64_t)M * FE;
-        for (int idx = tid; idx < M * (FE / 4); idx += blockDim.x) {
-            const int row = idx / (FE / 4), q4 = idx % (FE / 4);
-            const float* p = HB + row * SA + q4;
-            *reinterpret_cast<float4*>(dst + (int64_t)row * FE + 4 * q4) = make_float4(p[0], p[GA], p[2 * GA], p[3 * GA]);
-        }
-    }
+    // ---- store h; skipped when the caller keeps only the decoder cache ----------------------------------------------------
+    if (a.h_out) store_h(a.h_out, M, L);
     ESTAMP(13);
-    // ---- graph context: mean over the nodes in node order (k_mean_nodes), then a k-ordered chain per output (k_linear) ----
-    if (a.gctx) {
-        float* MEAN = CST;                          // the layer constants are dead
-        if (tid < FE) {
-            const float* col = HB + (tid & 3) * GA + (tid >> 2);
-            float s = 0.0f;
-            for (int n = 0; n < M; ++n) s = s + col[n * SA];
-            MEAN[tid] = s / (float)M;
-        }
-        __syncthreads();
-        if (tid < FE) {
-            const float4* w = reinterpret_cast<const float4*>(a.Wg + (int64_t)tid * FE);
-            float acc = 0.0f;
-#pragma unroll 8
-            for (int k4 = 0; k4 < FE / 4; ++k4) {
-                const float4 wv4 = w[k4];
-                acc = fma_(MEAN[4 * k4 + 0], wv4.x, acc);
-                acc = fma_(MEAN[4 * k4 + 1], wv4.y, acc);
-                acc = fma_(MEAN[4 * k4 + 2], wv4.z, acc);
-                acc = fma_(MEAN[4 * k4 + 3], wv4.w, acc);
-            }
-            a.gctx[inst * FE + tid] = acc;
-        }
-    }
+    if (a.cache.gctx) graph_context(a.cache.Wg, a.cache.gctx, M, L, CST);          // the layer constants are dead
     // ---- decoder cache from the resident embeddings: nproj projections of h, then Lp = L Wout ------------------------------
-    if (a.cache) {
+    if (a.cache.out) {
         float* STG = QA;                           // L in the A layout (operand of the Lp pass); aliases the dead attention buffers
-        float* crow = a.cache + (inst * (int64_t)M) * a.ld;
-        for (int sl = 0; sl <= a.nproj; ++sl) {
-            const bool lp = sl == a.nproj;
+        float* crow = a.cache.out + (inst * (int64_t)M) * a.cache.ld;
+        for (int sl = 0; sl <= a.cache.nproj; ++sl) {
+            const bool lp = sl == a.cache.nproj;
             f32x4 acc[RTW][2];
             const float* wp[2];
             float4 b0[2];
 #pragma unroll
             for (int ct = 0; ct < 2; ++ct)
-                wp[ct] = (lp ? a.WoT : a.Wc + (int64_t)sl * FE * FE) + ((int64_t)(2 * cw + ct) * (FE / 16)) * 256 + lane * 4;
+                wp[ct] = (lp ? a.cache.WoutT : a.cache.Wc + (int64_t)sl * FE * FE) + ((int64_t)(2 * cw + ct) * (FE / 16)) * 256 + lane * 4;
             load_b0<2>(b0, wp);
 #pragma unroll
             for (int ct = 0; ct < 2; ++ct)
@@ -620,7 +497,7 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
                         const int c = 32 * cw + 16 * ct + 4 * G;
                         const f32x4 v = acc[rt][ct];
                         if (node < M)
-                            *reinterpret_cast<float4*>(crow + (int64_t)node * a.ld + sl * FE + c) = make_float4(v[0], v[1], v[2], v[3]);
+                            *reinterpret_cast<float4*>(crow + (int64_t)node * a.cache.ld + sl * FE + c) = make_float4(v[0], v[1], v[2], v[3]);
                         if (sl == 2) {             // L also feeds the Lp pass: element (node, c + r) -> A layout (g = r, t = c / 4)
                             float* p = STG + node * SA + (c >> 2);
                             p[0] = v[0]; p[GA] = v[1]; p[2 * GA] = v[2]; p[3 * GA] = v[3];
@@ -657,19 +534,6 @@ int launch_pack_mfma_b(const float* W, float* Wp, int N, int K, hipStream_t st)
     return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
 }
 
-template <int RTT>
-static int launch_fused_t(const FusedArgs& a, int64_t B, hipStream_t st)
-{
-    constexpr int ROWS = 16 * RTT;
-    const size_t lds = ((size_t)ROWS * SA + 2 * (size_t)ROWS * SQ + 64 * (size_t)(ROWS + 4) + NCST) * sizeof(float);
-    auto k = k_encoder_fused<RTT>;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return EAMRL_E_LAUNCH;
-    hipLaunchKernelGGL(k, dim3((unsigned)B), dim3(512), lds, st, a);
-    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
-}
-
 #ifdef EAMRL_STAMPS
 extern "C" __attribute__((visibility("default"))) int eamrl_debug_read_enc_stamps(unsigned long long* out, int reset)
 {
@@ -689,30 +553,22 @@ bool encoder_fused_supports(int M, int E, int H, int FFdim, int nlayers)
 
 int launch_encoder_fused(const float* h_in, float* h_out, int64_t B, int M, int nlayers, int norm, float eps,
                          const eamrl_encoder_layer* layers, const eamrl_encoder_cache* cache, const eamrl_encoder_init* init,
-                         hipStream_t st)
+                         int dtype, hipStream_t st)
 {
     if (B <= 0) return 0;
-    FusedArgs a;
-    a.h_in = h_in; a.h_out = h_out; a.M = M; a.nlayers = nlayers; a.norm = norm; a.eps = eps;
-    a.feat = nullptr; a.F = 0; a.Wi = a.bi = a.depot = a.Wd = a.bd = nullptr; a.depot_ld = 0; a.init_out = nullptr;
-    if (init) {
-        a.h_in = nullptr;
-        a.feat = init->feat; a.F = init->F; a.Wi = init->W; a.bi = init->b; a.depot = init->depot; a.depot_ld = init->depot_ld;
-        a.Wd = init->Wd; a.bd = init->bd; a.init_out = init->init_out;
-    }
-    a.Wc = nullptr; a.WoT = nullptr; a.cache = nullptr; a.ld = 0; a.nproj = 0; a.Wg = nullptr; a.gctx = nullptr;
+    FusedArgs a = {};
+    a.h_in = init ? nullptr : h_in; a.h_out = h_out; a.M = M; a.nlayers = nlayers; a.norm = norm; a.eps = eps;
     if (cache) {
-        a.Wc = cache->Wc; a.WoT = cache->WoutT; a.cache = cache->out; a.ld = cache->ld; a.nproj = cache->nproj;
-        if (cache->Wg && cache->gctx) { a.Wg = cache->Wg; a.gctx = cache->gctx; }
+        a.cache = *cache;
+        if (!cache->Wg || !cache->gctx) a.cache.Wg = a.cache.gctx = nullptr;
     }
-    for (int l = 0; l < nlayers; ++l) {
-        const eamrl_encoder_layer& s = layers[l];
-        a.L[l] = FusedLayer{s.Wqkv, s.bqkv, s.Wo, s.bo, s.W1, s.b1, s.W2, s.b2, s.n1_gamma, s.n1_beta, s.n1_mean, s.n1_var,
-                            s.n2_gamma, s.n2_beta, s.n2_mean, s.n2_var};
-    }
-    if (M <= 32) return launch_fused_t<2>(a, B, st);
-    if (M <= 64) return launch_fused_t<4>(a, B, st);
-    return launch_fused_t<7>(a, B, st);
+    if (init) a.init = *init;
+    for (int l = 0; l < nlayers; ++l) a.L[l] = layers[l];
+    if (dtype != DTYPE_F32) return launch_encoder_fused16(a, B, dtype, st);
+    return launch_fused(a, B, st, [](auto rtt) {
+        constexpr int RTT = decltype(rtt)::value, ROWS = 16 * RTT;
+        return FusedVariant{k_encoder_fused<RTT>, ((size_t)ROWS * SA + 2 * (size_t)ROWS * SQ + 64 * (size_t)(ROWS + 4) + NCST) * sizeof(float)};
+    });
 }
 
 }  // namespace eamrl

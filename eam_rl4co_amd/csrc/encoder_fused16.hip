@@ -13,7 +13,9 @@
 //     rounded to T for the value product; Z = fp32 sum of the rounded weights; o = (sum w v) / Z in fp32;
 //   * residual adds, BatchNorm (eval), InstanceNorm, ReLU in fp32 (the residual stream HB stays fp32 in LDS); a T copy HT of
 //     h is what the next Linear reads;
-//   * init embedding and graph context: the fp32 code of k_encoder_fused (the init embeddings are bit-identical to it).
+//   * h load / store, init embedding, InstanceNorm and graph context: the shared stages of encoder_fused.hpp (load_h,
+//     init_embedding, store_h, instance_norm, graph_context) that k_encoder_fused runs too, so the init embeddings are
+//     bit-identical to it.
 // There is no bit-exact oracle: the accumulation order inside a 16-bit MFMA is not documented.
 //
 // Every GEMM pass is "swapped": the packed weight fragment is the MFMA's A operand and the activation fragment its B operand,
@@ -26,35 +28,14 @@
 //   VT  T [64][SV]       v of the head group, transposed (keys contiguous)         HID T [ROWS][ST]  aliases QA | KB | VT
 //   CST fp32             the layer's biases and normalisation constants
 // Row strides of 272 B (HT, HID) and 144 B (QA, KB) put the 16 rows of a ds_read_b128 fragment on distinct bank quads.
-#include "kernels.hpp"
+#include "encoder_fused.hpp"
 
 namespace eamrl {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int FE = 128;          // embed dim
-constexpr int FF = 512;          // feed-forward hidden
 constexpr int SH = 132;          // HB row stride (floats)
 constexpr int ST = 136;          // HT / HID row stride (T)
 constexpr int SQ = 72;           // QA / KB row stride (T)
-constexpr int MAX_LAYERS = 8;
-constexpr int NCST = 9 * FE + FF;
-
-struct Layer16 {
-    const void* Wqkv; const float* bqkv; const void* Wo; const float* bo;       // packed 16-bit weights (pack16), fp32 biases
-    const void* W1; const float* b1; const void* W2; const float* b2;
-    const float* n1g; const float* n1b; const float* n1m; const float* n1v;
-    const float* n2g; const float* n2b; const float* n2m; const float* n2v;
-};
-struct Args16 {
-    const float* h_in; float* h_out; int M; int nlayers; int norm; float eps;
-    const void* Wc; const void* WoT; float* cache; int64_t ld; int nproj;       // decoder cache (16-bit packed weights)
-    const float* Wg; float* gctx;                                               // graph context (fp32, row-major Wg)
-    const float* feat; int F; const float* Wi; const float* bi; const float* depot; int64_t depot_ld; const float* Wd; const float* bd;
-    float* init_out;
-    Layer16 L[MAX_LAYERS];
-};
 
 // T-specific fragment types and MFMA builtins
 template <typename T> struct Mf;
@@ -77,6 +58,21 @@ __device__ __forceinline__ typename Mf<T>::v4 cvt4(float a, float b, float c, fl
 {
     return (typename Mf<T>::v4){(T)a, (T)b, (T)c, (T)d};
 }
+
+// h: fp32 HB and its T copy HT, both row-major, for the shared stages of encoder_fused.hpp
+template <typename T>
+struct Layout16 {
+    float* HB; T* HT;
+    static constexpr int S = SH;
+    __device__ float* col(int c) const { return HB + c; }
+    __device__ void store4(int row, int q4, float4 v) const
+    {
+        *reinterpret_cast<float4*>(HB + row * SH + 4 * q4) = v;
+        *reinterpret_cast<typename Mf<T>::v4*>(HT + row * ST + 4 * q4) = cvt4<T>(v.x, v.y, v.z, v.w);
+    }
+    __device__ float4 load4(int row, int q4) const { return *reinterpret_cast<const float4*>(HB + row * SH + 4 * q4); }
+    __device__ void mirror(int row, int c, float y) const { HT[row * ST + c] = (T)y; }
+};
 
 // acc[rt][ct] += W[16 ct' + i][k] * A[row 16 rt + j][k] over NU k-groups of 32.
 //   arow: this lane's activation fragment of tile 0, group 0 (LDS: row row0 + j, column 8 G), tiles 16 S elements apart
@@ -139,30 +135,8 @@ __device__ __forceinline__ void residual_norm16(const f32x4 (&acc)[RTW][2], floa
     }
 }
 
-// InstanceNorm1d(affine) in place on HB and its T copy: thread = channel, sequential over the M nodes
-template <typename T>
-__device__ __forceinline__ void instance_norm16(float* HB, T* HT, int M, float eps, const float* cst)
-{
-    const int c = threadIdx.x;
-    if (c < FE) {
-        float* col = HB + c;
-        float s = 0.0f;
-        for (int n = 0; n < M; ++n) s = s + col[n * SH];
-        const float mean = s / (float)M;
-        float v = 0.0f;
-        for (int n = 0; n < M; ++n) { const float d = col[n * SH] - mean; v = fma_(d, d, v); }
-        const float inv = 1.0f / __builtin_sqrtf(v / (float)M + eps);
-        const float g = cst[c], bt = cst[FE + c];
-        for (int n = 0; n < M; ++n) {
-            const float y = fma_((col[n * SH] - mean) * inv, g, bt);
-            col[n * SH] = y;
-            HT[n * ST + c] = (T)y;
-        }
-    }
-}
-
 template <typename T, int RTT>
-__global__ __launch_bounds__(512, 1) void k_encoder_fused16(Args16 a)
+__global__ __launch_bounds__(512, 1) void k_encoder_fused16(FusedArgs a)
 {
     typedef typename Mf<T>::v8 v8;
     typedef typename Mf<T>::v4 v4;
@@ -179,7 +153,7 @@ __global__ __launch_bounds__(512, 1) void k_encoder_fused16(Args16 a)
     T* VT = KB + ROWS * SQ;                                     // [64][SV]
     T* HID = QA;                                                // [ROWS][ST]
     static_assert(ROWS * ST <= 2 * ROWS * SQ + 64 * SV, "HID must fit QA | KB | VT");
-    constexpr int C_BQKV = 0, C_BO = 3 * FE, C_B1 = 4 * FE, C_B2 = 4 * FE + FF, C_N1 = 5 * FE + FF, C_N2 = 7 * FE + FF;
+    const Layout16<T> L{HB, HT};
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -191,72 +165,12 @@ __global__ __launch_bounds__(512, 1) void k_encoder_fused16(Args16 a)
     const int64_t inst = blockIdx.x;
 
     // ---- h into HB (fp32) and HT (T); rows >= M are zero --------------------------------------------------------------
-    if (a.h_in) {
-        constexpr int NLD = (ROWS * (FE / 4) + 511) / 512;
-        const float* src = a.h_in + inst * (int64_t)M * FE;
-        float4 v[NLD];
-#pragma unroll
-        for (int u = 0; u < NLD; ++u) {
-            const int idx = tid + u * 512;
-            const int row = idx / (FE / 4), q4 = idx % (FE / 4);
-            v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (row < M) v[u] = *reinterpret_cast<const float4*>(src + (int64_t)row * FE + 4 * q4);
-        }
-#pragma unroll
-        for (int u = 0; u < NLD; ++u) {
-            const int idx = tid + u * 512;
-            const int row = idx / (FE / 4), q4 = idx % (FE / 4);
-            if (row < ROWS) {
-                *reinterpret_cast<float4*>(HB + row * SH + 4 * q4) = v[u];
-                *reinterpret_cast<v4*>(HT + row * ST + 4 * q4) = cvt4<T>(v[u].x, v[u].y, v[u].z, v[u].w);
-            }
-        }
-    } else {
-        // init embedding: the fp32 code of k_encoder_fused (the same fma chain per output, so the same bits)
-        const int q4 = tid % (FE / 4), r0 = tid / (FE / 4);
-        const int F = a.F;
-        float w[4][8], wd[4][2], bb[4], bdv[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            bb[c] = a.bi ? a.bi[4 * q4 + c] : 0.0f;
-            bdv[c] = (a.depot && a.bd) ? a.bd[4 * q4 + c] : 0.0f;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) w[c][k] = (k < F) ? a.Wi[(4 * q4 + c) * F + k] : 0.0f;
-#pragma unroll
-            for (int k = 0; k < 2; ++k) wd[c][k] = a.depot ? a.Wd[(4 * q4 + c) * 2 + k] : 0.0f;
-        }
-        const float* fsrc = a.feat + inst * (int64_t)M * F;
-        float* iout = a.init_out ? a.init_out + inst * (int64_t)M * FE : nullptr;
-        for (int row = r0; row < ROWS; row += 16) {
-            float y[4] = {0.f, 0.f, 0.f, 0.f};
-            if (row < M) {
-                if (a.depot && row == 0) {
-                    const float x0 = a.depot[inst * a.depot_ld], x1 = a.depot[inst * a.depot_ld + 1];
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) y[c] = fma_(x1, wd[c][1], fma_(x0, wd[c][0], bdv[c]));
-                } else {
-                    float x[8];
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) x[k] = (k < F) ? fsrc[(int64_t)row * F + k] : 0.0f;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        float acc = bb[c];
-#pragma unroll
-                        for (int k = 0; k < 8; ++k)
-                            if (k < F) acc = fma_(x[k], w[c][k], acc);
-                        y[c] = acc;
-                    }
-                }
-                if (iout) *reinterpret_cast<float4*>(iout + (int64_t)row * FE + 4 * q4) = make_float4(y[0], y[1], y[2], y[3]);
-            }
-            *reinterpret_cast<float4*>(HB + row * SH + 4 * q4) = make_float4(y[0], y[1], y[2], y[3]);
-            *reinterpret_cast<v4*>(HT + row * ST + 4 * q4) = cvt4<T>(y[0], y[1], y[2], y[3]);
-        }
-    }
+    if (a.h_in) load_h<ROWS>(a.h_in, M, L);
+    else init_embedding<ROWS>(a.init, M, L);
     __syncthreads();
 
     for (int layer = 0; layer < a.nlayers; ++layer) {
-        const Layer16& Ly = a.L[layer];
+        const eamrl_encoder_layer& Ly = a.L[layer];
         for (int i = tid; i < NCST; i += blockDim.x) {
             float v;
             if (i < C_BO) v = Ly.bqkv[i];
@@ -267,11 +181,11 @@ __global__ __launch_bounds__(512, 1) void k_encoder_fused16(Args16 a)
                 const bool second = i >= C_N2;
                 const int k = (i - (second ? C_N2 : C_N1));
                 const int c = k & (FE - 1);
-                const float* gam = second ? Ly.n2g : Ly.n1g;
-                const float* bet = second ? Ly.n2b : Ly.n1b;
+                const float* gam = second ? Ly.n2_gamma : Ly.n1_gamma;
+                const float* bet = second ? Ly.n2_beta : Ly.n1_beta;
                 if (a.norm == EAMRL_NORM_BATCH_EVAL) {
-                    const float* mean = second ? Ly.n2m : Ly.n1m;
-                    const float* var = second ? Ly.n2v : Ly.n1v;
+                    const float* mean = second ? Ly.n2_mean : Ly.n1_mean;
+                    const float* var = second ? Ly.n2_var : Ly.n1_var;
                     const float sc = gam[c] / __builtin_sqrtf(var[c] + a.eps);
                     const float ms = mean[c] * sc;
                     v = k < FE ? sc : bet[c] - ms;
@@ -389,7 +303,7 @@ __global__ __launch_bounds__(512, 1) void k_encoder_fused16(Args16 a)
         residual_norm16<T, RTW>(acc_o, HB, HT, row0, nrt, cw, j, G, a.norm, CST + C_N1);
         __syncthreads();
         if (a.norm == EAMRL_NORM_INSTANCE) {
-            instance_norm16<T>(HB, HT, M, a.eps, CST + C_N1);
+            instance_norm(L, M, a.eps, CST + C_N1);
             __syncthreads();
         }
         // ---- FFN: 4 chunks of 128 hidden units ---------------------------------------------------------------------------
@@ -438,52 +352,24 @@ __global__ __launch_bounds__(512, 1) void k_encoder_fused16(Args16 a)
         residual_norm16<T, RTW>(acc_f, HB, HT, row0, nrt, cw, j, G, a.norm, CST + C_N2);
         __syncthreads();
         if (a.norm == EAMRL_NORM_INSTANCE) {
-            instance_norm16<T>(HB, HT, M, a.eps, CST + C_N2);
+            instance_norm(L, M, a.eps, CST + C_N2);
             __syncthreads();
         }
     }
-    // ---- embeddings out (fp32, row-major) -----------------------------------------------------------------------------------
-    if (a.h_out) {
-        float* dst = a.h_out + inst * (int64_t)M * FE;
-        for (int idx = tid; idx < M * (FE / 4); idx += blockDim.x) {
-            const int row = idx / (FE / 4), q4 = idx % (FE / 4);
-            *reinterpret_cast<float4*>(dst + (int64_t)row * FE + 4 * q4) = *reinterpret_cast<const float4*>(HB + row * SH + 4 * q4);
-        }
-    }
-    // ---- graph context: the fp32 code of k_encoder_fused (mean in node order, k-ordered chain) ------------------------------
-    if (a.gctx) {
-        float* MEAN = CST;
-        if (tid < FE) {
-            float s = 0.0f;
-            for (int n = 0; n < M; ++n) s = s + HB[n * SH + tid];
-            MEAN[tid] = s / (float)M;
-        }
-        __syncthreads();
-        if (tid < FE) {
-            const float4* w = reinterpret_cast<const float4*>(a.Wg + (int64_t)tid * FE);
-            float acc = 0.0f;
-#pragma unroll 8
-            for (int k4 = 0; k4 < FE / 4; ++k4) {
-                const float4 wv4 = w[k4];
-                acc = fma_(MEAN[4 * k4 + 0], wv4.x, acc);
-                acc = fma_(MEAN[4 * k4 + 1], wv4.y, acc);
-                acc = fma_(MEAN[4 * k4 + 2], wv4.z, acc);
-                acc = fma_(MEAN[4 * k4 + 3], wv4.w, acc);
-            }
-            a.gctx[inst * FE + tid] = acc;
-        }
-    }
+    // ---- embeddings out (fp32, row-major), graph context ---------------------------------------------------------------------
+    if (a.h_out) store_h(a.h_out, M, L);
+    if (a.cache.gctx) graph_context(a.cache.Wg, a.cache.gctx, M, L, CST);
     // ---- decoder cache: nproj projections of h, then Lp = L Wout (L rounded to T in STG) ------------------------------------
-    if (a.cache) {
+    if (a.cache.out) {
         T* STG = QA;                                // [ROWS][ST], aliases the dead attention / hidden buffers
-        float* crow = a.cache + (inst * (int64_t)M) * a.ld;
-        for (int sl = 0; sl <= a.nproj; ++sl) {
-            const bool lp = sl == a.nproj;
+        float* crow = a.cache.out + (inst * (int64_t)M) * a.cache.ld;
+        for (int sl = 0; sl <= a.cache.nproj; ++sl) {
+            const bool lp = sl == a.cache.nproj;
             f32x4 acc[RTW][2];
             const v8* wp[2];
 #pragma unroll
             for (int ct = 0; ct < 2; ++ct) {
-                wp[ct] = lp ? wfrag<T>(a.WoT, 2 * cw + ct, FE, 0, lane) : wfrag<T>(a.Wc, 8 * sl + 2 * cw + ct, FE, 0, lane);
+                wp[ct] = lp ? wfrag<T>(a.cache.WoutT, 2 * cw + ct, FE, 0, lane) : wfrag<T>(a.cache.Wc, 8 * sl + 2 * cw + ct, FE, 0, lane);
 #pragma unroll
                 for (int rt = 0; rt < RTW; ++rt) acc[rt][ct] = splat4(0.0f);
             }
@@ -498,7 +384,7 @@ __global__ __launch_bounds__(512, 1) void k_encoder_fused16(Args16 a)
                         const int c = 32 * cw + 16 * ct + 4 * G;
                         const f32x4 v = acc[rt][ct];
                         if (node < M)
-                            *reinterpret_cast<float4*>(crow + (int64_t)node * a.ld + sl * FE + c) = make_float4(v[0], v[1], v[2], v[3]);
+                            *reinterpret_cast<float4*>(crow + (int64_t)node * a.cache.ld + sl * FE + c) = make_float4(v[0], v[1], v[2], v[3]);
                         if (sl == 2) *reinterpret_cast<v4*>(STG + node * ST + c) = cvt4<T>(v[0], v[1], v[2], v[3]);
                     }
                 }
@@ -519,26 +405,14 @@ __global__ void k_pack16(const float* __restrict__ W, T* __restrict__ Wp, int N,
     Wp[idx] = (T)W[(int64_t)(16 * ct + (l & 15)) * K + 32 * u + 8 * (l >> 4) + e];
 }
 
-template <typename T, int RTT>
-int launch16_t(const Args16& a, int64_t B, hipStream_t st)
-{
-    constexpr int ROWS = 16 * RTT;
-    const size_t lds = ((size_t)ROWS * SH + NCST) * sizeof(float) +
-                       ((size_t)ROWS * ST + 2 * (size_t)ROWS * SQ + 64 * (size_t)(ROWS + 8)) * sizeof(T);
-    auto k = k_encoder_fused16<T, RTT>;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return EAMRL_E_LAUNCH;
-    hipLaunchKernelGGL(k, dim3((unsigned)B), dim3(512), lds, st, a);
-    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
-}
-
 template <typename T>
-int launch16(const Args16& a, int64_t B, hipStream_t st)
+int launch16(const FusedArgs& a, int64_t B, hipStream_t st)
 {
-    if (a.M <= 32) return launch16_t<T, 2>(a, B, st);
-    if (a.M <= 64) return launch16_t<T, 4>(a, B, st);
-    return launch16_t<T, 7>(a, B, st);
+    return launch_fused(a, B, st, [](auto rtt) {
+        constexpr int RTT = decltype(rtt)::value, ROWS = 16 * RTT;
+        return FusedVariant{k_encoder_fused16<T, RTT>, ((size_t)ROWS * SH + NCST) * sizeof(float) +
+                                                           ((size_t)ROWS * ST + 2 * (size_t)ROWS * SQ + 64 * (size_t)(ROWS + 8)) * sizeof(T)};
+    });
 }
 
 }  // namespace
@@ -552,29 +426,8 @@ int launch_pack_mfma_b16(const float* W, void* Wp, int N, int K, int dtype, hipS
     return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
 }
 
-int launch_encoder_fused16(const float* h_in, float* h_out, int64_t B, int M, int nlayers, int norm, float eps,
-                           const eamrl_encoder_layer* layers, const eamrl_encoder_cache* cache, const eamrl_encoder_init* init,
-                           int dtype, hipStream_t st)
+int launch_encoder_fused16(const FusedArgs& a, int64_t B, int dtype, hipStream_t st)
 {
-    if (B <= 0) return 0;
-    Args16 a;
-    a.h_in = h_in; a.h_out = h_out; a.M = M; a.nlayers = nlayers; a.norm = norm; a.eps = eps;
-    a.feat = nullptr; a.F = 0; a.Wi = a.bi = a.depot = a.Wd = a.bd = nullptr; a.depot_ld = 0; a.init_out = nullptr;
-    if (init) {
-        a.h_in = nullptr;
-        a.feat = init->feat; a.F = init->F; a.Wi = init->W; a.bi = init->b; a.depot = init->depot; a.depot_ld = init->depot_ld;
-        a.Wd = init->Wd; a.bd = init->bd; a.init_out = init->init_out;
-    }
-    a.Wc = nullptr; a.WoT = nullptr; a.cache = nullptr; a.ld = 0; a.nproj = 0; a.Wg = nullptr; a.gctx = nullptr;
-    if (cache) {
-        a.Wc = cache->Wc; a.WoT = cache->WoutT; a.cache = cache->out; a.ld = cache->ld; a.nproj = cache->nproj;
-        if (cache->Wg && cache->gctx) { a.Wg = cache->Wg; a.gctx = cache->gctx; }
-    }
-    for (int l = 0; l < nlayers; ++l) {
-        const eamrl_encoder_layer& s = layers[l];
-        a.L[l] = Layer16{s.Wqkv, s.bqkv, s.Wo, s.bo, s.W1, s.b1, s.W2, s.b2, s.n1_gamma, s.n1_beta, s.n1_mean, s.n1_var,
-                         s.n2_gamma, s.n2_beta, s.n2_mean, s.n2_var};
-    }
     return dtype == EAMRL_DTYPE_BF16 ? launch16<__bf16>(a, B, st) : launch16<_Float16>(a, B, st);
 }
 

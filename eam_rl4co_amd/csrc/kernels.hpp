@@ -43,15 +43,14 @@ int launch_augment_xy(const float* xy, const float* cs, const int32_t* code, flo
 bool mha_encoder_mfma_supports(int N, int E, int H);
 int launch_mha_encoder_mfma(const float* qkv, float* out, int64_t B, int N, int E, int H, hipStream_t st);
 bool encoder_fused_supports(int M, int E, int H, int FFdim, int nlayers);
+// dtype DTYPE_F32: k_encoder_fused (encoder_fused.hip); EAMRL_DTYPE_F16 / EAMRL_DTYPE_BF16: the opt-in 16-bit k_encoder_fused16
+// (encoder_fused16.hip), whose packed weights come from launch_pack_mfma_b16
+constexpr int DTYPE_F32 = 0;
 int launch_encoder_fused(const float* h_in, float* h_out, int64_t B, int M, int nlayers, int norm, float eps,
                          const eamrl_encoder_layer* layers, const eamrl_encoder_cache* cache, const eamrl_encoder_init* init,
-                         hipStream_t st);
+                         int dtype, hipStream_t st);
 int launch_pack_mfma_b(const float* W, float* Wp, int N, int K, hipStream_t st);
-// opt-in 16-bit fused encoder (encoder_fused16.hip); dtype EAMRL_DTYPE_F16 / EAMRL_DTYPE_BF16
 int launch_pack_mfma_b16(const float* W, void* Wp, int N, int K, int dtype, hipStream_t st);
-int launch_encoder_fused16(const float* h_in, float* h_out, int64_t B, int M, int nlayers, int norm, float eps,
-                           const eamrl_encoder_layer* layers, const eamrl_encoder_cache* cache, const eamrl_encoder_init* init,
-                           int dtype, hipStream_t st);
 // BatchNorm-train backward and the tiny-K Linear weight gradient (train_norm.hip)
 int64_t batchnorm_backward_scratch(int64_t rows, int E);
 int launch_batchnorm_backward(const float* x, const float* dy, const float* mean, const float* var, const float* gamma, float eps,

@@ -29,6 +29,12 @@ def test_cabi_library_loads_and_exports_every_declared_symbol():
     # argument validation happens before any launch: null pointers are rejected on a machine without a GPU too
     assert lib.eamrl_tsp_step(None, None, None, None, None, None, 4, 10, None) == -1
     assert b"eamrl_tsp_step" in lib.eamrl_last_error()
+    # the 16-bit fused encoder accepts only EAMRL_DTYPE_F16 / EAMRL_DTYPE_BF16 (1 / 2); any other dtype is rejected first
+    for dtype in (0, 3):
+        assert lib.eamrl_encoder_fused16(None, None, 1, 20, 128, 8, 512, 3, 0, 1e-5, None, None, dtype, None) == -1
+        assert b"eamrl_encoder_fused16: requirement failed: dtype16_ok(dtype)" in lib.eamrl_last_error()
+        assert lib.eamrl_encoder_fused16_init(None, None, 1, 20, 128, 8, 512, 3, 0, 1e-5, None, None, dtype, None) == -1
+        assert b"eamrl_encoder_fused16_init: requirement failed: dtype16_ok(dtype)" in lib.eamrl_last_error()
 
 
 def test_state_dict_contract_matches_reference():
