@@ -1627,11 +1627,15 @@ static int launch_mha_bwd_t(const float* qkv, const float* dout, float* dqkv, in
     return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
 }
 
-bool mha_encoder_bwd_supports(int N, int E, int H) { return N >= 1 && N <= 112 && E == RE && H == RH; }
+bool mha_encoder_bwd_supports(int N, int E, int H)
+{
+    return (N >= 1 && N <= 112 && E == RE && H == RH) || mha_encoder_bwd_mfma_supports(N, E, H);
+}
 
 int launch_mha_encoder_bwd(const float* qkv, const float* dout, float* dqkv, int64_t B, int N, hipStream_t st)
 {
     if (B <= 0) return 0;
+    if (N > 112) return launch_mha_encoder_bwd_mfma(qkv, dout, dqkv, B, N, st);
     if (N <= 32) return launch_mha_bwd_t<2>(qkv, dout, dqkv, B, N, st);
     if (N <= 64) return launch_mha_bwd_t<4>(qkv, dout, dqkv, B, N, st);
     return launch_mha_bwd_t<7>(qkv, dout, dqkv, B, N, st);

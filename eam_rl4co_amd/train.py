@@ -156,7 +156,8 @@ class _SelfAttentionFn(torch.autograd.Function):
     """The encoder's multi-head self-attention on the packed projection qkv [B, N, 3E] ("b s (three h d)", as Wqkv writes it):
     forward eamrl_mha_encoder (the rollout's kernel), backward eamrl_mha_encoder_backward, which recomputes the softmax from
     qkv -- nothing but qkv is kept.  torch's scaled_dot_product_attention needs [B, H, N, D] operands (permuted copies in and
-    out) and its flash backward takes 0.7 ms per layer at 1024 x 100 nodes."""
+    out) and its flash backward takes 0.7 ms per layer at 1024 x 100 nodes.  Graphs of up to 1024 nodes: k_mha_encoder_bwd
+    (one workgroup per instance) to 112 nodes, k_mha_encoder_bwd_mfma (one per instance and head) above."""
 
     @staticmethod
     def forward(ctx, qkv, num_heads):
@@ -180,7 +181,7 @@ def _self_attention(qkv, B, N, E, H):
     from . import ops
 
     if (qkv.is_cuda and qkv.dtype == torch.float32 and os.environ.get("EAMRL_TORCH_ATTENTION", "0") != "1"
-            and N <= 112 and ops.mha_encoder_backward_supported(N, E, H)):
+            and ops.mha_encoder_backward_supported(N, E, H)):
         return _SelfAttentionFn.apply(qkv, H)
     q = qkv.view(B, N, 3, H, E // H).permute(2, 0, 3, 1, 4)
     return F.scaled_dot_product_attention(q[0], q[1], q[2]).permute(0, 2, 1, 3).reshape(B, N, E)
@@ -456,19 +457,23 @@ def graph_encoder_equals_native(policy, td) -> bool:
     layers (their training forward kernel sums in the rollout's order), every Linear, the self-attention and the norms on this
     library's kernels (none of the EAMRL_TORCH_* switches), fp32 on the GPU.  Batch-norm policies keep two passes: their graph
     runs on the same kernels since round 3 (`_BatchNormTrainFn`), but the rollout's pass is the one that updates the running
-    statistics."""
+    statistics.  Graphs of up to 1024 nodes, where the self-attention's backward is native (the native re-evaluation's limit
+    too); above that the graph's attention is torch's."""
+    from . import ops
+
     if any(os.environ.get(k, "0") == "1" for k in ("EAMRL_TORCH_LINEAR", "EAMRL_TORCH_ATTENTION", "EAMRL_TORCH_INSTANCE_NORM",
                                                   "EAMRL_SEPARATE_ENCODER_PASSES")):
         return False
     locs = td["locs"]
     enc = getattr(policy, "encoder", None)
     layers = getattr(getattr(enc, "net", None), "layers", None)
-    if layers is None or not locs.is_cuda or locs.dtype != torch.float32 or locs.shape[1] > 112:
+    if layers is None or not locs.is_cuda or locs.dtype != torch.float32:
         return False
     for layer in layers:
         mha, ffn = layer[0].module, layer[2].module
         E = mha.Wqkv.weight.shape[1]
-        if E != 128 or mha.num_heads != 8 or len(ffn.lins) != 2 or ffn.lins[0].weight.shape[0] % 128:
+        if E != 128 or mha.num_heads != 8 or len(ffn.lins) != 2 or ffn.lins[0].weight.shape[0] % 128 \
+                or not ops.mha_encoder_backward_supported(locs.shape[1], E, mha.num_heads):
             return False
         for norm in (layer[1], layer[3]):
             n = norm.normalizer

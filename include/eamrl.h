@@ -192,7 +192,9 @@ int eamrl_mha_encoder(const float* qkv, float* out, int64_t B, int N, int E, int
 /* Gradient of eamrl_mha_encoder for the training graph (MultiHeadAttention.forward under loss.backward(),
  * nn/attention.py:112-136): qkv [B][N][3E] as given to the forward, dout [B][N][E] -> dqkv [B][N][3E] (written).  The softmax
  * is recomputed (hardware exp; tile-order sums: held to 1e-5 of torch's scaled_dot_product_attention gradient, not part of
- * the bit-exact path).  N <= 112, E = 128, H = 8 (eamrl_mha_encoder_backward_supported). */
+ * the bit-exact path).  1 <= N <= 1024, E = 128, H = 8 (eamrl_mha_encoder_backward_supported): one workgroup per instance up to
+ * 112 nodes, one per (instance, head) above.  Deterministic (no floating-point atomics; an instance's result does not depend on
+ * the batch). */
 int eamrl_mha_encoder_backward_supported(int N, int E, int H);
 int eamrl_mha_encoder_backward(const float* qkv, const float* dout, float* dqkv, int64_t B, int N, int E, int H, void* stream);
 
