@@ -122,6 +122,7 @@ PROTOTYPES = {
                                 _vp, _vp, _vp, _vp, _vp],
     "eamrl_tour_length": [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp],
     "eamrl_sum_logp": [_vp, _i64, _vp, _i64, _i32, _vp],
+    "eamrl_tsp_two_opt": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
     "eamrl_rollout_finish": [_i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp],
     "eamrl_multi_copy": [_i32, _vp, _vp, _vp, _vp],
     "eamrl_instance_norm_forward": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _f32, _vp],

@@ -723,6 +723,19 @@ __attribute__((visibility("default"))) int eamrl_rollout_finish(int env, const f
                                           (hipStream_t)stream), "eamrl_rollout_finish");
 }
 
+__attribute__((visibility("default"))) int eamrl_tsp_two_opt(const float* locs, const float* distances,
+                                                            const int64_t* actions_in, int64_t* actions_out, int32_t* iters,
+                                                            int32_t* status, int64_t B, int N, int max_iterations,
+                                                            void* stream)
+{
+    REQUIRE(actions_in && actions_out && iters && status && actions_in != actions_out, "eamrl_tsp_two_opt");
+    REQUIRE((locs != nullptr) != (distances != nullptr), "eamrl_tsp_two_opt (exactly one of locs / distances)");
+    REQUIRE(B >= 0 && B <= 0x7fffffff && N >= 2 && N <= 1024 && max_iterations >= 0, "eamrl_tsp_two_opt");
+    if (B == 0) return 0;
+    return launched(launch_tsp_two_opt(locs, distances, actions_in, actions_out, iters, status, B, N, max_iterations,
+                                       (hipStream_t)stream), "eamrl_tsp_two_opt");
+}
+
 __attribute__((visibility("default"))) int eamrl_multi_copy(int n, const void* const* src, void* const* dst,
                                                            const int64_t* bytes, void* stream)
 {

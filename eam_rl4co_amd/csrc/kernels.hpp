@@ -128,5 +128,8 @@ int launch_exp1_noise(uint64_t seed, const uint64_t* seed_dev, float* noise, int
 int launch_ea_tsp(const float* locs, int64_t* pop, float* fitness, int64_t B, int S, int N, int G, double mutation_rate,
                   double crossover_rate, double selection_rate, const double* cross_rand, const int32_t* cross_idx,
                   const double* mut_rand, const int32_t* mut_idx, hipStream_t st);
+// TSP 2-opt local search, all sweeps in one launch (local_search.hip)
+int launch_tsp_two_opt(const float* locs, const float* distances, const int64_t* actions_in, int64_t* actions_out,
+                       int32_t* iters, int32_t* status, int64_t B, int N, int max_iterations, hipStream_t st);
 
 }  // namespace eamrl

@@ -493,6 +493,25 @@ class TSPEnv(RL4COEnvBase):
         cur_actions[selection_mask] = new_actions[selection_mask]
         return cur_actions
 
+    @staticmethod
+    def local_search(td, actions, max_iterations: int = 1000, num_threads: Optional[int] = None) -> torch.Tensor:
+        """2-opt until no improving move is left or `max_iterations` sweeps (tsp/env.py:187-192, tsp/local_search.py:17-79):
+        identical tours, computed on the GPU in one launch.  td["distances"] is used if present, else the Euclidean distances
+        of td["locs"].  `num_threads` (the reference's numba pool) is accepted and ignored.  As in the reference, any integer
+        dtype of `actions` is accepted (the result is int64) and the distances are taken as float32."""
+        distances = td.get("distances", None)
+        actions = actions.detach().long().contiguous()
+        if distances is not None:
+            tours, _, status = ops.tsp_two_opt(actions, distances=distances.detach().float().contiguous(),
+                                               max_iterations=max_iterations)
+        else:
+            tours, _, status = ops.tsp_two_opt(actions, locs=td["locs"].detach().float().contiguous(),
+                                               max_iterations=max_iterations)
+        bad = int(status.item())
+        if bad:
+            raise ValueError(f"local_search: {bad} of {actions.shape[0]} tours are not permutations of 0..{actions.shape[1] - 1}")
+        return tours
+
 
 class CVRPEnv(RL4COEnvBase):
     """Capacitated Vehicle Routing Problem (rl4co/envs/routing/cvrp/env.py:24-264)."""

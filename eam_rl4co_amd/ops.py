@@ -1040,6 +1040,41 @@ def check_solution(env_name, actions, demand=None, vcap=None, num_loc=None):
     return bad
 
 
+# the sizes at which eamrl_tsp_two_opt switches variant (include/eamrl.h EAMRL_TWO_OPT_*): results do not depend on them
+TWO_OPT_WAVE_MAX, TWO_OPT_BLOCK256_MAX, TWO_OPT_LDS_MATRIX_MAX = 48, 256, 120
+
+
+def tsp_two_opt(actions, locs=None, distances=None, max_iterations=1000):
+    """Best-improvement 2-opt on TSP tours, every sweep of every tour in one launch (eamrl_tsp_two_opt;
+    rl4co/envs/routing/tsp/local_search.py:17-79).  actions [B, N] int64 (not modified); exactly one of locs [B, N, 2]
+    and distances [B, N, N] (fp32).  -> (tours [B, N] int64, iters [B] int32 = sweeps run, status int32[1] = number of
+    rows that are not permutations of 0..N-1; those are returned unchanged).  Enqueued on the current stream, no host
+    sync: read `status` when convenient."""
+    lib = _lib.load()
+    _chk(actions, "actions", torch.int64)
+    if actions.dim() != 2:
+        raise ValueError(f"actions must be [B, N], got {tuple(actions.shape)}")
+    B, N = actions.shape
+    if (locs is None) == (distances is None):
+        raise ValueError("tsp_two_opt: pass exactly one of locs and distances")
+    if locs is not None:
+        _chk(locs, "locs", torch.float32, (B, N, 2))
+    else:
+        _chk(distances, "distances", torch.float32, (B, N, N))
+    if not 2 <= N <= 1024:
+        raise ValueError(f"tsp_two_opt: 2 <= N <= 1024 required, got {N}")
+    max_iterations = int(max_iterations)
+    if max_iterations < 0:
+        raise ValueError("tsp_two_opt: max_iterations must be >= 0")
+    dev = actions.device
+    tours = torch.empty_like(actions)
+    iters = torch.empty(B, dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(lib.eamrl_tsp_two_opt(_ptr(locs), _ptr(distances), _ptr(actions), _ptr(tours), _ptr(iters), _ptr(status), B, N,
+                                     max_iterations, _stream(actions)), "eamrl_tsp_two_opt")
+    return tours, iters, status
+
+
 # ------------------------------------------------------------------------------------------------------
 # decode
 # ------------------------------------------------------------------------------------------------------

@@ -555,6 +555,28 @@ int eamrl_replay_states(int env, const eamrl_state* state, int64_t R, int64_t B,
 int eamrl_replay_states_sdvrp(const eamrl_state* state, int64_t R, int M, const int64_t* actions, int T, uint32_t* bits,
                               int32_t* idxA, float* sc, float* rem_out, void* stream);
 
+/* ---- local search ----------------------------------------------------------------------------------------- */
+
+/* TSPEnv.local_search: best-improvement 2-opt  [rl4co/envs/routing/tsp/local_search.py:17-79; the env's method:
+ * rl4co/envs/routing/tsp/env.py:187-192].  One launch for all tours and all sweeps.  For every row a sweep scans the
+ * position pairs 1 <= i < j <= N-1 in this order for
+ *     change = ((d[t[i-1]][t[j]] + d[t[i]][t[(j+1) % N]]) - d[t[i-1]][t[i]]) - d[t[j]][t[(j+1) % N]]      (fp32, this order)
+ * keeps the first minimum below 0, and reverses positions i..j if it is below -1e-6; the row stops after the first sweep
+ * that reverses nothing or after max_iterations sweeps.  Position 0 never moves.
+ *   exactly one of  locs [B][N][2]  (d = the Euclidean leg sqrtf(fmaf(dy, dy, dx*dx)), the reference's
+ *   get_distance_matrix bit for bit)  and  distances [B][N][N]  (td["distances"], may be asymmetric)  is non-NULL;
+ *   actions_in [B][N] (read only), actions_out [B][N] (must not overlap actions_in; only equal pointers are rejected), iters [B] i32 = sweeps run,
+ *   status: device int32, caller zeroes; += 1 per row that is not a permutation of 0..N-1 (such a row is copied to
+ *   actions_out unchanged, iters 0).  2 <= N <= 1024, max_iterations >= 0 (0: a copy).
+ * The launch picks its variant by N alone: a 64-thread workgroup per tour up to EAMRL_TWO_OPT_WAVE_MAX nodes, 256 threads up
+ * to EAMRL_TWO_OPT_BLOCK256_MAX, 1024 above; `distances` is staged in LDS up to EAMRL_TWO_OPT_LDS_MATRIX_MAX nodes and read
+ * from global memory above.  The result does not depend on the variant. */
+#define EAMRL_TWO_OPT_WAVE_MAX 48
+#define EAMRL_TWO_OPT_BLOCK256_MAX 256
+#define EAMRL_TWO_OPT_LDS_MATRIX_MAX 120
+int eamrl_tsp_two_opt(const float* locs, const float* distances, const int64_t* actions_in, int64_t* actions_out,
+                      int32_t* iters, int32_t* status, int64_t B, int N, int max_iterations, void* stream);
+
 /* ---- beam search ------------------------------------------------------------------------------------------ */
 
 /* BeamSearch._make_beam_step  [rl4co/utils/decoding.py:573-608].  Rows in "(w b)" order, R = beam_width * B.

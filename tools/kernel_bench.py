@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of single kernels at the TSP-100 B=1024 shapes (run on the GPU box).
 
-    python tools/kernel_bench.py gemm | mha | decode | ea | train | all      [--iters 20]
+    python tools/kernel_bench.py gemm | mha | decode | ea | two_opt | train | all      [--iters 20]
 """
 import argparse
 import os
@@ -95,6 +95,42 @@ def bench_ea(iters):
         print(f"ea_tsp_run B={B} S={S} N={N} G={G} rates={rates}: {us:8.1f} us  ({B * S * G / us:.1f} M individuals-generations/s)")
 
 
+def bench_two_opt(iters):
+    """eamrl_tsp_two_opt (TSPEnv.local_search): every sweep of every tour in one launch.  HIP events around the launch, median
+    of `iters` launches after warm-up; sweeps = sum of the kernel's own per-tour counts."""
+    import eam_rl4co_amd as ea
+
+    torch.manual_seed(11)
+    for B, N, start in ((1024, 100, "greedy"), (1024, 100, "random"), (64, 500, "greedy")):
+        env = ea.get_env("tsp", generator_params=dict(num_loc=N), seed=5)
+        td = env.reset(batch_size=[B]).to("cuda")
+        if start == "greedy":
+            pol = ea.AttentionModelPolicy(env_name="tsp").eval().to("cuda")
+            with torch.no_grad():
+                tours0 = pol(td.clone(), env, phase="test", decode_type="greedy")["actions"].contiguous()
+        else:
+            tours0 = torch.stack([torch.randperm(N) for _ in range(B)]).to("cuda")
+        locs = td["locs"].contiguous()
+        for _ in range(3):
+            tours, sweeps, status = ops.tsp_two_opt(tours0, locs=locs)
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(iters):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            tours, sweeps, status = ops.tsp_two_opt(tours0, locs=locs)
+            e1.record()
+            torch.cuda.synchronize()
+            times.append(e0.elapsed_time(e1))
+        ms = sorted(times)[len(times) // 2]
+        total = int(sweeps.sum())
+        gain = float((env.get_reward(td, tours, check_solution=False) - env.get_reward(td, tours0, check_solution=False)).mean())
+        print(f"two_opt B={B} N={N} from {start:6s} tours: {ms:8.3f} ms (median of {iters}, min {min(times):.3f})  "
+              f"sweeps total {total} (max per tour {int(sweeps.max())})  {ms * 1e3 / total * B:7.3f} us per sweep per tour "
+              f"(a workgroup's time: tours run side by side)  {ms * 1e3 / int(sweeps.max()):7.3f} us per sweep of the longest tour  "
+              f"mean length gain {gain:.4f}  bad rows {int(status.item())}")
+
+
 def bench_train(iters):
     """One EAM training step of the fork (zoo/earl/model.py:129-247) end to end: sampled multistart rollout (native),
     evolutionary improvement (native), teacher-forced re-evaluation with autograd, backward, Adam step."""
@@ -152,6 +188,8 @@ def main():
         bench_mha(a.iters)
     if a.what in ("ea", "all"):
         bench_ea(a.iters)
+    if a.what in ("two_opt", "all"):
+        bench_two_opt(a.iters)
     for kv in filter(None, os.environ.get("EAMRL_DEBUG_KEYS", "").split(",")):   # kernel A/B experiments only
         from eam_rl4co_amd import _lib
         _lib.load().eamrl_debug_set(int(kv.split("=")[0]), int(kv.split("=")[1]))
