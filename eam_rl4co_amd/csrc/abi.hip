@@ -780,9 +780,8 @@ __attribute__((visibility("default"))) int eamrl_ea_tsp_run(const float* locs, i
             "eamrl_ea_tsp_run (population and tour length are limited to 128)");
     REQUIRE(mutation_rate == mutation_rate && crossover_rate == crossover_rate && selection_rate >= 0.0,
             "eamrl_ea_tsp_run");
-    int ne = S;
-    if (S > 2) { ne = (int)(selection_rate * (double)S); if (ne <= 0 || ne > S) ne = S; }
-    if (num_generations > 0 && ne / 2 > 0)      // an elite set of one produces no offspring and reads no draws
+    // an elite set of one produces no offspring and reads no draws
+    if (num_generations > 0 && ea_num_elites(selection_rate, S) / 2 > 0)
         REQUIRE(cross_rand && cross_idx && mut_rand && mut_idx, "eamrl_ea_tsp_run (draws)");
     if (B == 0) return 0;
     return launched(launch_ea_tsp(locs, pop, fitness, B, S, N, num_generations, mutation_rate, crossover_rate,
@@ -804,9 +803,8 @@ __attribute__((visibility("default"))) int eamrl_ea_cvrp_run(const float* locs, 
     REQUIRE((int64_t)S * L <= 24000, "eamrl_ea_cvrp_run (S * L <= 24000: three int16 populations must fit LDS)");
     REQUIRE(mutation_rate == mutation_rate && crossover_rate == crossover_rate && selection_rate >= 0.0,
             "eamrl_ea_cvrp_run");
-    int ne = S;
-    if (S > 2) { ne = (int)(selection_rate * (double)S); if (ne <= 0 || ne > S) ne = S; }
-    if (num_generations > 0 && ne / 2 > 0) REQUIRE(cross_rand && cross_u && mut_rand && mut_u, "eamrl_ea_cvrp_run (draws)");
+    if (num_generations > 0 && ea_num_elites(selection_rate, S) / 2 > 0)
+        REQUIRE(cross_rand && cross_u && mut_rand && mut_u, "eamrl_ea_cvrp_run (draws)");
     if (B == 0) return 0;
     return launched(launch_ea_cvrp(locs, demand, vcap, pop, fitness, B, S, N, L, num_generations, mutation_rate,
                                    crossover_rate, selection_rate, top_k, init_mut_rand, init_mut_u, cross_rand, cross_u,
@@ -827,9 +825,7 @@ __attribute__((visibility("default"))) int eamrl_ea_prize_run(int env, const flo
             num_generations >= 0, "eamrl_ea_prize_run (S <= 128, N <= 127 customers, L <= 128)");
     REQUIRE(mutation_rate == mutation_rate && crossover_rate == crossover_rate && selection_rate >= 0.0,
             "eamrl_ea_prize_run");
-    int ne = S;
-    if (S > 2) { ne = (int)(selection_rate * (double)S); if (ne <= 0 || ne > S) ne = S; }
-    if (num_generations > 0 && ne / 2 > 0)
+    if (num_generations > 0 && ea_num_elites(selection_rate, S) / 2 > 0)
         REQUIRE(cross_rand && mut_rand && mut_u && (cross_u || env == EAMRL_ENV_PCTSP), "eamrl_ea_prize_run (draws)");
     if (B == 0) return 0;
     return launched(launch_ea_prize(env, locs, prize, aux, pop, fitness, B, S, N, L, num_generations, mutation_rate,

@@ -1,12 +1,10 @@
-// Evolutionary improvement of PCTSP / OP tour populations (the fork's EA.run for the prize-collecting envs), one
-// workgroup per problem instance; same skeleton as evolution.hip (population, offspring and fitness live in LDS for all
-// generations, every random draw is an input).
+// PCTSP and OP operators of the evolutionary improvement of tour populations (the fork's EA.run for the prize-collecting
+// envs); the generation loop they plug into is k_ea in evolution_common.hpp.
 //
 // Reference (numba on CPU threads):
-//   EA.run ................... rl4co/models/zoo/earl/evolution.py:252-354
-//   inverse_mutate_pctsp ..... :555-583      cycle_crossover_pctsp .. :905-1101    calculate_fitness_cvrp (PCTSP) :364-370
+//   inverse_mutate_pctsp ..... rl4co/models/zoo/earl/evolution.py:555-583
+//   cycle_crossover_pctsp .... :905-1101     calculate_fitness_cvrp (PCTSP) :364-370
 //   order_crossover_op ....... :1110-1346    inverse_mutate_op ...... :1468-1572   calculate_fitness_op .......... :372-378
-//   elitism_selection ........ :1103-1108
 //
 // Arithmetic restated from numba's typing (oracle/ea_oracle.py has the same notes): float32 array elements added to a
 // `0.0` accumulator are summed in float64; PCTSP's prize/penalty ratios are rounded to float32 when stored; OP's distance
@@ -16,78 +14,11 @@
 // customers the OP crossover would look up beyond the node count (it reads out of bounds there) do not exist.
 // Integer results are bit-exact against oracle/ea_oracle.py; fitness uses the canonical reward arithmetic of
 // eamrl_pctsp_reward / eamrl_op_reward (lane-tree sums).
-#include "kernels.hpp"
+#include "evolution_common.hpp"
 
 namespace eamrl {
 
 namespace {
-
-constexpr int EVB = 256;       // threads
-constexpr int EV_MAX = 128;    // max population size, nodes and tour length
-
-enum { PRIZE_PCTSP = 0, PRIZE_OP = 1 };
-
-struct EaPrizeArgs {
-    const float* locs; const float* prize; const float* aux;      // aux: PCTSP penalty [B,M], OP max_length [B,M]
-    int64_t* pop; float* fitness;
-    int64_t B; int S, N, L, G, top_k;
-    double mutation_rate, crossover_rate;
-    const double* init_mut_rand; const double* init_mut_u;        // [B,S], [B,S,2]
-    const double* cross_rand; const double* cross_u;              // [G,B,P], [G,B,P] (OP only)
-    const double* mut_rand; const double* mut_u;                  // [G,B,O], [G,B,O,2]
-    int ne, P;
-};
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// np.random.randint(lo, hi) from a uniform u in [0, 1): lo + min(floor(u * (hi - lo)), hi - lo - 1)
-__device__ __forceinline__ int rint_u(int lo, int hi, double u)
-{
-    const int n = hi - lo;
-    int k = (int)(u * (double)n);
-    k = k > n - 1 ? n - 1 : (k < 0 ? 0 : k);
-    return lo + k;
-}
-
-struct Bits128 {
-    unsigned long long lo = 0ull, hi = 0ull;
-    __device__ __forceinline__ bool test(int i) const { return i < 64 ? (lo >> i) & 1ull : (hi >> (i - 64)) & 1ull; }
-    __device__ __forceinline__ void set(int i) { if (i < 64) lo |= 1ull << i; else hi |= 1ull << (i - 64); }
-    __device__ __forceinline__ void clear(int i) { if (i < 64) lo &= ~(1ull << i); else hi &= ~(1ull << (i - 64)); }
-    __device__ __forceinline__ bool any() const { return (lo | hi) != 0ull; }
-    __device__ __forceinline__ int lowest() const { return lo ? __builtin_ctzll(lo) : 64 + __builtin_ctzll(hi); }
-};
-
-// closed tour depot -> row -> depot (L + 1 legs) by one wavefront, canonical leg and lane-tree order (eamrl_tour_length)
-__device__ __forceinline__ float wave_route_length(const int16_t* row, const float2* loc, int L, int lane)
-{
-    float total = 0.0f;
-    for (int b0 = 0; b0 <= L; b0 += 64) {
-        const int t = b0 + lane;
-        float d = 0.0f;
-        if (t <= L) {
-            const float2 p0 = loc[t == 0 ? 0 : row[t - 1]];
-            const float2 p1 = loc[t == L ? 0 : row[t]];
-            const float dx = p1.x - p0.x, dy = p1.y - p0.y;
-            d = __builtin_sqrtf(fma_(dy, dy, dx * dx));
-        }
-        const float s = wave_tree_sum(d);
-        total = (b0 == 0) ? s : total + s;
-    }
-    return total;
-}
-
-// lane tree over v[row[t]], t < L (orc lane_tree: 64-blocks summed ascending)
-__device__ __forceinline__ float wave_gather_sum(const int16_t* row, const float* v, int L, int lane)
-{
-    float total = 0.0f;
-    for (int b0 = 0; b0 < L; b0 += 64) {
-        const int t = b0 + lane;
-        const float s = wave_tree_sum(t < L ? v[row[t]] : 0.0f);
-        total = (b0 == 0) ? s : total + s;
-    }
-    return total;
-}
 
 // float32 distance of EA.run's calculate_distance_matrix: sqrt(dx*dx + dy*dy), each operation rounded
 __device__ __forceinline__ double dist32(const float2* loc, int a, int b)
@@ -111,11 +42,8 @@ __device__ __forceinline__ void pctsp_mutate_row(int16_t* o, int L, const double
     if (v < 2) return;
     const int i1 = rint_u(1, v, u2[0]), i2 = rint_u(1, v, u2[1]);
     const int start = i1 < i2 ? i1 : i2, end = i1 < i2 ? i2 : i1;
-    if (start < end) {
-        for (int lo = start, hi = end - 1; lo < hi; ++lo, --hi) { const int16_t x = o[lo]; o[lo] = o[hi]; o[hi] = x; }
-    } else if (start < L - 1) {
-        const int16_t x = o[start]; o[start] = o[start + 1]; o[start + 1] = x;
-    }
+    if (start < end) reverse_row(o, start, end - 1);
+    else if (start < L - 1) reverse_row(o, start, start + 1);
 }
 
 // One child of cycle_crossover_pctsp.  p1 / p2 are the pair's parents IN PAIR ORDER (the cycles are found from p1's side for
@@ -259,7 +187,7 @@ __device__ __forceinline__ void op_mutate_row(int16_t* row, int L, const float2*
             double total = dist32(loc, 0, t(0));
             for (int j = 1; j < ve; ++j) total += dist32(loc, t(j - 1), t(j));
             if (total <= safe && !dup) {
-                for (int lo = s, hi = e; lo < hi; ++lo, --hi) { const int16_t x = row[lo]; row[lo] = row[hi]; row[hi] = x; }
+                reverse_row(row, s, e);
                 success = true;
             }
         }
@@ -267,48 +195,57 @@ __device__ __forceinline__ void op_mutate_row(int16_t* row, int L, const float2*
     if (!success && cz >= 0) row[cz] = cz_old;
 }
 
+enum { PRIZE_PCTSP = 0, PRIZE_OP = 1 };
+
 template <int ENV>
-__global__ __launch_bounds__(EVB) void k_ea_prize(EaPrizeArgs a)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int S = a.S, L = a.L, M = a.N + 1, P = a.P, O = 2 * a.P;
-    float2* loc = reinterpret_cast<float2*>(smem);                        // [M <= 128]
-    float* prize = reinterpret_cast<float*>(loc + EV_MAX);                // [M]
-    float* aux = prize + EV_MAX;                                          // [M] penalty (PCTSP) / max_length (OP)
-    float* fit = aux + EV_MAX;                                            // [S]
-    float* ofit = fit + EV_MAX;                                           // [O]
-    int16_t* first = reinterpret_cast<int16_t*>(ofit + EV_MAX);           // [S]
-    int16_t* order = first + EV_MAX;                                      // [S + O]
-    int16_t* sel = order + 2 * EV_MAX;                                    // [ne]
-    int* flags = reinterpret_cast<int*>(sel + EV_MAX);
-    int16_t* pop = reinterpret_cast<int16_t*>(flags + 4);                 // [S][L]
-    int16_t* off = pop + (size_t)S * L;                                   // [O][L]
-    int16_t* tmp = off + (size_t)S * L;                                   // [S][L] (top-k replacement only)
-    uint8_t* scratch = reinterpret_cast<uint8_t*>(tmp + (size_t)S * L);   // [O][2 * EV_MAX] (PCTSP crossover)
-
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int64_t b = blockIdx.x;
-    const float worst = ENV == PRIZE_PCTSP ? (float)(2.5 * (double)L) : 0.0f;
-
-    for (int i = tid; i < M; i += EVB) {
-        loc[i] = *reinterpret_cast<const float2*>(a.locs + (b * M + i) * 2);
-        prize[i] = a.prize[b * M + i];
-        aux[i] = a.aux[b * M + i];
-    }
-    for (int i = tid; i < S * L; i += EVB) pop[i] = (int16_t)clampi((int)a.pop[b * S * L + i], 0, M - 1);
-    if (tid == 0) flags[0] = 0;
-    __syncthreads();
-    const double global_max = (double)aux[0];                             // OP: td["max_length"][0], the depot's entry
-    float pen_total = 0.0f;
-    if (ENV == PRIZE_PCTSP) {
-        // penalties of all customers, lane tree over aux[1..M-1] (every wavefront computes the same value)
-        for (int b0 = 0; b0 < M - 1; b0 += 64) {
-            const int t = b0 + lane;
-            const float s = wave_tree_sum(t < M - 1 ? aux[1 + t] : 0.0f);
-            pen_total = (b0 == 0) ? s : pen_total + s;
+struct PrizeOps {
+    static constexpr int ENV_FLOATS = 2 * EV_MAX;  // prize [M], aux [M]: penalty (PCTSP) / max_length (OP)
+    static constexpr bool INIT_MUTATE = true;
+    // PCTSP crossover: [O][2 * EV_MAX] bytes, a thread's node tables
+    static constexpr size_t tail_bytes(int O) { return ENV == PRIZE_PCTSP ? (size_t)O * 2 * EV_MAX : 0; }
+    const float2* loc; float* prize; float* aux; uint8_t* scratch; int L, M;
+    double global_max; float pen_total, worst;
+    __device__ __forceinline__ void load(const EaArgs& a, int64_t b, float* env, uint8_t* tail, const float2* loc_, int lane)
+    {
+        loc = loc_; prize = env; aux = env + EV_MAX; scratch = tail; L = a.L; M = a.M;
+        worst = ENV == PRIZE_PCTSP ? (float)(2.5 * (double)L) : 0.0f;
+        for (int i = threadIdx.x; i < M; i += EVB) {
+            prize[i] = a.prize[b * M + i];
+            aux[i] = a.aux[b * M + i];
+        }
+        global_max = (double)a.aux[b * M];                                // OP: td["max_length"][0], the depot's entry
+        pen_total = 0.0f;
+        if (ENV == PRIZE_PCTSP) {
+            // penalties of all customers, lane tree over aux[1..M-1] (every wavefront computes the same value)
+            for (int b0 = 0; b0 < M - 1; b0 += 64) {
+                const int t = b0 + lane;
+                const float s = wave_tree_sum(t < M - 1 ? a.aux[b * M + 1 + t] : 0.0f);
+                pen_total = (b0 == 0) ? s : pen_total + s;
+            }
         }
     }
-    auto fitness_of = [&](const int16_t* row) -> float {
+    __device__ __forceinline__ void mutate_row(int16_t* row, const double* u2) const
+    {
+        if (ENV == PRIZE_PCTSP) pctsp_mutate_row(row, L, u2);
+        else op_mutate_row(row, L, loc, global_max, u2);
+    }
+    __device__ __forceinline__ void init_mutate(const EaArgs& a, int16_t* row, int64_t i) const { mutate_row(row, a.init_mut_u + i * 2); }
+    __device__ __forceinline__ void mutate(const EaArgs& a, int16_t* o, int64_t dm) const { mutate_row(o, a.mut_u + dm * 2); }
+    __device__ __forceinline__ bool child(const EaArgs& a, const int16_t* p1, const int16_t* p2, int role, int16_t* o,
+                                          int64_t dp, int tid) const
+    {
+        if (ENV == PRIZE_PCTSP) {
+            pctsp_child(p1, p2, role, o, L, M, prize, aux, scratch + (size_t)tid * 2 * EV_MAX);
+            return false;
+        }
+        const int e1 = valid_end_from_one(p1, L), e2 = valid_end_from_one(p2, L);
+        int max_cross = e1 - 1 < e2 - 1 ? e1 - 1 : e2 - 1;
+        max_cross = max_cross < L - 1 ? max_cross : L - 1;
+        if (p1[e1 - 1] != 0 || p2[e2 - 1] != 0 || max_cross <= 1) return true;
+        return !op_child(role ? p2 : p1, rint_u(1, max_cross, a.cross_u[dp]), o, L, M, loc, global_max);
+    }
+    __device__ __forceinline__ float fitness(const int16_t* row, int lane) const
+    {
         if (ENV == PRIZE_PCTSP) {
             const float len = wave_route_length(row, loc, L, lane);
             const float saved = wave_gather_sum(row, aux, L, lane);
@@ -316,124 +253,8 @@ __global__ __launch_bounds__(EVB) void k_ea_prize(EaPrizeArgs a)
             return worst - (0.0f - reward);
         }
         return worst - (0.0f - wave_gather_sum(row, prize, L, lane));
-    };
-
-    if (tid < S) {
-        first[tid] = pop[tid * L];                                        // node_to_position uses the INITIAL first nodes
-        if (a.init_mut_rand[b * S + tid] < a.mutation_rate) {
-            const double* u2 = a.init_mut_u + (b * S + tid) * 2;
-            if (ENV == PRIZE_PCTSP) pctsp_mutate_row(pop + tid * L, L, u2);
-            else op_mutate_row(pop + tid * L, L, loc, global_max, u2);
-        }
     }
-    __syncthreads();
-    for (int s = wv; s < S; s += EVB / 64) {
-        const float f = fitness_of(pop + s * L);
-        if (lane == 0) fit[s] = f;
-    }
-    if (tid < S) {
-        int dup = 0;
-        for (int j = 0; j < tid; ++j) dup |= (first[j] == first[tid]);
-        if (dup) atomicOr(&flags[0], 1);
-    }
-    __syncthreads();
-    const bool by_first = flags[0] == 0 && !a.top_k;
-
-    for (int g = 0; g < a.G && O > 0; ++g) {
-        if (S <= 2) {
-            if (tid < S) sel[tid] = (int16_t)tid;
-        } else if (tid < S) {
-            const float f = fit[tid];
-            int rank = 0;
-            for (int j = 0; j < S; ++j) rank += (fit[j] < f) | ((fit[j] == f) & (j < tid));
-            if (rank >= S - a.ne) sel[rank - (S - a.ne)] = (int16_t)tid;
-        }
-        __syncthreads();
-
-        if (tid < O) {
-            const int p = tid >> 1, role = tid & 1;
-            const int16_t* p1 = pop + (int)sel[2 * p] * L;
-            const int16_t* p2 = pop + (int)sel[2 * p + 1] * L;
-            const int16_t* own = role ? p2 : p1;
-            int16_t* o = off + tid * L;
-            const int64_t dp = ((int64_t)g * a.B + b) * P + p;
-            double rate = a.crossover_rate;
-            if (p > 0 && P > 1) {
-                rate = ((double)P * a.crossover_rate - 1.0) / (double)(P - 1);
-                rate = rate > 1.0 ? 1.0 : rate;
-                rate = rate < 0.0 ? 0.0 : rate;
-            }
-            const double r = (p == 0) ? 0.0 : a.cross_rand[dp];
-            bool keep_parent = !(r < rate);
-            if (!keep_parent) {
-                if (ENV == PRIZE_PCTSP) {
-                    pctsp_child(p1, p2, role, o, L, M, prize, aux, scratch + (size_t)tid * 2 * EV_MAX);
-                } else {
-                    const int e1 = valid_end_from_one(p1, L), e2 = valid_end_from_one(p2, L);
-                    int max_cross = e1 - 1 < e2 - 1 ? e1 - 1 : e2 - 1;
-                    max_cross = max_cross < L - 1 ? max_cross : L - 1;
-                    if (p1[e1 - 1] != 0 || p2[e2 - 1] != 0 || max_cross <= 1) keep_parent = true;
-                    else keep_parent = !op_child(own, rint_u(1, max_cross, a.cross_u[dp]), o, L, M, loc, global_max);
-                }
-            }
-            if (keep_parent) for (int j = 0; j < L; ++j) o[j] = own[j];
-            const int64_t dm = ((int64_t)g * a.B + b) * O + tid;
-            if (a.mut_rand[dm] < a.mutation_rate) {
-                if (ENV == PRIZE_PCTSP) pctsp_mutate_row(o, L, a.mut_u + dm * 2);
-                else op_mutate_row(o, L, loc, global_max, a.mut_u + dm * 2);
-            }
-        }
-        __syncthreads();
-
-        for (int t = wv; t < O; t += EVB / 64) {
-            const float f = fitness_of(off + t * L);
-            if (lane == 0) ofit[t] = f;
-        }
-        __syncthreads();
-
-        if (by_first) {
-            if (tid < S) {
-                float best = fit[tid];
-                int src = -1;
-                for (int t = 0; t < O; ++t)
-                    if (off[t * L] == first[tid] && ofit[t] > best) { best = ofit[t]; src = t; }
-                order[tid] = (int16_t)src;
-                if (src >= 0) fit[tid] = best;
-            }
-            __syncthreads();
-            for (int i = tid; i < S * L; i += EVB) {
-                const int s = i / L, src = order[s];
-                if (src >= 0) pop[i] = off[src * L + (i - s * L)];
-            }
-        } else {
-            const int C = S + O;
-            if (tid < C) {
-                const float f = tid < S ? fit[tid] : ofit[tid - S];
-                int rank = 0;
-                for (int j = 0; j < C; ++j) {
-                    const float fj = j < S ? fit[j] : ofit[j - S];
-                    rank += (fj < f) | ((fj == f) & (j < tid));
-                }
-                order[tid] = (int16_t)(C - 1 - rank);
-            }
-            __syncthreads();
-            for (int i = tid; i < C * L; i += EVB) {
-                const int c = i / L, dst = order[c];
-                if (dst < S) tmp[dst * L + (i - c * L)] = c < S ? pop[i] : off[i - S * L];
-            }
-            float keep = 0.0f;
-            int dst = S;
-            if (tid < C) { dst = order[tid]; keep = tid < S ? fit[tid] : ofit[tid - S]; }
-            __syncthreads();
-            if (dst < S) fit[dst] = keep;
-            for (int i = tid; i < S * L; i += EVB) pop[i] = tmp[i];
-        }
-        __syncthreads();
-    }
-
-    for (int i = tid; i < S * L; i += EVB) a.pop[b * S * L + i] = pop[i];
-    if (tid < S) a.fitness[b * S + tid] = fit[tid];
-}
+};
 
 }  // namespace
 
@@ -442,30 +263,14 @@ int launch_ea_prize(int env, const float* locs, const float* prize, const float*
                     const double* init_mut_rand, const double* init_mut_u, const double* cross_rand, const double* cross_u,
                     const double* mut_rand, const double* mut_u, hipStream_t st)
 {
-    EaPrizeArgs a;
+    EaArgs a{};
     a.locs = locs; a.prize = prize; a.aux = aux; a.pop = pop; a.fitness = fitness;
-    a.B = B; a.S = S; a.N = N; a.L = L; a.G = G; a.top_k = top_k;
+    a.B = B; a.S = S; a.N = N; a.M = N + 1; a.L = L; a.G = G; a.top_k = top_k;
     a.mutation_rate = mutation_rate; a.crossover_rate = crossover_rate;
     a.init_mut_rand = init_mut_rand; a.init_mut_u = init_mut_u; a.cross_rand = cross_rand; a.cross_u = cross_u;
     a.mut_rand = mut_rand; a.mut_u = mut_u;
-    int ne = S;
-    if (S > 2) {
-        ne = (int)(selection_rate * (double)S);          // int(selection_rate * pop.shape[0]); idx[-0:] is everything
-        if (ne <= 0) ne = S;
-        if (ne > S) ne = S;
-    }
-    a.ne = ne;
-    a.P = ne / 2;
-    const bool pctsp = env == EAMRL_ENV_PCTSP;
-    const size_t lds = EV_MAX * sizeof(float2) + 4 * EV_MAX * sizeof(float) + 5 * EV_MAX * sizeof(int16_t) + 16 +
-                       3 * (size_t)S * L * sizeof(int16_t) + (pctsp ? (size_t)2 * a.P * 2 * EV_MAX : 0);
-    if (lds > 150 * 1024) return EAMRL_E_ARG;
-    auto k = pctsp ? k_ea_prize<PRIZE_PCTSP> : k_ea_prize<PRIZE_OP>;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return EAMRL_E_LAUNCH;
-    hipLaunchKernelGGL(k, dim3((unsigned)B), dim3(EVB), lds, st, a);
-    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
+    return env == EAMRL_ENV_PCTSP ? ea_launch<PrizeOps<PRIZE_PCTSP>>(a, selection_rate, st)
+                                  : ea_launch<PrizeOps<PRIZE_OP>>(a, selection_rate, st);
 }
 
 }  // namespace eamrl

@@ -125,6 +125,13 @@ bool rollout_resident_supports(int env, const DecArgs& a);
 bool rollout_ms_mfma_supports(int env, const DecArgs& a, bool shape_only = false);
 int launch_rollout_ms_mfma(int env, const DecArgs& a, hipStream_t st);
 int launch_exp1_noise(uint64_t seed, const uint64_t* seed_dev, float* noise, int64_t R, int T, int M, hipStream_t st);
+// elites of EA.run's elitism_selection: int(selection_rate * pop.shape[0]), and idx[-0:] is everything; pairs = elites / 2
+inline int ea_num_elites(double selection_rate, int S)
+{
+    if (S <= 2) return S;
+    const int ne = (int)(selection_rate * (double)S);
+    return ne <= 0 || ne > S ? S : ne;
+}
 int launch_ea_tsp(const float* locs, int64_t* pop, float* fitness, int64_t B, int S, int N, int G, double mutation_rate,
                   double crossover_rate, double selection_rate, const double* cross_rand, const int32_t* cross_idx,
                   const double* mut_rand, const int32_t* mut_idx, hipStream_t st);

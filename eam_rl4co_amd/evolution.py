@@ -3,8 +3,8 @@ rl4co/models/zoo/earl/evolution.py: `EA` (:125-354) and `evolution_worker` (:28-
 
 The reference moves the sampled tours to the CPU, spreads the instances over a thread pool and runs numba
 operators per instance, every training step.  Here the whole batch is one launch of `eamrl_ea_tsp_run`
-(csrc/evolution.hip): one workgroup per instance keeps its population in LDS for all generations, and the
-tours never leave the GPU.
+(the generation loop `k_ea` of csrc/evolution_common.hpp with the env's operators): one workgroup per instance
+keeps its population in LDS for all generations, and the tours never leave the GPU.
 
 Randomness: the reference draws inside the operators from numba's per-thread `np.random`, so it is not
 reproducible; here the draws are explicit tensors (`EADraws`), generated on the device from a `torch.Generator`
@@ -14,7 +14,7 @@ or supplied by the caller -- the form in which the operators are tested against 
 Built: TSP (order crossover, inversion mutation, elitism, per-start-node / top-k replacement, single-start
 rotation population), CVRP (route-prefix crossover with capacity repair, in-route inversion, initial
 mutation pass), PCTSP (cycle crossover with prize top-up, prefix inversion) and OP (budget-checked rebuild and
-inversion) -- csrc/evolution_prize.hip for the last two.  FFSP (not a routing env of this path) raises
+inversion) -- operators in csrc/evolution.hip and, for the last two, csrc/evolution_prize.hip.  FFSP (not a routing env of this path) raises
 NotImplementedError.
 """
 from __future__ import annotations

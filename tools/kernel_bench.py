@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of single kernels at the TSP-100 B=1024 shapes (run on the GPU box).
 
-    python tools/kernel_bench.py gemm | mha | decode | ea | two_opt | train | all      [--iters 20]
+    python tools/kernel_bench.py gemm | mha | decode | ea | two_opt | train | all      [--iters 20] [--dump DIR]
 """
 import argparse
 import os
@@ -79,20 +79,54 @@ def bench_decode(iters, t_max=None):
     print(f"decode resident t_max={t_max or M}: {sorted(times[2:])[len(times[2:]) // 2]:8.1f} us (median, events around ops.rollout)")
 
 
-def bench_ea(iters):
-    """eamrl_ea_tsp_run at the POMO training shape: 1024 instances x 100 starts x 100 nodes, 3 generations."""
+def bench_ea(iters, dump=None):
+    """eamrl_ea_{tsp,cvrp,prize}_run at the POMO training shape: 1024 instances x 100 starts x 100 nodes / customers,
+    3 generations, default rates and all-pairs-cross rates.  TSP populations are random permutations per start node;
+    CVRP / PCTSP / OP populations are a sampled multistart rollout of the untrained policy (real action rows with
+    padding).  Everything is seeded.  HIP events around the launch, median of `iters` launches after warm-up.
+    dump: directory that receives ea_<env>_<case>.pt = {init, pop (int16: node ids), fitness} of every case."""
     import eam_rl4co_amd as ea
 
     B, S, N, G = 1024, 100, 100, 3
-    env = ea.get_env("tsp", generator_params=dict(num_loc=N))
-    td = env.reset(batch_size=[B]).to("cuda")
-    init = torch.stack([torch.stack([torch.cat([torch.tensor([s]), torch.tensor([x for x in torch.randperm(N).tolist() if x != s])])
-                                     for s in range(S)]) for _ in range(4)]).repeat(B // 4, 1, 1).cuda()
-    for rates in ((0.1, 0.6, 0.2), (0.5, 0.9, 1.0)):
-        runner = ea.EA(env, dict(num_generations=G, mutation_rate=rates[0], crossover_rate=rates[1], selection_rate=rates[2]))
-        d = ea.EADraws.sample(G, B, S, N, rates[2], "cuda")
-        us = timeit(lambda: runner.run(init, td, draws=d), iters)
-        print(f"ea_tsp_run B={B} S={S} N={N} G={G} rates={rates}: {us:8.1f} us  ({B * S * G / us:.1f} M individuals-generations/s)")
+    for env_name in ("tsp", "cvrp", "pctsp", "op"):
+        torch.manual_seed(11)
+        env = ea.get_env(env_name, generator_params=dict(num_loc=N), seed=5)
+        td = env.reset(batch_size=[B]).to("cuda")
+        if env_name == "tsp":
+            init = torch.stack([torch.stack([torch.cat([torch.tensor([s]), torch.tensor([x for x in torch.randperm(N).tolist() if x != s])])
+                                             for s in range(S)]) for _ in range(4)]).repeat(B // 4, 1, 1).cuda()
+        else:
+            pol = ea.AttentionModelPolicy(env_name=env_name).eval().to("cuda")
+            with torch.no_grad():
+                out = pol(td.clone(), env, phase="train", decode_type="multistart_sampling", num_starts=S)
+            init = ea.unbatchify(out["actions"], S).contiguous()
+        L = init.shape[-1]
+        for case, rates in enumerate(((0.1, 0.6, 0.2), (0.5, 0.9, 1.0))):
+            runner = ea.EA(env, dict(num_generations=G, mutation_rate=rates[0], crossover_rate=rates[1], selection_rate=rates[2]))
+            gen = torch.Generator(device="cuda").manual_seed(100 + case)
+            if env_name == "tsp":
+                d = ea.EADraws.sample(G, B, S, N, rates[2], "cuda", gen)
+            else:
+                d = (ea.EACvrpDraws if env_name == "cvrp" else ea.EAPrizeDraws).sample(G, B, S, rates[2], "cuda", gen)
+            for _ in range(3):
+                pop, fit = runner.run(init, td, draws=d)
+            torch.cuda.synchronize()
+            times = []
+            for _ in range(iters):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                pop, fit = runner.run(init, td, draws=d)
+                e1.record()
+                torch.cuda.synchronize()
+                times.append(e0.elapsed_time(e1) * 1e3)
+            us = sorted(times)[len(times) // 2]
+            print(f"ea_{env_name}_run B={B} S={S} N={N} L={L} G={G} rates={rates}: {us:8.1f} us (median of {iters}, min {min(times):.1f})"
+                  f"  ({B * S * G / us:.1f} M individuals-generations/s)", flush=True)
+            if dump:
+                os.makedirs(dump, exist_ok=True)
+                assert int(pop.min()) >= 0 and int(pop.max()) < 2 ** 15
+                torch.save({"init": init.to(torch.int16).cpu(), "pop": pop.to(torch.int16).cpu(), "fitness": fit.cpu()},
+                           os.path.join(dump, f"ea_{env_name}_{case}.pt"))
 
 
 def bench_two_opt(iters):
@@ -176,6 +210,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", nargs="?", default="all")
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--dump", default=None, metavar="DIR", help="ea: save every case's resulting pop and fitness tensors")
     ap.add_argument("--bm128", type=int, default=0)
     ap.add_argument("--generic-epilogue", type=int, default=0, help="1: run-time configured GEMM epilogue (A/B against the templates)")
     a = ap.parse_args()
@@ -187,7 +222,7 @@ def main():
     if a.what in ("mha", "all"):
         bench_mha(a.iters)
     if a.what in ("ea", "all"):
-        bench_ea(a.iters)
+        bench_ea(a.iters, a.dump)
     if a.what in ("two_opt", "all"):
         bench_two_opt(a.iters)
     for kv in filter(None, os.environ.get("EAMRL_DEBUG_KEYS", "").split(",")):   # kernel A/B experiments only
