@@ -535,7 +535,14 @@ int eamrl_multi_copy(int n, const void* const* src, void* const* dst, const int6
  * EAMRL_ENV_PCTSP [pctsp/env.py:189-205]: demand = real_prize [B][N+1], vcap unused; bad[0] += rows with a customer
  * visited twice, bad[1] += rows that neither collect a total prize >= 1 - 1e-5 nor visit every customer.
  * EAMRL_ENV_SDVRP replays the deliveries [sdvrp/env.py:148-171]: bad[0] += rows with demand left at the end,
- * bad[1] += rows that visit the depot twice in a row while any entry of the replay's demand vector is nonzero. */
+ * bad[1] += rows that visit the depot twice in a row while any entry of the replay's demand vector is nonzero.  That
+ * vector starts with the depot slot -capacity, which the first depot visit turns into 0: a row that never visits the
+ * depot has demand left.  SDVRP replays every row to its end, so one row may be counted in both counters; the other envs
+ * count a row once, for the first assertion of the reference that it fails.
+ * An id < 0 or above the highest node id never indexes out of bounds: the validity check counts such a row as an invalid
+ * tour, bad[0] += 1, and reads nothing through the id (SDVRP: its replay stops there).  The same holds for the checks of
+ * eamrl_op_check_solution, eamrl_cvrptw_check_time and eamrl_rollout_finish; where a kernel also computes a length or a
+ * reward for such a row, it gathers with the id clamped into range. */
 int eamrl_check_solution(int env, const int64_t* actions, const float* demand, const float* vcap, int64_t R,
                          int64_t B, int N, int T, int32_t* bad, void* stream);
 
