@@ -112,9 +112,9 @@ PROTOTYPES = {
     "eamrl_pack_mask_bits": [_vp, _vp, _i64, _i32, _i32, _i32, _vp],
     "eamrl_tsp_mask_bits": [_vp, _vp, _i64, _i32, _i32, _vp],
     "eamrl_mean_nodes": [_vp, _vp, _i64, _i32, _i32, _vp],
-    "eamrl_am_decode_step": [_i32, C.POINTER(Cache), C.POINTER(State), _i64, _i32, _vp, _vp, _f32, _f32, _i32, _f32, _i32,
+    "eamrl_am_decode_step": [_i32, C.POINTER(Cache), C.POINTER(State), _i64, _i32, _vp, _vp, _f32, _f32, _i32, C.c_double, _i32,
                              _vp, _vp, _vp, _vp, _vp, _vp],
-    "eamrl_am_rollout": [_i32, C.POINTER(Cache), C.POINTER(State), _i64, _i32, _vp, _vp, _i32, _f32, _f32, _i32, _f32, _i32,
+    "eamrl_am_rollout": [_i32, C.POINTER(Cache), C.POINTER(State), _i64, _i32, _vp, _vp, _i32, _f32, _f32, _i32, C.c_double, _i32,
                          _vp, _vp, _vp, _vp, _vp],
     "eamrl_exp1_noise": [C.c_uint64, _vp, _vp, _i64, _i32, _i32, _vp],
     "eamrl_rollout_rng_native": [_i32, C.POINTER(Cache), _i64],

@@ -564,7 +564,7 @@ __attribute__((visibility("default"))) int eamrl_mean_nodes(const float* emb, fl
 }
 
 static int fill_args(const char* what, int env, const eamrl_cache* c, const eamrl_state* s, int64_t R, int mode,
-                     const float* noise, const int64_t* given, float clip, float temp, int top_k, float top_p,
+                     const float* noise, const int64_t* given, float clip, float temp, int top_k, double top_p,
                      uint32_t* status, DecArgs& a, bool seeded = false)
 {
     REQUIRE(c && s, what);
@@ -577,7 +577,7 @@ static int fill_args(const char* what, int env, const eamrl_cache* c, const eamr
     REQUIRE(((uintptr_t)c->K % 16 == 0) && ((uintptr_t)c->V % 16 == 0) && ((uintptr_t)c->Lp % 16 == 0), what);
     REQUIRE(R > 0 && R % c->B == 0 && R <= 0x7fffffffLL, what);
     REQUIRE(s->cur && s->mask && status, what);
-    REQUIRE(temp > 0.0f && top_k >= 0 && top_p >= 0.0f && top_p <= 1.0f, what);
+    REQUIRE(temp > 0.0f && top_k >= 0 && top_p >= 0.0 && top_p <= 1.0, what);
     if (env == EAMRL_ENV_TSP) REQUIRE(c->Pb && s->first && s->istep, what);
     if (env == EAMRL_ENV_CVRP) REQUIRE(s->used && s->vcap && c->M >= 2, what);
     if (env == EAMRL_ENV_SDVRP) REQUIRE(s->used && s->vcap && s->rem && c->dyn && c->M >= 2, what);
@@ -601,7 +601,7 @@ static int fill_args(const char* what, int env, const eamrl_cache* c, const eamr
 __attribute__((visibility("default"))) int eamrl_am_decode_step(int env, const eamrl_cache* cache_host,
                                                                const eamrl_state* state_host, int64_t R, int mode,
                                                                const float* noise, const int64_t* given, float tanh_clip,
-                                                               float temperature, int top_k, float top_p,
+                                                               float temperature, int top_k, double top_p,
                                                                int fuse_env_step, int64_t* action,
                                                                float* logp, float* logprobs_all, float* logits_raw,
                                                                uint32_t* status, void* stream)
@@ -626,7 +626,7 @@ __attribute__((visibility("default"))) int eamrl_am_decode_step(int env, const e
 __attribute__((visibility("default"))) int eamrl_am_rollout(int env, const eamrl_cache* cache_host,
                                                            const eamrl_state* state_host, int64_t R, int mode,
                                                            const float* noise, const int64_t* given, int t_given,
-                                                           float tanh_clip, float temperature, int top_k, float top_p,
+                                                           float tanh_clip, float temperature, int top_k, double top_p,
                                                            int t_max, int64_t* actions, float* logps, int32_t* steps_out,
                                                            uint32_t* status, void* stream)
 {
@@ -642,7 +642,7 @@ __attribute__((visibility("default"))) int eamrl_am_rollout(int env, const eamrl
     if (mode == EAMRL_EVALUATE) REQUIRE(t_given > 0, "eamrl_am_rollout");
     a.fuse_env = 1; a.t_max = t_max; a.t_given = t_given;
     a.action = actions; a.logp = logps; a.steps_out = steps_out;
-    const bool filtering = top_k > 0 || (top_p > 0.0f && top_p < 1.0f);        // only the streaming kernel filters
+    const bool filtering = top_k > 0 || (top_p > 0.0 && top_p < 1.0);        // only the streaming kernel filters
     if (!g_debug[11] && !filtering && rollout_ms_mfma_supports(env, a))
         return launched(launch_rollout_ms_mfma(env, a, (hipStream_t)stream), "eamrl_am_rollout");
     if (!g_debug[1] && !filtering && rollout_resident_supports(env, a))
@@ -674,7 +674,7 @@ __attribute__((visibility("default"))) int eamrl_am_rollout_seeded(int env, cons
 {
     DecArgs a;
     int rc = fill_args("eamrl_am_rollout_seeded", env, cache_host, state_host, R, EAMRL_SAMPLE, nullptr, nullptr, tanh_clip,
-                       temperature, 0, 0.0f, status, a, true);
+                       temperature, 0, 0.0, status, a, true);
     if (rc) return rc;
     REQUIRE(actions && logps && steps_out && a.done && t_max > 0, "eamrl_am_rollout_seeded");
     a.fuse_env = 1; a.t_max = t_max; a.t_given = 0;
@@ -688,7 +688,7 @@ __attribute__((visibility("default"))) int eamrl_am_rollout_seeded(int env, cons
     rc = launch_exp1_noise(seed, seed_dev, noise_scratch, R, t_max, a.M, (hipStream_t)stream);
     if (rc) return launched(rc, "eamrl_am_rollout_seeded");
     return eamrl_am_rollout(env, cache_host, state_host, R, EAMRL_SAMPLE, noise_scratch, nullptr, 0, tanh_clip, temperature, 0,
-                            0.0f, t_max, actions, logps, steps_out, status, stream);
+                            0.0, t_max, actions, logps, steps_out, status, stream);
 }
 
 __attribute__((visibility("default"))) int eamrl_tour_length(const float* locs, const int64_t* actions, float* reward,

@@ -344,7 +344,7 @@ __device__ void decode_row(const DecArgs& a, const RowLds& l, int64_t r, const R
     float mx = block_max(tmax, l.red);  // (syncs inside: partL reads above are complete)
 
     // ---- D6b top-k / top-p filtering of the scaled logits (process_logits, rl4co/utils/decoding.py:110-136,170-176) -----
-    const bool use_topp = a.top_p > 0.0f && a.top_p < 1.0f;
+    const bool use_topp = a.top_p > 0.0 && a.top_p < 1.0;
     if (a.top_k > 0 || use_topp) {
         float* pp = l.partL;                      // [M] keep flags, then probabilities
         float* srt = l.partL + M;                 // [M] probabilities in ascending (value, index) order -> remove flags
@@ -362,7 +362,7 @@ __device__ void decode_row(const DecArgs& a, const RowLds& l, int64_t r, const R
             __syncthreads();
         }
         if (use_topp) {                           // nucleus: drop the lower tail whose running probability <= 1 - top_p
-            const float thr = (float)(1.0 - (double)a.top_p);
+            const float thr = (float)(1.0 - a.top_p);      // float32(1 - top_p) of the caller's double, as torch compares
             float t2 = -INFINITY;
             for (int n = tid; n < M; n += BLOCK) t2 = __builtin_fmaxf(t2, l.x[n]);
             const float m2 = block_max(t2, l.red);

@@ -901,7 +901,7 @@ bool rollout_ms_mfma_supports(int env, const DecArgs& a, bool shape_only)
         if (!shape_only && (!a.dyn || !a.rem || !a.used || !a.vcap)) return false;
         if (a.R % a.B != 0 || a.R >= (1ll << 31)) return false;
         const int64_t S = a.R / a.B;
-        return S >= 2 && S <= SMAX && a.top_k == 0 && !(a.top_p > 0.0f && a.top_p < 1.0f);
+        return S >= 2 && S <= SMAX && a.top_k == 0 && !(a.top_p > 0.0 && a.top_p < 1.0);
     }
     if ((env != EAMRL_ENV_TSP && !depot_env) || a.E != ME || a.H != MH || a.M < 2 || a.M > 112 || a.ld % 4 != 0 || a.ld >= (1 << 24)) return false;
     if (depot_env && (g_debug[14] || (!shape_only && (!a.visited || !a.used || !a.vcap || !a.demand)))) return false;
@@ -910,7 +910,7 @@ bool rollout_ms_mfma_supports(int env, const DecArgs& a, bool shape_only)
     if (!shape_only && (env == EAMRL_ENV_PCTSP || env == EAMRL_ENV_OP) && !a.istep) return false;
     if (a.R % a.B != 0 || a.R >= (1ll << 31)) return false;    // mul32w below
     const int64_t S = a.R / a.B;
-    return S >= 2 && S <= SMAX && a.top_k == 0 && !(a.top_p > 0.0f && a.top_p < 1.0f);
+    return S >= 2 && S <= SMAX && a.top_k == 0 && !(a.top_p > 0.0 && a.top_p < 1.0);
 }
 
 int launch_rollout_ms_mfma(int env, const DecArgs& a, hipStream_t st)

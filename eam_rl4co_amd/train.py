@@ -523,7 +523,8 @@ def _filter_logits_(logits, act, top_k: int, top_p: float):
             x = logits.masked_fill(drop, float("-inf"))
             srt, idx = torch.sort(x, dim=-1, descending=False, stable=True)
             cum = torch.softmax(srt, dim=-1).cumsum(-1)
-            drop |= torch.zeros_like(drop).scatter_(-1, idx, cum <= (1.0 - top_p))
+            thr = torch.tensor(1.0 - float(top_p), dtype=torch.float32).item()     # float32(1 - top_p): the double rounded once
+            drop |= torch.zeros_like(drop).scatter_(-1, idx, cum <= thr)
         drop.scatter_(-1, act[..., None], False)
     return logits.masked_fill(drop, float("-inf"))
 

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define EAMRL_VERSION 100 /* 0.1.0 */
+#define EAMRL_VERSION 101 /* 0.1.1: top_p is a double */
 
 /* environments */
 #define EAMRL_ENV_TSP 0
@@ -456,15 +456,16 @@ typedef struct eamrl_state {
  * [zoo/am/decoder.py:161-198; nn/attention.py:282-328; utils/decoding.py:140-190,346-465]:
  * context query -> 8-head masked glimpse -> logits -> tanh clip -> mask -> /temperature -> [top-k] -> [top-p] ->
  * log_softmax -> greedy / sampling / evaluate.  top_k > 0: entries below the k-th largest scaled logit are dropped
- * (ties kept); 0 < top_p < 1: the lower tail whose running softmax mass (ascending order) is <= 1 - top_p is dropped
- * [utils/decoding.py:110-136,170-176]; 0 = off.  Reads the state, does not modify it unless fuse_env_step != 0, in which
+ * (ties kept); 0 < top_p < 1: the lower tail whose running softmax mass (ascending (value, index) order, float32 sums) is
+ * <= (float)(1.0 - top_p) is dropped -- top_p is a double so that this threshold is the one torch compares with, the
+ * double 1 - top_p rounded once to float32 [utils/decoding.py:110-136,170-176]; 0 = off.  Reads the state, does not modify it unless fuse_env_step != 0, in which
  * case it also applies TSPEnv._step / CVRPEnv._step / SDVRPEnv._step (+mask) with the selected action.
  * EAMRL_ENV_SDVRP: cache->dyn and state->rem are required (dynamic embedding of the remaining demand, see eamrl_cache).
  * noise [R][M] (SAMPLE) / given [R] (EVALUATE) else NULL.  Outputs: action [R], logp [R];
  * optional logprobs_all [R][M] (store_all_logp) and logits_raw [R][M] (pre-clip decoder logits). */
 int eamrl_am_decode_step(int env, const eamrl_cache* cache_host, const eamrl_state* state_host, int64_t R,
                          int mode, const float* noise, const int64_t* given, float tanh_clip, float temperature,
-                         int top_k, float top_p, int fuse_env_step, int64_t* action, float* logp, float* logprobs_all,
+                         int top_k, double top_p, int fuse_env_step, int64_t* action, float* logp, float* logprobs_all,
                          float* logits_raw, uint32_t* status, void* stream);
 
 /* Whole decode loop in one launch (ConstructivePolicy.forward's while-loop, constructive/base.py:236-250):
@@ -474,7 +475,7 @@ int eamrl_am_decode_step(int env, const eamrl_cache* cache_host, const eamrl_sta
  * filtering the streaming kernel is used (the register-resident one does not filter). */
 int eamrl_am_rollout(int env, const eamrl_cache* cache_host, const eamrl_state* state_host, int64_t R, int mode,
                      const float* noise, const int64_t* given, int t_given, float tanh_clip, float temperature,
-                     int top_k, float top_p, int t_max, int64_t* actions, float* logps, int32_t* steps_out,
+                     int top_k, double top_p, int t_max, int64_t* actions, float* logps, int32_t* steps_out,
                      uint32_t* status, void* stream);
 
 /* Sampling without a noise tensor.  The Exp(1) draw of (row r, step t, node n) is a pure function of the call's seed:

@@ -672,7 +672,7 @@ typedef struct {
                          * reference scales by a node's remaining demand and adds to its K / V / Lp rows (folded here,
                          * see decode_row)                                              nn/env_embeddings/dynamic.py:59-78 */
     int top_k;          /* process_logits top-k filtering (0 = off)                      utils/decoding.py:110-115 */
-    float top_p;        /* process_logits nucleus filtering (0 or >= 1 = off)            utils/decoding.py:118-136 */
+    double top_p;       /* process_logits nucleus filtering (0 or >= 1 = off); the caller's double   decoding.py:118-136 */
 } orc_dec_t;
 
 static int decode_row(const orc_dec_t* c, long r, int64_t first, int64_t cur, int64_t istep, float remaining, float now,
@@ -785,7 +785,8 @@ static int decode_row(const orc_dec_t* c, long r, int64_t first, int64_t cur, in
     /* D6b top-k / top-p filtering of the scaled logits (process_logits, decoding.py:170-176).
      *   top-k: keep n iff fewer than k entries are strictly larger (== "logits < k-th largest" removed; ties kept).
      *   top-p: p = softmax(x) (d_expf(x - max) / lane_tree sum); entries in ascending (value, index) order; running sum c
-     *          sequential in that order; remove while c <= (float)(1 - top_p). */
+     *          sequential in that order; remove while c <= (float)(1 - top_p), the double rounded once (torch's
+     *          comparison of a float32 tensor with the Python double 1 - top_p). */
     if (c->top_k > 0) {
         const int k = c->top_k < M ? c->top_k : M;
         for (int n = 0; n < M; ++n) {
@@ -795,8 +796,8 @@ static int decode_row(const orc_dec_t* c, long r, int64_t first, int64_t cur, in
         }
         for (int n = 0; n < M; ++n) if (ex[n] == 0.0f) x[n] = -INFINITY;
     }
-    if (c->top_p > 0.0f && c->top_p < 1.0f) {
-        const float thr = (float)(1.0 - (double)c->top_p);
+    if (c->top_p > 0.0 && c->top_p < 1.0) {
+        const float thr = (float)(1.0 - c->top_p);
         float m2 = -INFINITY;
         for (int n = 0; n < M; ++n) if (x[n] > m2) m2 = x[n];
         for (int n = 0; n < M; ++n) ex[n] = (x[n] > -INFINITY) ? d_expf(x[n] - m2) : 0.0f;
@@ -813,7 +814,7 @@ static int decode_row(const orc_dec_t* c, long r, int64_t first, int64_t cur, in
         for (int j = 0; j < M; ++j) { cs = cs + srt[j]; srt[j] = (cs <= thr) ? 1.0f : 0.0f; }
         for (int n = 0; n < M; ++n) if (srt[rk[n]] != 0.0f) x[n] = -INFINITY;
     }
-    if (c->top_k > 0 || (c->top_p > 0.0f && c->top_p < 1.0f)) {
+    if (c->top_k > 0 || (c->top_p > 0.0 && c->top_p < 1.0)) {
         mx = -INFINITY;
         for (int n = 0; n < M; ++n) if (x[n] > mx) mx = x[n];
     }
@@ -854,7 +855,7 @@ ORC_API int orc_decode_step(int env, long R, long Binst, int M, int E, int H,
                             const float* used, const float* vcap, const uint8_t* mask,
                             const float* rem, const float* dyn, const float* time,
                             int mode, const float* noise, const int64_t* given, float clip, float temp,
-                            int top_k, float top_p,
+                            int top_k, double top_p,
                             int64_t* out_action, float* out_logp, float* out_logits, float* out_logprobs)
 {
     orc_dec_t c = { env, R, Binst, M, E, H, K, V, Lp, Pa, Pb, cvec, gctx, clip, temp, dyn, top_k, top_p };
@@ -1104,7 +1105,7 @@ ORC_API int orc_rollout(int env, long R, long Binst, int M, int E, int H,
                         const float* locs,   /* OP, CVRPTW: [Binst][M][2]; OP: `demand` is then the arrival limit [Binst][M] */
                         const float* tw, const float* dur, float* time,   /* CVRPTW: [Binst][M][2], [Binst][M], [R] */
                         int mode, const float* noise, const int64_t* given, int Tgiven,
-                        float clip, float temp, int top_k, float top_p, int Tmax,
+                        float clip, float temp, int top_k, double top_p, int Tmax,
                         int64_t* actions, float* logps)
 {
     int64_t* a = (int64_t*)malloc(sizeof(int64_t) * R);

@@ -393,7 +393,7 @@ def decode_step(st: State, cache, mode="greedy", noise=None, given=None, clip=10
         _p(cache["K"]), _p(cache["V"]), _p(cache["Lp"]), _p(cache["Pa"]), _p(cache["Pb"]), _p(cache["cvec"]),
         _p(cache["gctx"]), _p(st.first), _p(st.cur), _p(st.istep), _p(st.used), _p(st.vcap), _p(st.mask),
         _p(st.rem), _p(cache.get("dyn")), _p(st.time),
-        C.c_int(MODES[mode]), _p(nz), _p(gv), C.c_float(clip), C.c_float(temp), C.c_int(int(top_k)), C.c_float(top_p),
+        C.c_int(MODES[mode]), _p(nz), _p(gv), C.c_float(clip), C.c_float(temp), C.c_int(int(top_k)), C.c_double(top_p),
         _p(act), _p(lp), _p(logits), _p(logprobs))
     if rc == -1:
         raise AssertionError("Logits contain NaNs")
@@ -426,7 +426,7 @@ def rollout(st: State, cache, mode="greedy", noise=None, given=None, clip=10.0, 
         _p(st.mask), _p(st.visited), _p(st.done), _p(st.rem), _p(cache.get("dyn")), _p(st.oplocs), _p(st.tw), _p(st.dur),
         _p(st.time), C.c_int(MODES[mode]), _p(noise),
         _p(given), C.c_int(tg),
-        C.c_float(clip), C.c_float(temp), C.c_int(int(top_k)), C.c_float(top_p), C.c_int(t_max), _p(actions), _p(logps))
+        C.c_float(clip), C.c_float(temp), C.c_int(int(top_k)), C.c_double(top_p), C.c_int(t_max), _p(actions), _p(logps))
     if T == -1:
         raise AssertionError("Logits contain NaNs")
     if T == -2:

@@ -89,7 +89,7 @@ def test_library_loads_and_shares_torch_stream():
     from eam_rl4co_amd import _lib, ops
 
     lib = _lib.load()
-    assert lib.eamrl_version() == 100
+    assert lib.eamrl_version() == 101
     x = torch.arange(6, dtype=torch.float32, device=DEV).reshape(3, 2)
     w = torch.tensor([[1.0, 10.0]], device=DEV)
     s = torch.cuda.Stream()

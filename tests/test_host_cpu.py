@@ -24,7 +24,7 @@ def test_cabi_library_loads_and_exports_every_declared_symbol():
     assert len(declared) >= 16
     lib = _lib.load()   # binds every prototype; raises if one is missing
     assert declared == set(_lib.PROTOTYPES), declared ^ set(_lib.PROTOTYPES)
-    assert lib.eamrl_version() == 100
+    assert lib.eamrl_version() == 101
     assert lib.eamrl_debug_set(99, 0) == -1 and b"unknown key" in lib.eamrl_last_error()
     # argument validation happens before any launch: null pointers are rejected on a machine without a GPU too
     assert lib.eamrl_tsp_step(None, None, None, None, None, None, 4, 10, None) == -1
