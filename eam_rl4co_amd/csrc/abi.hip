@@ -623,6 +623,31 @@ __attribute__((visibility("default"))) int eamrl_am_decode_step(int env, const e
     return launched(launch_decode_step(env, a, (hipStream_t)stream), "eamrl_am_decode_step");
 }
 
+// The kernel a whole-rollout call runs on -- the one place that decides it (eamrl_am_rollout, eamrl_am_rollout_seeded and the
+// eamrl_rollout_kernel query all ask here).  The start-sharing MFMA kernel does not filter; the register-resident one does
+// (graphs up to 112 nodes under a filter, 128 without); everything else streams.  shape_only: asked before a state exists.
+static int rollout_kernel_for(int env, const DecArgs& a, bool shape_only)
+{
+    if (!g_debug[11] && rollout_ms_mfma_supports(env, a, shape_only)) return EAMRL_KERNEL_MS_MFMA;
+    if (!g_debug[1] && rollout_resident_supports(env, a)) return EAMRL_KERNEL_RESIDENT;
+    return EAMRL_KERNEL_STREAM;
+}
+
+__attribute__((visibility("default"))) int eamrl_rollout_kernel(int env, const eamrl_cache* cache_host, int64_t R, int t_max,
+                                                               int top_k, double top_p)
+{
+    const char* what = "eamrl_rollout_kernel";
+    REQUIRE(cache_host, what);
+    REQUIRE(env >= EAMRL_ENV_TSP && env <= EAMRL_ENV_CVRPTW, what);
+    REQUIRE(cache_host->B > 0 && cache_host->M > 0 && cache_host->E > 0 && cache_host->H > 0, what);
+    REQUIRE(R > 0 && R % cache_host->B == 0 && R <= 0x7fffffffLL && t_max > 0, what);
+    REQUIRE(top_k >= 0 && top_p >= 0.0 && top_p <= 1.0, what);
+    DecArgs a{};
+    a.B = cache_host->B; a.M = cache_host->M; a.E = cache_host->E; a.H = cache_host->H; a.ld = cache_host->ld; a.R = R;
+    a.t_max = t_max; a.top_k = top_k; a.top_p = top_p;
+    return rollout_kernel_for(env, a, true);
+}
+
 __attribute__((visibility("default"))) int eamrl_am_rollout(int env, const eamrl_cache* cache_host,
                                                            const eamrl_state* state_host, int64_t R, int mode,
                                                            const float* noise, const int64_t* given, int t_given,
@@ -642,10 +667,10 @@ __attribute__((visibility("default"))) int eamrl_am_rollout(int env, const eamrl
     if (mode == EAMRL_EVALUATE) REQUIRE(t_given > 0, "eamrl_am_rollout");
     a.fuse_env = 1; a.t_max = t_max; a.t_given = t_given;
     a.action = actions; a.logp = logps; a.steps_out = steps_out;
-    const bool filtering = top_k > 0 || (top_p > 0.0 && top_p < 1.0);        // only the streaming kernel filters
-    if (!g_debug[11] && !filtering && rollout_ms_mfma_supports(env, a))
+    const int kernel = rollout_kernel_for(env, a, false);
+    if (kernel == EAMRL_KERNEL_MS_MFMA)
         return launched(launch_rollout_ms_mfma(env, a, (hipStream_t)stream), "eamrl_am_rollout");
-    if (!g_debug[1] && !filtering && rollout_resident_supports(env, a))
+    if (kernel == EAMRL_KERNEL_RESIDENT)
         return launched(launch_rollout_resident(env, a, (hipStream_t)stream), "eamrl_am_rollout");
     return launched(launch_rollout_stream(env, a, (hipStream_t)stream), "eamrl_am_rollout");
 }
@@ -679,7 +704,7 @@ __attribute__((visibility("default"))) int eamrl_am_rollout_seeded(int env, cons
     REQUIRE(actions && logps && steps_out && a.done && t_max > 0, "eamrl_am_rollout_seeded");
     a.fuse_env = 1; a.t_max = t_max; a.t_given = 0;
     a.action = actions; a.logp = logps; a.steps_out = steps_out;
-    if (!g_debug[11] && rollout_ms_mfma_supports(env, a)) {
+    if (rollout_kernel_for(env, a, false) == EAMRL_KERNEL_MS_MFMA) {
         a.seed = seed; a.seed_dev = seed_dev; a.use_rng = 1;
         return launched(launch_rollout_ms_mfma(env, a, (hipStream_t)stream), "eamrl_am_rollout_seeded");
     }

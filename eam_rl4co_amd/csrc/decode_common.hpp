@@ -22,8 +22,9 @@ struct DecArgs {
     uint64_t seed; const uint64_t* seed_dev; int use_rng;   // SAMPLE without a noise tensor: exp1_noise4(seed ^ *seed_dev, row,
                                                             // step, node / 4) (dmath.hpp); seed_dev may be null
     float clip, temp; int fuse_env; int t_max;
-    int top_k; double top_p;     // process_logits filtering (0 = off); handled by the step / streaming kernels.  top_p is the
-                                 // caller's double: the nucleus threshold is (float)(1.0 - top_p), rounded once
+    int top_k; double top_p;     // process_logits filtering (0 = off): the step, streaming and register-resident (FILT) kernels;
+                                 // the start-sharing MFMA kernel declines filtered calls.  top_p is the caller's double: the
+                                 // nucleus threshold is (float)(1.0 - top_p), rounded once
     int64_t* action; float* logp; float* logprobs_all; float* logits_raw;
     int32_t* steps_out; uint32_t* status;
     float* heads_out;   // optional [R][t_max][E]: the glimpse output of every decode step (start-sharing MFMA kernel only)

@@ -35,6 +35,9 @@ constexpr int RE = 128;      // embed dim
 constexpr int RH = 8;        // heads
 constexpr int RD = 16;       // head dim
 constexpr int RNP = 128;     // node slots
+constexpr int RFM = 112;     // largest graph of the filtering (top-k / top-p) variant
+
+bool res_filtering(const DecArgs& a) { return a.top_k > 0 || (a.top_p > 0.0 && a.top_p < 1.0); }
 
 #ifdef EAMRL_STAMPS   // development build only (tools/stamps.sh): per-stage cycle sums of wavefront 0
 __device__ unsigned long long g_stamps[8];
@@ -77,7 +80,12 @@ constexpr int res_sdf(int env) { return env == EAMRL_ENV_SDVRP ? RE : 4; }
 constexpr int res_xyf(int env) { return (env == EAMRL_ENV_OP || env == EAMRL_ENV_CVRPTW) ? RNP : 2; }
 constexpr int res_twf(int env) { return env == EAMRL_ENV_CVRPTW ? RNP : 2; }
 
-template <int ENV, int CP, int CR, bool MS>
+//
+// FILT (top-k / top-p calls, M <= 112): stage D6b of the step kernel (decode_step.hip) runs in the finishing wavefront between the
+// temperature division and the log-softmax, statement for statement the same arithmetic -- see the block in S5.  Its scratch
+// (2 * RNP floats) lies behind the context rows, so the layout and the code of the FILT = false instantiations are those of
+// the kernel without the switch.
+template <int ENV, int CP, int CR, bool MS, bool FILT>
 __global__ __launch_bounds__(RB, 2) void k_rollout_resident(DecArgs a, int S, int G)
 {
     constexpr bool SD = ENV == EAMRL_ENV_SDVRP;
@@ -418,7 +426,89 @@ __global__ __launch_bounds__(RB, 2) void k_rollout_resident(DecArgs a, int S, in
                 v2 = v2 / splat2(a.temp);
             }
             x[0] = v2.x; x[1] = v2.y;
-            const float mx = wave_max(vmax_raw(x[0], x[1]));
+            float mx = wave_max(vmax_raw(x[0], x[1]));
+            if constexpr (FILT) {
+                // ---- D6b top-k / top-p filtering of the scaled logits (process_logits, rl4co/utils/decoding.py:110-136,170-176), the
+                // definition of k_decode_step: the lane holds nodes n0 = lane and n1 = lane + 64, the row goes through LDS once per
+                // pass and every lane counts its two entries against all M (float4 broadcast reads; slots >= M hold -inf and are
+                // excluded by index where they could count).  Only this wavefront touches the scratch: its LDS accesses execute in order.
+                float* fxs = Plds + M * RE;         // [RNP] the row's logits
+                float* srt = fxs + RNP;             // [RNP] probabilities in ascending (value, index) order
+                const int M4 = (M + 3) & ~3;
+                if (a.top_k > 0) {                  // keep n iff fewer than k entries are strictly larger (ties kept)
+                    const int k = a.top_k < M ? a.top_k : M;
+                    fxs[n0] = x[0];
+                    fxs[n1] = x[1];
+                    __builtin_amdgcn_wave_barrier();
+                    int c0 = 0, c1 = 0;
+                    for (int m = 0; m < M4; m += 4) {
+                        const float4 q4 = *reinterpret_cast<const float4*>(fxs + m);
+                        const float xm[4] = {q4.x, q4.y, q4.z, q4.w};
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) { c0 += xm[u] > x[0]; c1 += xm[u] > x[1]; }
+                    }
+                    __builtin_amdgcn_wave_barrier();
+                    if (!(c0 < k)) x[0] = -INFINITY;
+                    if (!(c1 < k)) x[1] = -INFINITY;
+                }
+                if (a.top_p > 0.0 && a.top_p < 1.0) {     // nucleus: drop the lower tail whose running probability <= 1 - top_p
+                    const float thr = (float)(1.0 - a.top_p);      // float32(1 - top_p) of the caller's double, as torch compares
+                    const float m2 = wave_max(vmax_raw(x[0], x[1]));
+                    const float p0 = (x[0] > -INFINITY) ? d_expf(x[0] - m2) : 0.0f;
+                    const float p1 = (x[1] > -INFINITY) ? d_expf(x[1] - m2) : 0.0f;
+                    const float Zp = wave_tree_sum(p0) + wave_tree_sum(p1);      // second 64-block: zeros when M <= 64
+                    fxs[n0] = x[0];
+                    fxs[n1] = x[1];
+                    __builtin_amdgcn_wave_barrier();
+                    // rank = number of entries m < M that precede in (value, index) order.  Node n1 lies behind every m < 64 and
+                    // node n0 before every m >= 64, so the index decides only inside an entry's own block of 64.
+                    int r0 = 0, r1 = 0;
+                    const int Ma4 = M4 < 64 ? M4 : 64;
+                    for (int m = 0; m < Ma4; m += 4) {
+                        const float4 q4 = *reinterpret_cast<const float4*>(fxs + m);
+                        const float xm[4] = {q4.x, q4.y, q4.z, q4.w};
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) {
+                            const bool on = m + u < M;
+                            r0 += on & ((xm[u] < x[0]) | ((xm[u] == x[0]) & (m + u < lane)));
+                            r1 += on & ((xm[u] < x[1]) | (xm[u] == x[1]));
+                        }
+                    }
+                    for (int m = 64; m < M4; m += 4) {
+                        const float4 q4 = *reinterpret_cast<const float4*>(fxs + m);
+                        const float xm[4] = {q4.x, q4.y, q4.z, q4.w};
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) {
+                            const bool on = m + u < M;
+                            r0 += on & (xm[u] < x[0]);
+                            r1 += on & ((xm[u] < x[1]) | ((xm[u] == x[1]) & (m + u - 64 < lane)));
+                        }
+                    }
+                    if (in0) srt[r0] = p0 / Zp;             // the ranks of the M nodes are a permutation of 0 .. M-1
+                    if (in1) srt[r1] = p1 / Zp;
+                    __builtin_amdgcn_wave_barrier();
+                    // the running sum is sequential by definition: one float add per entry in rank order (every lane runs the same
+                    // chain on broadcast reads).  The terms are >= 0, so the sums never decrease and the removed entries are the
+                    // ranks below J = the number of sums <= thr.
+                    float cs = 0.0f;
+                    int J = 0;
+                    for (int j = 0; j < M4; j += 4) {
+                        const float4 s4 = *reinterpret_cast<const float4*>(srt + j);
+                        cs = cs + s4.x; J += (j < M) & (cs <= thr);
+                        cs = cs + s4.y; J += (j + 1 < M) & (cs <= thr);
+                        cs = cs + s4.z; J += (j + 2 < M) & (cs <= thr);
+                        cs = cs + s4.w; J += (j + 3 < M) & (cs <= thr);
+                    }
+                    __builtin_amdgcn_wave_barrier();
+                    if (r0 < J) x[0] = -INFINITY;
+                    if (r1 < J) x[1] = -INFINITY;
+                }
+                // what follows sees the survivors only: "an entry takes part iff it is still finite"
+                v2.x = x[0]; v2.y = x[1];
+                fe[0] = x[0] > -INFINITY;
+                fe[1] = x[1] > -INFINITY;
+                mx = wave_max(vmax_raw(x[0], x[1]));
+            }
             const f32x2 ex2 = d_expf2_nonpos(v2 - splat2(mx));
             const float e0 = fe[0] ? ex2.x : 0.0f;
             const float e1 = fe[1] ? ex2.y : 0.0f;
@@ -643,12 +733,12 @@ __global__ __launch_bounds__(RB, 2) void k_rollout_resident(DecArgs a, int S, in
     }
 }
 
-template <int ENV, int CP, int CR, bool MS>
+template <int ENV, int CP, int CR, bool MS, bool FILT>
 int launch_ms(const DecArgs& a, int S, int G, hipStream_t st)
 {
     const size_t lds = ((sizeof(ResLds<CP, res_tmax(ENV), res_sdf(ENV), res_xyf(ENV), res_twf(ENV)>) + 15) & ~size_t(15)) +
-                       (size_t)a.M * RE * sizeof(float);
-    auto k = k_rollout_resident<ENV, CP, CR, MS>;
+                       (size_t)a.M * RE * sizeof(float) + (FILT ? 2 * RNP * sizeof(float) : 0);
+    auto k = k_rollout_resident<ENV, CP, CR, MS, FILT>;
     if (lds > 64 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return EAMRL_E_LAUNCH;
@@ -656,7 +746,7 @@ int launch_ms(const DecArgs& a, int S, int G, hipStream_t st)
     return 0;
 }
 
-template <int ENV, int CP, int CR>
+template <int ENV, int CP, int CR, bool FILT>
 int launch_cp(const DecArgs& a, hipStream_t st)
 {
     // multistart batch: enough workgroups per instance to fill the chip four times over, the rest of the starts
@@ -666,9 +756,9 @@ int launch_cp(const DecArgs& a, hipStream_t st)
     if (S > 1 && a.R % a.B == 0 && !g_debug[6]) {
         int64_t G = (4 * 512 + a.B - 1) / a.B;
         G = G < 1 ? 1 : (G > S ? S : G);
-        rc = launch_ms<ENV, CP, CR, true>(a, (int)S, (int)G, st);
+        rc = launch_ms<ENV, CP, CR, true, FILT>(a, (int)S, (int)G, st);
     } else {
-        rc = launch_ms<ENV, CP, CR, false>(a, 1, 1, st);
+        rc = launch_ms<ENV, CP, CR, false, FILT>(a, 1, 1, st);
     }
     if (rc) return rc;
     launch_rollout_pad(ENV, a, st);
@@ -680,12 +770,19 @@ int launch_env(const DecArgs& a, hipStream_t st)
 {
     const int C = (a.M + EAMRL_NCHUNK - 1) / EAMRL_NCHUNK;
     if (a.t_max > res_tmax(ENV)) return EAMRL_E_ARG;
-    if (C <= 8) return launch_cp<ENV, 8, 8>(a, st);
-    if (C <= 16) return launch_cp<ENV, 16, 16>(a, st);
-    if (C <= 26) return launch_cp<ENV, 28, 26>(a, st);      // M <= 104 (TSP-100; CVRP-100: M = 101).  (An odd CR leaves the
+    if (res_filtering(a)) {     // M <= RFM: the 32-slot variant is never needed
+        if (C <= 8) return launch_cp<ENV, 8, 8, true>(a, st);
+        if (C <= 16) return launch_cp<ENV, 16, 16, true>(a, st);
+        if (C <= 26) return launch_cp<ENV, 28, 26, true>(a, st);
+        if (C <= 28) return launch_cp<ENV, 28, 28, true>(a, st);
+        return EAMRL_E_ARG;
+    }
+    if (C <= 8) return launch_cp<ENV, 8, 8, false>(a, st);
+    if (C <= 16) return launch_cp<ENV, 16, 16, false>(a, st);
+    if (C <= 26) return launch_cp<ENV, 28, 26, false>(a, st);      // M <= 104 (TSP-100; CVRP-100: M = 101).  (An odd CR leaves the
                                                             // pair-register array of the values unaligned: the 25-slot variant spilled.)
-    if (C <= 28) return launch_cp<ENV, 28, 28>(a, st);
-    return launch_cp<ENV, 32, 32>(a, st);
+    if (C <= 28) return launch_cp<ENV, 28, 28, false>(a, st);
+    return launch_cp<ENV, 32, 32, false>(a, st);
 }
 
 }  // namespace
@@ -704,7 +801,7 @@ extern "C" __attribute__((visibility("default"))) int eamrl_debug_read_stamps(un
 
 bool rollout_resident_supports(int env, const DecArgs& a)
 {
-    return a.E == RE && a.H == RH && a.M <= RNP && a.M >= 2 && a.ld % 4 == 0 && a.t_max <= res_tmax(env);
+    return a.E == RE && a.H == RH && a.M <= (res_filtering(a) ? RFM : RNP) && a.M >= 2 && a.ld % 4 == 0 && a.t_max <= res_tmax(env);
 }
 
 int launch_rollout_resident(int env, const DecArgs& a, hipStream_t st)

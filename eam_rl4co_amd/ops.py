@@ -1380,6 +1380,20 @@ def exp1_noise(seed: int, R: int, T: int, M: int, device="cuda", seed_dev=None):
     return out
 
 
+ROLLOUT_KERNELS = ("ms_mfma", "resident", "stream")       # EAMRL_KERNEL_* of include/eamrl.h
+
+
+def rollout_kernel(st_or_env_name, cache, R, t_max, top_k=0, top_p=0.0) -> str:
+    """The kernel `rollout` runs for this shape: "ms_mfma" (start-sharing MFMA kernel), "resident" (register-resident) or
+    "stream".  Host only: nothing is launched, and the answer comes from the function the dispatcher itself branches on
+    (eamrl_rollout_kernel).  `cache` is a DecodeCache or a `_lib.Cache` struct (only its shape fields are read)."""
+    env_name = st_or_env_name if isinstance(st_or_env_name, str) else st_or_env_name.env_name
+    cs = cache if isinstance(cache, _lib.Cache) else cache.struct()
+    rc = _lib.load().eamrl_rollout_kernel(ENVS[env_name], C.byref(cs), int(R), int(t_max), int(top_k), float(top_p))
+    _lib.check(min(rc, 0), "eamrl_rollout_kernel")
+    return ROLLOUT_KERNELS[rc]
+
+
 def _rollout_outputs(R, t_max, dev):
     """actions [R, t_max] i64, logps [R, t_max] f32 and flags int32[4] = (steps, status, bad0, bad1) as views of ONE
     zero-filled buffer (one fill launch instead of three)."""
@@ -1439,7 +1453,8 @@ def rollout(st: RolloutState, cache: DecodeCache, mode="greedy", noise=None, giv
         if seed is None:
             raise ValueError("rollout: sampling needs `noise` or `seed`")
         if top_k or (0.0 < top_p < 1.0):
-            noise = exp1_noise(seed, R, int(t_max), M, dev, seed_dev)      # the filtering (streaming) kernel reads a tensor
+            # the kernels that filter (register-resident FILT variant, streaming) read their noise from a tensor
+            noise = exp1_noise(seed, R, int(t_max), M, dev, seed_dev)
         else:
             actions, logps, info = _rollout_outputs(R, int(t_max), dev)
             cs = cache.struct()

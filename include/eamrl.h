@@ -471,12 +471,24 @@ int eamrl_am_decode_step(int env, const eamrl_cache* cache_host, const eamrl_sta
 /* Whole decode loop in one launch (ConstructivePolicy.forward's while-loop, constructive/base.py:236-250):
  * repeats {decode step, env step} until every row is done or t_max steps were taken.  actions/logps are
  * [R][t_max] (right-padded: finished CVRP rows keep selecting the depot, logp 0).  noise [R][t_max][M],
- * given [R][t_given].  steps_out (device int32): number of steps executed = max over rows.  With top_k / top_p
- * filtering the streaming kernel is used (the register-resident one does not filter). */
+ * given [R][t_given].  steps_out (device int32): number of steps executed = max over rows.  top_k / top_p as in
+ * eamrl_am_decode_step, bit for bit: a filtered call runs on the register-resident kernel's filtering variant for graphs
+ * up to 112 nodes (E = 128, H = 8; multistart batches included -- the start-sharing kernel does not filter) and on the
+ * streaming kernel otherwise. */
 int eamrl_am_rollout(int env, const eamrl_cache* cache_host, const eamrl_state* state_host, int64_t R, int mode,
                      const float* noise, const int64_t* given, int t_given, float tanh_clip, float temperature,
                      int top_k, double top_p, int t_max, int64_t* actions, float* logps, int32_t* steps_out,
                      uint32_t* status, void* stream);
+
+/* Which kernel eamrl_am_rollout / _seeded runs for this shape: EAMRL_KERNEL_MS_MFMA | _RESIDENT | _STREAM (< 0: bad
+ * arguments).  Host only, nothing is launched and no pointer of the cache is followed; it is the function the dispatcher
+ * itself branches on (the eamrl_debug_set switches included), asked before a state exists: the answer assumes a state
+ * with every pointer its env needs (eamrl_state); a multistart call whose state lacks one that the start-sharing kernel
+ * reads is served by the next kernel in the list instead.  top_k = 0 and top_p of 0 or 1 mean no filter. */
+#define EAMRL_KERNEL_MS_MFMA 0  /* start-sharing MFMA kernel (multistart batches, no filter) */
+#define EAMRL_KERNEL_RESIDENT 1 /* register-resident kernel (<= 128 nodes; <= 112 under a filter) */
+#define EAMRL_KERNEL_STREAM 2   /* streaming kernel (any size) */
+int eamrl_rollout_kernel(int env, const eamrl_cache* cache_host, int64_t R, int t_max, int top_k, double top_p);
 
 /* Sampling without a noise tensor.  The Exp(1) draw of (row r, step t, node n) is a pure function of the call's seed:
  * Philox4x32-10 on the counter (n / 4, t, r) with the seed as key, word n % 4 -> u = (2 (x >> 9) + 1) 2^-24 -> -log(u)

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of single kernels at the TSP-100 B=1024 shapes (run on the GPU box).
 
-    python tools/kernel_bench.py gemm | mha | decode | ea | two_opt | train | all      [--iters 20] [--dump DIR]
+    python tools/kernel_bench.py gemm | mha | decode | filtered | ea | two_opt | train | all      [--iters 20] [--dump DIR]
+                                 [--json FILE]   (filtered: the results as JSON)
+decode, filtered and train run only when named; `all` is gemm, mha, ea and two_opt.
 """
 import argparse
 import os
@@ -77,6 +79,78 @@ def bench_decode(iters, t_max=None):
         torch.cuda.synchronize()
         times.append(e0.elapsed_time(e1) * 1e3)
     print(f"decode resident t_max={t_max or M}: {sorted(times[2:])[len(times[2:]) // 2]:8.1f} us (median, events around ops.rollout)")
+
+
+def bench_filtered(iters, json_path=None):
+    """Top-k / top-p sampling rollouts (ops.rollout, untrained policy, seeded instances and noise) per shape on three paths:
+    the default dispatch (register-resident kernel, filtering variant), the streaming kernel forced (eamrl_debug_set(1, 1):
+    where filtered calls ran before the resident kernel filtered) and the unfiltered resident kernel on the same shape (the
+    start-sharing MFMA kernel switched off for the multistart shape), which gives the cost of the filter stage itself.
+    HIP events around the launch on a fresh state each, median of `iters` after 3 warm-up launches."""
+    import json
+
+    import eam_rl4co_amd as ea
+    from eam_rl4co_amd import _lib
+    from eam_rl4co_amd.policy import _env_step_, _max_decode_steps, state_from_td
+
+    lib = _lib.load()
+    dev = "cuda"
+    shapes = [("tsp", 100, 1024, 0, dict(top_p=0.9)), ("tsp", 100, 1024, 0, dict(top_k=10)), ("cvrp", 100, 1024, 0, dict(top_p=0.9)),
+              ("tsp", 100, 64, 100, dict(top_p=0.9)), ("tsp", 20, 128, 0, dict(top_p=0.9))]
+    results = []
+    for env_name, N, B, S, filt in shapes:
+        torch.manual_seed(11)
+        env = ea.get_env(env_name, generator_params=dict(num_loc=N), seed=5)
+        td = env.reset(batch_size=[B]).to(dev)
+        pol = ea.AttentionModelPolicy(env_name=env_name).eval().to(dev)
+        with torch.no_grad():
+            emb, _ = pol.encoder(td)
+            cache = pol.decoder._precompute_cache(emb, num_starts=S)
+        M, R = td["action_mask"].shape[1], B * max(S, 1)
+        t_max = _max_decode_steps(env_name, M, 1 if S else 0)
+        noise = ops.exp1_noise(7, R, t_max, M, dev)
+
+        def fresh():
+            st = state_from_td(env_name, td, S)
+            if S:
+                _env_step_(st, torch.arange(S, device=dev).repeat_interleave(B) + (0 if env_name == "tsp" else 1))
+            return st
+
+        def measure(kw, keys):
+            for k in keys:
+                lib.eamrl_debug_set(k, 1)
+            try:
+                kernel = ops.rollout_kernel(env_name, cache, R, t_max, **kw)
+                times, steps = [], 0
+                for i in range(iters + 3):
+                    st = fresh()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    e0.record()
+                    _, _, info = ops.rollout(st, cache, "sampling", noise=noise, t_max=t_max, **kw)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    if i >= 3:
+                        times.append(e0.elapsed_time(e1) * 1e3)
+                    steps = int(info[0])
+                    assert int(info[1]) == 0
+            finally:
+                for k in keys:
+                    lib.eamrl_debug_set(k, 0)
+            times.sort()
+            return dict(kernel=kernel, median_us=times[len(times) // 2], min_us=times[0], max_us=times[-1], steps=steps)
+
+        row = dict(env=env_name, num_loc=N, batch=B, starts=S, filter=filt, iters=iters,
+                   default=measure(filt, ()), stream_forced=measure(filt, (1,)), unfiltered_resident=measure({}, (11,) if S else ()))
+        results.append(row)
+        d, f, u = row["default"], row["stream_forced"], row["unfiltered_resident"]
+        print(f"filtered {env_name}{N} B={B} S={S} {filt}: {d['kernel']} {d['median_us']:9.1f} us [{d['min_us']:.1f}, {d['max_us']:.1f}]   "
+              f"{f['kernel']} {f['median_us']:9.1f} us [{f['min_us']:.1f}, {f['max_us']:.1f}]   unfiltered {u['kernel']} "
+              f"{u['median_us']:9.1f} us   ({d['steps']} / {f['steps']} / {u['steps']} steps; median of {iters})", flush=True)
+    if json_path:
+        os.makedirs(os.path.dirname(os.path.abspath(json_path)), exist_ok=True)
+        with open(json_path, "w") as fh:
+            json.dump(dict(what="kernel_bench filtered", device=torch.cuda.get_device_name(0), results=results), fh, indent=1)
 
 
 def bench_ea(iters, dump=None):
@@ -211,6 +285,7 @@ def main():
     ap.add_argument("what", nargs="?", default="all")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--dump", default=None, metavar="DIR", help="ea: save every case's resulting pop and fitness tensors")
+    ap.add_argument("--json", default=None, metavar="FILE", help="filtered: write the results as JSON")
     ap.add_argument("--bm128", type=int, default=0)
     ap.add_argument("--generic-epilogue", type=int, default=0, help="1: run-time configured GEMM epilogue (A/B against the templates)")
     a = ap.parse_args()
@@ -221,6 +296,8 @@ def main():
         bench_gemm(a.iters)
     if a.what in ("mha", "all"):
         bench_mha(a.iters)
+    if a.what in ("filtered",):
+        bench_filtered(a.iters, a.json)
     if a.what in ("ea", "all"):
         bench_ea(a.iters, a.dump)
     if a.what in ("two_opt", "all"):
