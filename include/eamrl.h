@@ -360,7 +360,7 @@ int eamrl_pointer_attention(const float* query, const float* key, const float* v
  * Not bit-exact by contract: hardware exp / log, tile-order sums; log-probs within 1e-5 of the rollout's. */
 typedef struct eamrl_reeval {
     const float *K, *V, *Lp, *Pa, *Pb; int64_t ld;          /* [B][M][.] fp32, common row stride ld (floats), 16-byte aligned rows */
-    const float* gctx; const float* Cvec; int NC;           /* [B][E] or NULL; [NC][E] (NC <= 4 forward, <= 2 backward) */
+    const float* gctx; const float* Cvec; int NC;           /* [B][E] or NULL; [NC][E] (NC <= 4 forward, <= 2 backward and with key chunks) */
     const int32_t* idxA; const int32_t* idxB; const float* sc;
     const uint32_t* maskbits; const int64_t* actions;       /* actions [R][T] */
     int64_t B, R; int S, T, M, tstart, nchunk; float clip, temp;      /* nchunk: workgroups per instance (rows split) */

@@ -560,9 +560,13 @@ def test_linear_autograd_function_matches_torch(relu, with_res):
     ("am_sdvrp", "sdvrp", 130, 2, 0, None), ("am_sdvrp", "sdvrp", 240, 2, 3, None),
     # SDVRP: the dynamic embedding's rank-one terms (remaining demands per step) in all three kernels
     ("am_sdvrp", "sdvrp", 20, 5, 0, None), ("am_sdvrp", "sdvrp", 50, 3, 6, None), ("am_sdvrp", "sdvrp", 100, 2, 3, None),
-    # the gather kernel's cooperative bins (the depot of CVRP names > 512 queries of an instance) and its own chunking
-    # (more than 24,576 queries of an instance: 250 samples x 100 steps)
+    # many rows of one instance: the depot of CVRP names more than 512 queries of an instance, 250 samples x 100 steps are more
+    # than 24,576.  Both get nchunk = S workgroups of ONE row each (B <= 2), so neither reaches the gather kernel's cooperative
+    # bins (more than 512 queries of a workgroup on one node: tests/test_gpu_reeval.py, gather_big_bin) nor its own chunking
+    # (more than 24,576 queries of a WORKGROUP, about 12.6 M queries in all: not covered by any test)
     ("am_cvrp", "cvrp", 50, 2, 50, None), ("am_tsp", "tsp", 100, 1, 250, False),
+    # several rows of an instance in one workgroup: nchunk = 8 for 20 starts of 64 instances (2 or 3 rows each)
+    ("pomo_tsp", "tsp", 20, 64, 20, None),
 ])
 def test_native_reevaluation_matches_autograd(cfg, env_name, N, B, ns, ms):
     """eamrl_reeval_forward / _backward (fp32 MFMA kernels) against the PyTorch-autograd re-evaluation of the same actions:
