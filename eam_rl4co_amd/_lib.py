@@ -137,6 +137,8 @@ PROTOTYPES = {
     "eamrl_ea_prize_run": [_i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, C.c_double, C.c_double, C.c_double, _i32,
                            _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "eamrl_ea_tsp_run": [_vp, _vp, _vp, _i64, _i32, _i32, _i32, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp],
+    "eamrl_math_probe": [_i32, _vp, _vp, _i64, _vp],
+    "eamrl_wave_probe": [_i32, _vp, _vp, _vp, _vp, _i64, _vp],
 }
 _RESTYPES = {"eamrl_last_error": C.c_char_p, "eamrl_linear_wgrad_scratch": C.c_int64,
              "eamrl_small_linear_wgrad_scratch": C.c_int64, "eamrl_batchnorm_backward_scratch": C.c_int64,

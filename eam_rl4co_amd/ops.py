@@ -1380,6 +1380,54 @@ def exp1_noise(seed: int, R: int, T: int, M: int, device="cuda", seed_dev=None):
     return out
 
 
+# EAMRL_PROBE_* / EAMRL_WPROBE_* of include/eamrl.h (test support: the functions of csrc/dmath.hpp one at a time)
+MATH_PROBES = {"expf": 0, "expf2": 1, "expf2_nonpos": 2, "expf2_nonpos_x2": 3, "expf4": 4, "expf4_nonpos": 5, "logf": 6,
+               "logf4": 7, "rcpf": 8, "tanhf": 9, "tanhf2": 10, "tanhf4": 11, "exp1_from_bits": 12, "philox": 13}
+WAVE_PROBES = {"tree_sum": 0, "max": 1, "argmax": 2, "vmax": 3, "vmax3": 4, "vmax5": 5, "zrot": 6, "z_total_rel": 7}
+
+
+def math_probe(fn: str, bits):
+    """y[i] = f(x[i]) for one function of dmath.hpp (MATH_PROBES); `bits` is an int32 device tensor holding the float32 (or
+    noise word) bit patterns, the result likewise.  Elements 4 g .. 4 g + 3 fill the slots of one wide call; the length must
+    be a multiple of 4.  "philox": bits [G, 6] (counter, key) -> [G, 4] words."""
+    lib = _lib.load()
+    _need_gpu(bits, "bits")
+    if bits.dtype != torch.int32 or not bits.is_contiguous():
+        raise TypeError("math_probe: bits must be a contiguous int32 tensor (bit patterns)")
+    if fn == "philox":
+        if bits.dim() != 2 or bits.shape[1] != 6:
+            raise ValueError("math_probe: philox takes [G, 6] words")
+        out = torch.empty(bits.shape[0], 4, dtype=torch.int32, device=bits.device)
+    else:
+        out = torch.empty_like(bits)
+    rc = lib.eamrl_math_probe(MATH_PROBES[fn], _ptr(bits), _ptr(out), out.numel(), _stream(bits))
+    if rc != 0:
+        raise RuntimeError(f"eamrl_math_probe({fn}) failed ({rc}): n = {out.numel()} must be a multiple of 4")
+    return out
+
+
+def wave_probe(fn: str, v_bits, idx=None):
+    """One wavefront primitive of dmath.hpp (WAVE_PROBES) on [W, 64] cases, one 64-lane wavefront each; v_bits int32 bit
+    patterns, idx int32 [W, 64] (argmax: the lane's index; zrot / z_total_rel: idx[w, 0] = start, idx[w, 1] = n1).
+    -> out_v [W, 64] int32 bit patterns of what every lane ends with (argmax: (out_v, out_i))."""
+    lib = _lib.load()
+    _need_gpu(v_bits, "v_bits")
+    if v_bits.dtype != torch.int32 or not v_bits.is_contiguous() or v_bits.dim() != 2 or v_bits.shape[1] != 64:
+        raise TypeError("wave_probe: v_bits must be a contiguous int32 [W, 64] tensor")
+    needs_idx = fn in ("argmax", "zrot", "z_total_rel")
+    if needs_idx:
+        if idx is None or idx.dtype != torch.int32 or not idx.is_contiguous() or idx.shape != v_bits.shape \
+                or idx.device != v_bits.device:
+            raise TypeError(f"wave_probe: {fn} needs an int32 idx of v_bits' shape on its device")
+    out_v = torch.empty_like(v_bits)
+    out_i = torch.empty_like(v_bits) if fn == "argmax" else None
+    rc = lib.eamrl_wave_probe(WAVE_PROBES[fn], _ptr(v_bits), _ptr(idx if needs_idx else None), _ptr(out_v), _ptr(out_i),
+                              v_bits.shape[0], _stream(v_bits))
+    if rc != 0:
+        raise RuntimeError(f"eamrl_wave_probe({fn}) failed ({rc})")
+    return (out_v, out_i) if fn == "argmax" else out_v
+
+
 ROLLOUT_KERNELS = ("ms_mfma", "resident", "stream")       # EAMRL_KERNEL_* of include/eamrl.h
 
 

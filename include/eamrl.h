@@ -668,6 +668,51 @@ int eamrl_ea_prize_run(int env, const float* locs, const float* prize, const flo
                        const double* cross_rand, const double* cross_u, const double* mut_rand, const double* mut_u,
                        void* stream);
 
+/* ---- test support: the defined device math, one function at a time ---------------------------------------- */
+
+/* Probes of csrc/dmath.hpp (csrc/math_probe.hip).  No product path calls them; the tests hold each function of the header to
+ * the oracle bit for bit through them.  They pin the header's functions as this library's flags compile them, not each
+ * inlined copy inside the kernels that include the header.  Values travel as 32-bit words, so NaN payloads and -0 arrive
+ * untouched.  Return 0 = enqueued, EAMRL_E_ARG / EAMRL_E_LAUNCH otherwise (eamrl_last_error is not set).
+ *
+ * eamrl_math_probe: y[i] = f(x[i]), n a multiple of 4.  One thread takes the elements 4 g .. 4 g + 3: they are the four slots
+ * of a four-wide call, the 2 + 2 slots of two two-wide calls (one call of the _X2 form), four scalar calls.
+ * EAMRL_PROBE_EXP1_FROM_BITS reads x as the uint32 words.  EAMRL_PROBE_PHILOX: case g reads the SIX words x[6 g ..] =
+ * counter c0..c3, key k0 k1 and writes the four Philox4x32-10 words y[4 g ..] (x holds 6 n / 4 words). */
+#define EAMRL_PROBE_EXPF 0
+#define EAMRL_PROBE_EXPF2 1
+#define EAMRL_PROBE_EXPF2_NONPOS 2
+#define EAMRL_PROBE_EXPF2_NONPOS_X2 3
+#define EAMRL_PROBE_EXPF4 4
+#define EAMRL_PROBE_EXPF4_NONPOS 5
+#define EAMRL_PROBE_LOGF 6
+#define EAMRL_PROBE_LOGF4 7
+#define EAMRL_PROBE_RCPF 8
+#define EAMRL_PROBE_TANHF 9
+#define EAMRL_PROBE_TANHF2 10
+#define EAMRL_PROBE_TANHF4 11
+#define EAMRL_PROBE_EXP1_FROM_BITS 12
+#define EAMRL_PROBE_PHILOX 13
+int eamrl_math_probe(int fn, const uint32_t* x, uint32_t* y, int64_t n, void* stream);
+
+/* eamrl_wave_probe: one full 64-lane wavefront per case w; v, out_v [nwaves][64] float words, idx, out_i [nwaves][64] i32.
+ * Lane l ends with out_v[w][l] (and out_i[w][l] for ARGMAX): every lane's result is stored.  a_k = v[w][(l + k) % 64].
+ *   TREE_SUM / MAX: wave_tree_sum(a_0) / wave_max(a_0);  ARGMAX: wave_argmax(a_0, idx[w][l]);
+ *   VMAX / VMAX3 / VMAX5: vmax_raw(a_0, a_1) / vmax3_raw(a_0, a_1, a_2) / vmax5_raw(a_0 .. a_4)  (lane-local);
+ *   ZROT: start = idx[w][0], n1 = idx[w][1]; a zeroed ZRot<float> gets add(a_0) .. add(a_{n1-start-1}), result total(n1);
+ *   Z_TOTAL_REL: z[k] = sequential sum of the a_i with i = k (mod 4), i < n1 - start; result z_total_rel(z0..z3, start).
+ * idx may be NULL for the forms that do not read it, out_i for all but ARGMAX. */
+#define EAMRL_WPROBE_TREE_SUM 0
+#define EAMRL_WPROBE_MAX 1
+#define EAMRL_WPROBE_ARGMAX 2
+#define EAMRL_WPROBE_VMAX 3
+#define EAMRL_WPROBE_VMAX3 4
+#define EAMRL_WPROBE_VMAX5 5
+#define EAMRL_WPROBE_ZROT 6
+#define EAMRL_WPROBE_Z_TOTAL_REL 7
+int eamrl_wave_probe(int fn, const uint32_t* v, const int32_t* idx, uint32_t* out_v, int32_t* out_i, int64_t nwaves,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

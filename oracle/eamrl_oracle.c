@@ -22,6 +22,7 @@
  *   orc_init_embed_* .......... rl4co/models/nn/env_embeddings/init.py:55-68,115-138
  *   orc_pointer_attention ..... rl4co/models/nn/attention.py:282-328 (PointerAttention.forward; the pointer= injection point)
  *   orc_exp1_noise ............ the counter-based Exp(1) draws of in-kernel sampling (replaces torch.multinomial's, utils/decoding.py:403-417)
+ *   orc_math_fn, orc_philox_words  the defined transcendentals and the generator's words one by one (csrc/dmath.hpp is held to them)
  *   orc_mean_nodes ............ rl4co/models/zoo/am/decoder.py:225-227 (embeddings.mean(1))
  *   orc_decode_step ........... rl4co/models/zoo/am/decoder.py:133-198 (_compute_q/_compute_kvl/forward),
  *                               rl4co/models/nn/env_embeddings/context.py:50-74,105-157,
@@ -188,6 +189,38 @@ ORC_API void orc_exp1_noise(uint64_t seed, float* noise, long R, int T, int M)
                     noise[((long)r * T + t) * M + 4 * q + i] = 0.0f - d_logf(u);
                 }
             }
+}
+
+/* One defined function over raw 32-bit words (tests/test_gpu_math.py, tests/test_host_math.py): y[i] = f(x[i]) with no domain
+ * guard and no float conversion on the way, so NaN payloads and -0 arrive as given.  fn: 0 d_expf, 1 d_logf, 2 d_rcpf,
+ * 3 d_tanhf, 4 the noise word -> Exp(1) draw of orc_exp1_noise (x is the Philox word). */
+ORC_API int orc_math_fn(int fn, const uint32_t* x, uint32_t* y, long n)
+{
+    if (fn < 0 || fn > 4) return -1;
+#pragma omp parallel for schedule(static)
+    for (long i = 0; i < n; ++i) {
+        const float a = bits2f(x[i]);
+        float r;
+        switch (fn) {
+        case 0: r = d_expf(a); break;
+        case 1: r = d_logf(a); break;
+        case 2: r = d_rcpf(a); break;
+        case 3: r = d_tanhf(a); break;
+        default: r = 0.0f - d_logf((float)(2u * (x[i] >> 9) + 1u) * 5.9604644775390625e-8f); break;
+        }
+        y[i] = f2bits(r);
+    }
+    return 0;
+}
+
+/* The Philox4x32-10 words of orc_exp1_noise: case g reads counter c0..c3 and key k0 k1 from ck[6 g ..], writes out[4 g ..]. */
+ORC_API void orc_philox_words(const uint32_t* ck, uint32_t* out, long ncases)
+{
+    for (long g = 0; g < ncases; ++g) {
+        uint32_t c[4] = {ck[6 * g], ck[6 * g + 1], ck[6 * g + 2], ck[6 * g + 3]};
+        philox4x32_10(c, ck[6 * g + 4], ck[6 * g + 5]);
+        for (int i = 0; i < 4; ++i) out[4 * g + i] = c[i];
+    }
 }
 
 /* adjacent-pair tree inside 64-blocks, blocks ascending */

@@ -108,6 +108,27 @@ def math_probe(x):
     return e, l, t
 
 
+MATH_FNS = {"exp": 0, "log": 1, "rcp": 2, "tanh": 3, "exp1_from_bits": 4}
+
+
+def math_fn(name, bits):
+    """One defined function (MATH_FNS) over uint32 bit patterns -> uint32 bit patterns of the float32 results.  No domain guard
+    and no float conversion: what d_logf makes of a denormal is returned as it is.  "exp1_from_bits" takes the noise words."""
+    bits = np.ascontiguousarray(bits, dtype=np.uint32).ravel()
+    out = np.empty_like(bits)
+    rc = lib().orc_math_fn(C.c_int(MATH_FNS[name]), _p(bits), _p(out), C.c_long(bits.size))
+    assert rc == 0
+    return out
+
+
+def philox_words(counter_key):
+    """[G, 6] uint32 (counter c0..c3, key k0 k1) -> [G, 4] Philox4x32-10 words, as orc_exp1_noise draws them."""
+    ck = np.ascontiguousarray(counter_key, dtype=np.uint32).reshape(-1, 6)
+    out = np.empty((ck.shape[0], 4), np.uint32)
+    lib().orc_philox_words(_p(ck), _p(out), C.c_long(ck.shape[0]))
+    return out
+
+
 def lane_tree(v):
     v = _f32(v).ravel()
     return np.float32(lib().orc_lane_tree(_p(v), C.c_int(v.size)))
