@@ -105,6 +105,29 @@ __attribute__((visibility("default"))) int eamrl_pctsp_step_mask(uint8_t* visite
                                  (hipStream_t)stream), "eamrl_pctsp_step_mask");
 }
 
+__attribute__((visibility("default"))) int eamrl_pdp_step_mask(uint8_t* visited, uint8_t* to_deliver, int64_t* cur,
+                                                              const int64_t* action, uint8_t* mask, uint8_t* done, int64_t R,
+                                                              int M, void* stream)
+{
+    REQUIRE(visited && to_deliver && mask, "eamrl_pdp_step_mask");
+    REQUIRE(!action || (cur && done), "eamrl_pdp_step_mask");
+    REQUIRE(R >= 0 && M >= 3 && M % 2 == 1, "eamrl_pdp_step_mask");
+    if (R == 0) return 0;
+    return launched(launch_pdp(visited, to_deliver, cur, action, mask, done, R, M, (hipStream_t)stream), "eamrl_pdp_step_mask");
+}
+
+__attribute__((visibility("default"))) int eamrl_pdp_init_embedding(const float* locs, const float* Wd, const float* bd,
+                                                                   const float* Wp, const float* bp, const float* Wl,
+                                                                   const float* bl, float* h, int64_t B, int M, int E,
+                                                                   void* stream)
+{
+    REQUIRE(locs && Wd && Wp && Wl && h, "eamrl_pdp_init_embedding");
+    REQUIRE(B >= 0 && M >= 3 && M % 2 == 1 && E > 0, "eamrl_pdp_init_embedding");
+    if (B == 0) return 0;
+    return launched(launch_pdp_init_embedding(locs, Wd, bd, Wp, bp, Wl, bl, h, B, M, E, (hipStream_t)stream),
+                    "eamrl_pdp_init_embedding");
+}
+
 __attribute__((visibility("default"))) int eamrl_cvrptw_step_mask(uint8_t* visited, float* used, const float* vcap,
                                                                  const float* demand, int64_t* cur, float* time,
                                                                  const float* locs, const float* tw, const float* dur,
@@ -568,9 +591,9 @@ static int fill_args(const char* what, int env, const eamrl_cache* c, const eamr
                      uint32_t* status, DecArgs& a, bool seeded = false)
 {
     REQUIRE(c && s, what);
-    REQUIRE(env >= EAMRL_ENV_TSP && env <= EAMRL_ENV_CVRPTW, what);
+    REQUIRE(env >= EAMRL_ENV_TSP && env <= EAMRL_ENV_PDP, what);
     REQUIRE(mode == EAMRL_GREEDY || mode == EAMRL_SAMPLE || mode == EAMRL_EVALUATE, what);
-    REQUIRE(c->K && c->V && c->Lp && c->Pa && c->cvec, what);
+    REQUIRE(c->K && c->V && c->Lp && c->Pa && (c->cvec || env == EAMRL_ENV_PDP), what);
     REQUIRE(c->B > 0 && c->M > 0 && c->E > 0 && c->H > 0, what);
     REQUIRE(c->E % c->H == 0 && (c->E / c->H) % 4 == 0 && c->E % (4 * EAMRL_NCHUNK) == 0, what);
     REQUIRE(c->ld >= c->E && c->ld % 4 == 0, what);
@@ -584,6 +607,7 @@ static int fill_args(const char* what, int env, const eamrl_cache* c, const eamr
     if (env == EAMRL_ENV_PCTSP) REQUIRE(s->used && s->vcap && c->M >= 2, what);
     if (env == EAMRL_ENV_OP) REQUIRE(s->used && s->vcap && c->M >= 2, what);
     if (env == EAMRL_ENV_CVRPTW) REQUIRE(s->used && s->vcap && s->time && c->M >= 2, what);
+    if (env == EAMRL_ENV_PDP) REQUIRE(c->M >= 3 && c->M % 2 == 1, what);
     if (mode == EAMRL_SAMPLE) REQUIRE(noise != nullptr || seeded, what);
     if (mode == EAMRL_EVALUATE) REQUIRE(given != nullptr, what);
     a = DecArgs{};
@@ -593,6 +617,7 @@ static int fill_args(const char* what, int env, const eamrl_cache* c, const eamr
     a.mask = s->mask; a.visited = s->visited; a.done = s->done;
     a.rem = s->rem; a.dyn = c->dyn; a.locs = s->locs; a.time = s->time; a.tw = s->tw; a.dur = s->dur;
     a.heads_out = s->heads_out;
+    a.to_deliver = s->to_deliver;
     a.seed = 0; a.seed_dev = nullptr; a.use_rng = 0;
     a.R = R; a.mode = mode; a.noise = noise; a.given = given; a.clip = clip; a.temp = temp; a.top_k = top_k; a.top_p = top_p; a.status = status;
     return 0;
@@ -617,6 +642,7 @@ __attribute__((visibility("default"))) int eamrl_am_decode_step(int env, const e
         if (env == EAMRL_ENV_PCTSP) REQUIRE(a.visited && a.demand && a.istep, "eamrl_am_decode_step");
         if (env == EAMRL_ENV_OP) REQUIRE(a.visited && a.demand && a.istep && a.locs, "eamrl_am_decode_step");
         if (env == EAMRL_ENV_CVRPTW) REQUIRE(a.visited && a.demand && a.locs && a.tw && a.dur, "eamrl_am_decode_step");
+        if (env == EAMRL_ENV_PDP) REQUIRE(a.visited && a.to_deliver, "eamrl_am_decode_step");
     }
     a.fuse_env = fuse_env_step;
     a.action = action; a.logp = logp; a.logprobs_all = logprobs_all; a.logits_raw = logits_raw;
@@ -638,7 +664,7 @@ __attribute__((visibility("default"))) int eamrl_rollout_kernel(int env, const e
 {
     const char* what = "eamrl_rollout_kernel";
     REQUIRE(cache_host, what);
-    REQUIRE(env >= EAMRL_ENV_TSP && env <= EAMRL_ENV_CVRPTW, what);
+    REQUIRE(env >= EAMRL_ENV_TSP && env <= EAMRL_ENV_PDP, what);
     REQUIRE(cache_host->B > 0 && cache_host->M > 0 && cache_host->E > 0 && cache_host->H > 0, what);
     REQUIRE(R > 0 && R % cache_host->B == 0 && R <= 0x7fffffffLL && t_max > 0, what);
     REQUIRE(top_k >= 0 && top_p >= 0.0 && top_p <= 1.0, what);
@@ -664,6 +690,7 @@ __attribute__((visibility("default"))) int eamrl_am_rollout(int env, const eamrl
     if (env == EAMRL_ENV_PCTSP) REQUIRE(a.visited && a.demand && a.istep, "eamrl_am_rollout");
     if (env == EAMRL_ENV_OP) REQUIRE(a.visited && a.demand && a.istep && a.locs, "eamrl_am_rollout");
     if (env == EAMRL_ENV_CVRPTW) REQUIRE(a.visited && a.demand && a.locs && a.tw && a.dur, "eamrl_am_rollout");
+    if (env == EAMRL_ENV_PDP) REQUIRE(a.visited && a.to_deliver, "eamrl_am_rollout");
     if (mode == EAMRL_EVALUATE) REQUIRE(t_given > 0, "eamrl_am_rollout");
     a.fuse_env = 1; a.t_max = t_max; a.t_given = t_given;
     a.action = actions; a.logp = logps; a.steps_out = steps_out;
@@ -739,11 +766,20 @@ __attribute__((visibility("default"))) int eamrl_rollout_finish(int env, const f
                                                                const float* vcap, float* reward, float* ll, int32_t* bad,
                                                                int64_t R, int64_t B, int M, int T, void* stream)
 {
-    REQUIRE(env == EAMRL_ENV_TSP || env == EAMRL_ENV_CVRP, "eamrl_rollout_finish (TSP or CVRP)");
+    REQUIRE(env == EAMRL_ENV_TSP || env == EAMRL_ENV_CVRP || env == EAMRL_ENV_PDP, "eamrl_rollout_finish (TSP, CVRP or PDP)");
     REQUIRE(locs && actions && R >= 0 && B > 0 && M >= 2 && M <= 4096 && T > 0, "eamrl_rollout_finish");
     REQUIRE(!ll || (logp && ld >= T), "eamrl_rollout_finish (logp)");
     if (env == EAMRL_ENV_CVRP && bad) REQUIRE(demand && vcap, "eamrl_rollout_finish (demand, vcap)");
     if (R == 0) return 0;
+    if (env == EAMRL_ENV_PDP) {     // reward and log-likelihood as for any depot env; the verdict by the PDP kernel
+        REQUIRE(!bad || (M % 2 == 1 && (T == M - 1 || T == M)), "eamrl_rollout_finish (PDP: T = N or N + 1)");
+        if (reward || ll) {
+            const int rc = launch_rollout_finish(env, locs, actions, logp, ld, nullptr, nullptr, reward, ll, nullptr, R, B, M, T,
+                                                 (hipStream_t)stream);
+            if (rc) return launched(rc, "eamrl_rollout_finish");
+        }
+        return bad ? launched(launch_pdp_check(actions, R, M, T, bad, (hipStream_t)stream), "eamrl_rollout_finish") : 0;
+    }
     return launched(launch_rollout_finish(env, locs, actions, logp, ld, demand, vcap, reward, ll, bad, R, B, M, T,
                                           (hipStream_t)stream), "eamrl_rollout_finish");
 }
@@ -774,6 +810,11 @@ __attribute__((visibility("default"))) int eamrl_check_solution(int env, const i
                                                                int32_t* bad, void* stream)
 {
     REQUIRE(actions && bad && R >= 0 && B > 0 && N > 0 && T > 0, "eamrl_check_solution");
+    if (env == EAMRL_ENV_PDP) {
+        REQUIRE(N >= 2 && N % 2 == 0 && N < 4096 && (T == N || T == N + 1), "eamrl_check_solution (PDP: N even, T = N or N + 1)");
+        if (R == 0) return 0;
+        return launched(launch_pdp_check(actions, R, N + 1, T, bad, (hipStream_t)stream), "eamrl_check_solution");
+    }
     REQUIRE(env >= EAMRL_ENV_TSP && env <= EAMRL_ENV_PCTSP, "eamrl_check_solution");
     if (env == EAMRL_ENV_CVRP || env == EAMRL_ENV_SDVRP) REQUIRE(demand && vcap, "eamrl_check_solution");
     if (env == EAMRL_ENV_PCTSP) REQUIRE(demand != nullptr, "eamrl_check_solution");

@@ -28,6 +28,7 @@ struct DecArgs {
     int64_t* action; float* logp; float* logprobs_all; float* logits_raw;
     int32_t* steps_out; uint32_t* status;
     float* heads_out;   // optional [R][t_max][E]: the glimpse output of every decode step (start-sharing MFMA kernel only)
+    uint8_t* to_deliver;   // PDP: [R][M] nodes whose turn has come (the depot, the pickups, deliveries of visited pickups)
 };
 
 // LDS carve for one row handled by one workgroup.

@@ -95,6 +95,10 @@ __device__ void decode_row(const DecArgs& a, const RowLds& l, int64_t r, const R
         if (ENV == EAMRL_ENV_TSP) {
             if (s.istep == 0) ctx = a.cvec[e];
             else ctx = a.Pa[(bi * M + s.first) * ld + e] + a.Pb[(bi * M + s.cur) * ld + e];
+        } else if (ENV == EAMRL_ENV_PDP) {
+            // PDPContext (context.py:242-253): the current node's row alone, no state column.  Spelled as the depot envs' fma with
+            // a zero column and a zero state -- the expression the CPU oracle's CVRP-form step evaluates (a -0 element gives +0)
+            ctx = fma_(0.0f, 0.0f, a.Pa[(bi * M + s.cur) * ld + e]);
         } else {
             // VRPContext: free capacity; PCTSPContext: clamp(prize_required - cur_total_prize, min=0)  (context.py:160-208)
             float state = s.vcap - s.used;
@@ -458,7 +462,22 @@ __device__ bool env_step_row(const DecArgs& a, const RowLds& l, uint8_t* vis, fl
     const int tid = threadIdx.x;
     const int M = a.M;
     __syncthreads();  // all readers of msk / x are done
-    if (ENV == EAMRL_ENV_SDVRP) {
+    if (ENV == EAMRL_ENV_PDP) {
+        // PDPEnv._step (pdp/env.py:66-106): visit the node, open its partner (a + N/2) % (N + 1) -- the reference's modulo, which
+        // for a delivery lands on the depot or a pickup, already open --, mask = unvisited and to deliver
+        uint8_t* tdl = reinterpret_cast<uint8_t*>(rem);
+        const int64_t d = (act + (M - 1) / 2) % M;
+        s.cur = act;
+        if (tid == 0) { vis[act] = 1; tdl[d] = 1; }
+        __syncthreads();
+        int all_vis = 1;
+        for (int n = tid; n < M; n += BLOCK) {
+            const int v = vis[n] != 0;
+            l.msk[n] = (!v) & (tdl[n] != 0);
+            all_vis &= v;
+        }
+        return __syncthreads_and(all_vis) != 0;
+    } else if (ENV == EAMRL_ENV_SDVRP) {
         // SDVRPEnv._step + get_action_mask (sdvrp/env.py:58-92,137-146): deliver min(remaining demand, free capacity)
         const float sel = rem[act];
         const float free_cap = s.vcap - s.used;
@@ -592,6 +611,11 @@ __device__ __forceinline__ void load_row_state(const DecArgs& a, int64_t r, RowS
         s.istep = a.istep[r];
         s.used = 0.0f;
         s.vcap = 0.0f;
+    } else if (ENV == EAMRL_ENV_PDP) {
+        s.first = 0;
+        s.istep = 1;
+        s.used = 0.0f;
+        s.vcap = 0.0f;
     } else {
         s.first = 0;
         s.istep = (ENV == EAMRL_ENV_PCTSP || ENV == EAMRL_ENV_OP) ? a.istep[r] : 1;
@@ -609,15 +633,16 @@ __device__ __forceinline__ void store_row_state(const DecArgs& a, const RowLds& 
     __syncthreads();
     for (int n = tid; n < a.M; n += BLOCK) {
         a.mask[r * a.M + n] = l.msk[n];
-        if (ENV == EAMRL_ENV_CVRP || ENV == EAMRL_ENV_PCTSP || ENV == EAMRL_ENV_OP || ENV == EAMRL_ENV_CVRPTW)
+        if (ENV == EAMRL_ENV_CVRP || ENV == EAMRL_ENV_PCTSP || ENV == EAMRL_ENV_OP || ENV == EAMRL_ENV_CVRPTW || ENV == EAMRL_ENV_PDP)
             a.visited[r * a.M + n] = vis[n];
         if (ENV == EAMRL_ENV_SDVRP) a.rem[r * a.M + n] = rem[n];
+        if (ENV == EAMRL_ENV_PDP) a.to_deliver[r * a.M + n] = reinterpret_cast<const uint8_t*>(rem)[n];
     }
     if (tid == 0) {
         a.cur[r] = s.cur;
         a.done[r] = done ? 1 : 0;
         if (ENV == EAMRL_ENV_TSP) { a.first[r] = s.first; a.istep[r] = s.istep; }
-        else a.used[r] = s.used;
+        else if (ENV != EAMRL_ENV_PDP) a.used[r] = s.used;
         if (ENV == EAMRL_ENV_PCTSP || ENV == EAMRL_ENV_OP) a.istep[r] = s.istep;
         if (ENV == EAMRL_ENV_CVRPTW) a.time[r] = s.now;
     }
@@ -631,9 +656,10 @@ __device__ __forceinline__ void load_row_lds(const DecArgs& a, const RowLds& l, 
     const int tid = threadIdx.x;
     for (int n = tid; n < a.M; n += BLOCK) {
         l.msk[n] = a.mask[r * a.M + n];
-        if ((ENV == EAMRL_ENV_CVRP || ENV == EAMRL_ENV_PCTSP || ENV == EAMRL_ENV_OP || ENV == EAMRL_ENV_CVRPTW) && want_vis)
+        if ((ENV == EAMRL_ENV_CVRP || ENV == EAMRL_ENV_PCTSP || ENV == EAMRL_ENV_OP || ENV == EAMRL_ENV_CVRPTW || ENV == EAMRL_ENV_PDP) && want_vis)
             vis[n] = a.visited[r * a.M + n];
         if (ENV == EAMRL_ENV_SDVRP) rem[n] = a.rem[r * a.M + n];
+        if (ENV == EAMRL_ENV_PDP && want_vis) reinterpret_cast<uint8_t*>(rem)[n] = a.to_deliver[r * a.M + n];   // behind `vis`
     }
     if (ENV == EAMRL_ENV_SDVRP)
         for (int e = tid; e < 3 * a.E; e += BLOCK) dyn[e] = a.dyn[e];
@@ -726,7 +752,7 @@ __global__ void k_rollout_pad(DecArgs a, int env)
 
 void launch_rollout_pad(int env, const DecArgs& a, hipStream_t st)
 {
-    if (env != EAMRL_ENV_TSP)
+    if (env != EAMRL_ENV_TSP && env != EAMRL_ENV_PDP)      // (PDP: every row takes the same number of steps)
         hipLaunchKernelGGL(k_rollout_pad, dim3((unsigned)((a.R + 255) / 256)), dim3(256), 0, st, a, env);
 }
 
@@ -736,6 +762,7 @@ static int launch_decode(int env, const DecArgs& a, bool rollout, hipStream_t st
     size_t lds = row_lds_bytes(a.M, a.E, a.H) + Mp;                       // + visited bytes
     if (env == EAMRL_ENV_SDVRP)                                            // + remaining demand + dynamic vectors + folds
         lds += 4 * Mp + 12 * (size_t)a.E + 4 * (2 * (size_t)a.H + EAMRL_NCHUNK);
+    if (env == EAMRL_ENV_PDP) lds += Mp;                                   // + to_deliver bytes
     if (lds > 160 * 1024) return EAMRL_E_ARG;
     dim3 grid((unsigned)a.R), block(BLOCK);
     void (*k)(DecArgs);
@@ -744,13 +771,15 @@ static int launch_decode(int env, const DecArgs& a, bool rollout, hipStream_t st
           : env == EAMRL_ENV_CVRP ? k_rollout_stream<EAMRL_ENV_CVRP>
           : env == EAMRL_ENV_SDVRP ? k_rollout_stream<EAMRL_ENV_SDVRP>
           : env == EAMRL_ENV_PCTSP ? k_rollout_stream<EAMRL_ENV_PCTSP>
-          : env == EAMRL_ENV_OP ? k_rollout_stream<EAMRL_ENV_OP> : k_rollout_stream<EAMRL_ENV_CVRPTW>;
+          : env == EAMRL_ENV_OP ? k_rollout_stream<EAMRL_ENV_OP>
+          : env == EAMRL_ENV_PDP ? k_rollout_stream<EAMRL_ENV_PDP> : k_rollout_stream<EAMRL_ENV_CVRPTW>;
     else
         k = env == EAMRL_ENV_TSP ? k_decode_step<EAMRL_ENV_TSP>
           : env == EAMRL_ENV_CVRP ? k_decode_step<EAMRL_ENV_CVRP>
           : env == EAMRL_ENV_SDVRP ? k_decode_step<EAMRL_ENV_SDVRP>
           : env == EAMRL_ENV_PCTSP ? k_decode_step<EAMRL_ENV_PCTSP>
-          : env == EAMRL_ENV_OP ? k_decode_step<EAMRL_ENV_OP> : k_decode_step<EAMRL_ENV_CVRPTW>;
+          : env == EAMRL_ENV_OP ? k_decode_step<EAMRL_ENV_OP>
+          : env == EAMRL_ENV_PDP ? k_decode_step<EAMRL_ENV_PDP> : k_decode_step<EAMRL_ENV_CVRPTW>;
     if (lds > 64 * 1024) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)lds) != hipSuccess)

@@ -96,6 +96,12 @@ int launch_cvrptw_check(const int64_t* actions, const float* locs, const float* 
 int launch_op(uint8_t* visited, float* tour_len, float* prize_tot, const float* prize, const float* locs, const float* maxlen,
               int64_t* cur, int64_t* istep, const int64_t* action, uint8_t* mask, uint8_t* done, int64_t R, int64_t B, int M,
               hipStream_t st);
+// pickup and delivery (pdp.hip)
+int launch_pdp(uint8_t* visited, uint8_t* to_deliver, int64_t* cur, const int64_t* action, uint8_t* mask, uint8_t* done, int64_t R,
+               int M, hipStream_t st);
+int launch_pdp_check(const int64_t* actions, int64_t R, int M, int T, int32_t* bad, hipStream_t st);
+int launch_pdp_init_embedding(const float* locs, const float* Wd, const float* bd, const float* Wp, const float* bp,
+                              const float* Wl, const float* bl, float* h, int64_t B, int M, int E, hipStream_t st);
 int launch_op_reward(const float* prize, const int64_t* actions, float* reward, int64_t R, int64_t B, int M, int T,
                      hipStream_t st);
 int launch_op_check(const int64_t* actions, const float* locs, const float* maxlen, int64_t R, int64_t B, int M, int T,

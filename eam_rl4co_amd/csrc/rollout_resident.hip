@@ -93,6 +93,7 @@ __global__ __launch_bounds__(RB, 2) void k_rollout_resident(DecArgs a, int S, in
     constexpr bool OP = ENV == EAMRL_ENV_OP;        // orienteering: dem = arrival limit per node, used = tour length
     constexpr bool TW = ENV == EAMRL_ENV_CVRPTW;    // CVRP + clock: coordinates and windows in LDS
     constexpr bool CV = ENV == EAMRL_ENV_CVRP || TW;
+    constexpr bool PD = ENV == EAMRL_ENV_PDP;       // pickup and delivery: two bit sets (visited, to deliver), no scalar state
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using L = ResLds<CP, res_tmax(ENV), res_sdf(ENV), res_xyf(ENV), res_twf(ENV)>;
     L& l = *reinterpret_cast<L*>(smem);
@@ -196,11 +197,20 @@ __global__ __launch_bounds__(RB, 2) void k_rollout_resident(DecArgs a, int S, in
     int64_t first = 0, cur = 0, istep = 1, i0 = 0;
     float used = 0.0f, vcap = 0.0f, now = 0.0f;
     int count = 0;
+    // PDP: the row's visited and to_deliver sets as two 128-bit words of the finishing wavefront (scalar registers); bit n of
+    // word 0 = node n, of word 1 = node 64 + n
+    unsigned long long pvis[2] = {0ull, 0ull}, ptd[2] = {0ull, 0ull};
     float gq[2] = {0.f, 0.f}, cv[2] = {0.f, 0.f}, cv2[2] = {0.f, 0.f}, p1f[2] = {0.f, 0.f}, mydem[2] = {0.f, 0.f};
     bool done = l.done != 0;
     if (wv == fw) {
         cur = a.cur[r];
         if (ENV == EAMRL_ENV_TSP) { first = a.first[r]; istep = a.istep[r]; }
+        else if (PD) {
+            pvis[0] = __ballot(in0 && a.visited[r * M + (in0 ? n0 : 0)] != 0);
+            pvis[1] = __ballot(in1 && a.visited[r * M + (in1 ? n1 : 0)] != 0);
+            ptd[0] = __ballot(in0 && a.to_deliver[r * M + (in0 ? n0 : 0)] != 0);
+            ptd[1] = __ballot(in1 && a.to_deliver[r * M + (in1 ? n1 : 0)] != 0);
+        }
         else { used = a.used[r]; vcap = a.vcap[r]; }
         if (PC || OP) { istep = a.istep[r]; i0 = istep; }
         if (TW) now = a.time[r];
@@ -213,7 +223,7 @@ __global__ __launch_bounds__(RB, 2) void k_rollout_resident(DecArgs a, int S, in
         for (int k = 0; k < 2; ++k) {
             const int e = lane + 64 * k;
             gq[k] = a.gctx ? a.gctx[bi * RE + e] : 0.0f;
-            cv[k] = a.cvec[e];
+            cv[k] = PD ? 0.0f : a.cvec[e];      // PDP: no state column; the query is the depot envs' fma with zeros (decode_step.hip D1)
             if (ENV == EAMRL_ENV_TSP && istep > 0) p1f[k] = a.Pa[(bi * M + first) * ld + e];
             const int nn = lane + 64 * k;
             if (CV && nn >= 1 && nn < M) mydem[k] = l.dem[nn - 1];
@@ -610,6 +620,22 @@ __global__ __launch_bounds__(RB, 2) void k_rollout_resident(DecArgs a, int S, in
                     if (nn >= 1 && nn < M) l.msk[nn] = !((l.vis[nn] != 0) | v0);
                 }
                 if (lane == 0) l.msk[0] = !((used < 1.0f) && (count < M - 1));
+            } else if (PD) {
+                // PDPEnv._step (pdp/env.py:66-106): visit the node, open its partner (sel + N/2) % (N + 1) -- the reference's modulo,
+                // which for a delivery lands on the depot or a pickup, already open --, mask = unvisited and to deliver
+                const int d = (sel + (M - 1) / 2) % M;
+                cur = sel;
+                if (sel < 64) pvis[0] |= 1ull << sel; else pvis[1] |= 1ull << (sel - 64);
+                if (d < 64) ptd[0] |= 1ull << d; else ptd[1] |= 1ull << (d - 64);
+                const unsigned long long full0 = M >= 64 ? ~0ull : (1ull << M) - 1ull;
+                const unsigned long long full1 = M >= 128 ? ~0ull : (M > 64 ? (1ull << (M - 64)) - 1ull : 0ull);
+                done = ((pvis[0] & full0) == full0) && ((pvis[1] & full1) == full1);
+                __builtin_amdgcn_wave_barrier();
+                if (lane == 0) l.done = done;
+#pragma unroll
+                for (int k = 0; k < 2; ++k) l.q[lane + 64 * k] = fma_(cv[k], vcap - used, Plds[cur * RE + lane + 64 * k]) + gq[k];
+                l.msk[n0] = in0 && !((pvis[0] >> lane) & 1ull) && ((ptd[0] >> lane) & 1ull);
+                l.msk[n1] = in1 && !((pvis[1] >> lane) & 1ull) && ((ptd[1] >> lane) & 1ull);
             } else if (SD) {
                 // SDVRPEnv._step + get_action_mask (sdvrp/env.py:58-92,137-146): deliver min(remaining demand, free capacity)
                 const float selrem = l.dem[sel];
@@ -718,11 +744,15 @@ __global__ __launch_bounds__(RB, 2) void k_rollout_resident(DecArgs a, int S, in
         if (CV || PC || OP) a.visited[r * M + tid] = l.vis[tid];
         if (SD) a.rem[r * M + tid] = l.dem[tid];
     }
+    if (PD && wv == fw) {
+        if (in0) { a.visited[r * M + n0] = (pvis[0] >> lane) & 1ull; a.to_deliver[r * M + n0] = (ptd[0] >> lane) & 1ull; }
+        if (in1) { a.visited[r * M + n1] = (pvis[1] >> lane) & 1ull; a.to_deliver[r * M + n1] = (ptd[1] >> lane) & 1ull; }
+    }
     if (wv == fw && lane == 0) {
         a.cur[r] = cur;
         a.done[r] = done ? 1 : 0;
         if (ENV == EAMRL_ENV_TSP) { a.first[r] = first; a.istep[r] = istep; }
-        else a.used[r] = used;
+        else if (!PD) a.used[r] = used;
         if (PC || OP) a.istep[r] = i0;    // launch_rollout_pad adds the batch's step count
         if (TW) a.time[r] = now;
         atomicMax(a.steps_out, t);
@@ -810,7 +840,8 @@ int launch_rollout_resident(int env, const DecArgs& a, hipStream_t st)
          : env == EAMRL_ENV_CVRP ? launch_env<EAMRL_ENV_CVRP>(a, st)
          : env == EAMRL_ENV_SDVRP ? launch_env<EAMRL_ENV_SDVRP>(a, st)
          : env == EAMRL_ENV_PCTSP ? launch_env<EAMRL_ENV_PCTSP>(a, st)
-         : env == EAMRL_ENV_OP ? launch_env<EAMRL_ENV_OP>(a, st) : launch_env<EAMRL_ENV_CVRPTW>(a, st);
+         : env == EAMRL_ENV_OP ? launch_env<EAMRL_ENV_OP>(a, st)
+         : env == EAMRL_ENV_PDP ? launch_env<EAMRL_ENV_PDP>(a, st) : launch_env<EAMRL_ENV_CVRPTW>(a, st);
 }
 
 }  // namespace eamrl

@@ -1,11 +1,11 @@
-"""TSP / CVRP (and CVRPTW, SDVRP, PCTSP, OP) environments behind the reference's RL4COEnvBase interface, stepping on
+"""TSP / CVRP (and CVRPTW, SDVRP, PCTSP, OP, PDP) environments behind the reference's RL4COEnvBase interface, stepping on
 MI355X kernels.
 
 Interface mirrored (same names, argument meaning, TensorDict keys / shapes / dtypes and error messages):
   rl4co/envs/common/base.py:19-346        RL4COEnvBase (reset / step / get_reward / get_action_mask / dataset ...)
   rl4co/envs/common/utils.py:21-102       Generator, get_sampler (uniform branch)
   rl4co/envs/routing/tsp/{env,generator}.py, rl4co/envs/routing/cvrp/{env,generator}.py,
-  rl4co/envs/routing/{cvrptw,sdvrp,pctsp,op}/{env,generator}.py
+  rl4co/envs/routing/{cvrptw,sdvrp,pctsp,op,pdp}/{env,generator}.py
 Instances are generated on the host with torch's global CPU generator exactly like the reference
 (SURVEY Appendix A10), so the same seed gives bit-identical instances; every state transition, mask,
 reward and validity check runs in libeamrl_hip.so and requires the TensorDict to live on the GPU.
@@ -252,6 +252,31 @@ class OPGenerator(Generator):
 
 
 # --------------------------------------------------------------------------------------------------------
+class PDPGenerator(Generator):
+    """locs [B, num_loc, 2], depot [B, 2]; pickups are the first half of locs, deliveries the second, pickup i pairs with
+    delivery i + num_loc / 2   (pdp/generator.py:15-90).  An odd num_loc is raised to the next even number with a warning,
+    as the reference does."""
+
+    def __init__(self, num_loc: int = 20, min_loc: float = 0.0, max_loc: float = 1.0, init_sol_type: str = "random",
+                 loc_distribution="uniform", depot_distribution=None, **kwargs):
+        self.num_loc, self.min_loc, self.max_loc, self.init_sol_type = num_loc, min_loc, max_loc, init_sol_type
+        if num_loc % 2 != 0:
+            log.warning("Number of locations must be even. Adding 1 to the number of locations.")
+            self.num_loc += 1
+        self.loc_sampler = kwargs.get("loc_sampler") or get_sampler("loc", loc_distribution, min_loc, max_loc, **kwargs)
+        self.depot_sampler = kwargs.get("depot_sampler") or (
+            get_sampler("depot", depot_distribution, min_loc, max_loc, **kwargs) if depot_distribution is not None else None)
+
+    def _generate(self, batch_size):
+        if self.depot_sampler is not None:
+            depot = self.depot_sampler.sample((*batch_size, 2))
+            locs = self.loc_sampler.sample((*batch_size, self.num_loc, 2))
+        else:  # one draw of num_loc + 1 points, the first is the depot
+            pts = self.loc_sampler.sample((*batch_size, self.num_loc + 1, 2))
+            depot, locs = pts[..., 0, :], pts[..., 1:, :]
+        return TensorDict({"locs": locs, "depot": depot}, batch_size=batch_size)
+
+
 class TensorDictDataset(torch.utils.data.Dataset):
     """List-of-dicts dataset with the reference's collate contract (rl4co/data/dataset.py:43-75)."""
 
@@ -358,7 +383,7 @@ class RL4COEnvBase:
 
     def get_num_starts(self, td):
         n = td["action_mask"].shape[-1]
-        return n - 1 if self.name in ("cvrp", "sdvrp", "pctsp", "spctsp", "op", "cvrptw") else n          # depot cannot be a start node (utils/ops.py:120-130)
+        return n - 1 if self.name in ("cvrp", "sdvrp", "pctsp", "spctsp", "op", "cvrptw") else n          # depot cannot be a start node (utils/ops.py:120-130; PDPEnv overrides both)
 
     def select_start_nodes(self, td, num_starts):
         """POMO start nodes: flat row j = s*B + b starts at node s (+1 with a depot) (utils/ops.py:133-169)."""
@@ -851,7 +876,81 @@ class OPEnv(RL4COEnvBase):
         assert bad[1] == 0, "Max length exceeded"
 
 
-ENV_REGISTRY = {"tsp": TSPEnv, "cvrp": CVRPEnv, "sdvrp": SDVRPEnv, "pctsp": PCTSPEnv, "spctsp": SPCTSPEnv, "op": OPEnv, "cvrptw": CVRPTWEnv}
+class PDPEnv(RL4COEnvBase):
+    """Pickup and Delivery Problem (rl4co/envs/routing/pdp/env.py:24-244): one vehicle, N/2 pickups each to be visited before
+    its delivery, tour closed through the depot.  State: `available` and `to_deliver` (bool [B, N + 1]); a node is feasible
+    iff it is available and to deliver.  force_start_at_depot: the depot is the forced first action (one step more)."""
+
+    name = "pdp"
+
+    def __init__(self, generator: PDPGenerator = None, generator_params: dict = {}, force_start_at_depot: bool = False,
+                 **kwargs):
+        super().__init__(**kwargs)
+        self.generator = generator if generator is not None else PDPGenerator(**generator_params)
+        self.force_start_at_depot = force_start_at_depot
+
+    def _reset(self, td=None, batch_size=None):
+        dev = td.device
+        n = td["locs"].shape[-2]
+        if n % 2:
+            raise ValueError(f"PDP needs an even number of locations (pickups + deliveries), got {n}")
+        to_deliver = torch.zeros(*batch_size, n + 1, dtype=torch.bool, device=dev)
+        to_deliver[..., :n // 2 + 1] = True
+        available = torch.ones(*batch_size, n + 1, dtype=torch.bool, device=dev)
+        if self.force_start_at_depot:
+            mask = torch.zeros_like(available)
+            mask[..., 0] = True                     # only the depot at the first step
+        else:
+            available[..., 0] = False               # the depot is added by the reward
+            mask = available & to_deliver
+        return TensorDict({
+            "locs": torch.cat((td["depot"][..., None, :], td["locs"]), -2),
+            "current_node": torch.zeros(*batch_size, 1, dtype=torch.int64, device=dev),
+            "to_deliver": to_deliver,
+            "available": available,
+            "i": torch.zeros(*batch_size, 1, dtype=torch.int64, device=dev),
+            "action_mask": mask,
+        }, batch_size=batch_size)
+
+    def _step(self, td):
+        mask = td["action_mask"]
+        if not mask.is_contiguous():
+            mask = mask.contiguous()
+        visited = ~td["available"]                  # the kernels keep the complement (eamrl_state.visited)
+        to_deliver = td["to_deliver"].contiguous()
+        done = _flat(td["done"], torch.bool)
+        cur = _flat(td["current_node"], torch.int64)
+        ops.pdp_step_mask_(visited, to_deliver, cur, td["action"].reshape(-1).contiguous(), mask, done)
+        td.update({"action_mask": mask, "available": ~visited, "to_deliver": to_deliver, "i": td["i"] + 1,
+                   "current_node": cur.reshape(-1, 1), "done": done, "reward": torch.zeros_like(done)})
+        return td
+
+    def get_action_mask(self, td):
+        mask = torch.empty(td["available"].shape, dtype=torch.bool, device=td["available"].device)
+        return ops.pdp_step_mask_(~td["available"], td["to_deliver"].contiguous(), None, None, mask)
+
+    def _get_reward(self, td, actions):
+        return ops.tour_length_reward(td["locs"].contiguous(), actions.contiguous(), with_depot=True)
+
+    def check_solution_validity(self, td, actions) -> None:
+        n = td["locs"].shape[-2] - 1
+        assert actions.shape[-1] == n + int(self.force_start_at_depot), "Not visiting all nodes"
+        bad = ops.check_solution("pdp", actions.contiguous(), num_loc=n).tolist()
+        assert bad[0] == 0, "Not visiting all nodes"
+        assert bad[1] == 0, "Deliverying without pick-up"
+
+    def get_num_starts(self, td):
+        """Only the pickups can be start nodes (pdp/env.py:228-230)."""
+        return (td["locs"].shape[-2] - 1) // 2
+
+    def select_start_nodes(self, td, num_starts):
+        """Flat row j = s*B + b starts at pickup s % (N/2) + 1 (pdp/env.py:232-240)."""
+        num_possible_starts = (td["locs"].shape[-2] - 1) // 2
+        return torch.arange(num_starts, device=td.device).repeat_interleave(td.shape[0]) % num_possible_starts + 1
+
+
+ENV_REGISTRY = {"tsp": TSPEnv, "cvrp": CVRPEnv, "sdvrp": SDVRPEnv, "pctsp": PCTSPEnv, "spctsp": SPCTSPEnv, "op": OPEnv, "cvrptw": CVRPTWEnv,
+                "pdp": PDPEnv}
 
 
 def get_env(env_name: str, *args, **kwargs) -> RL4COEnvBase:

@@ -10,11 +10,12 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (ENV_CVRP, ENV_CVRPTW, ENV_OP, ENV_PCTSP, ENV_SDVRP, ENV_TSP, EVALUATE, GREEDY, NORM_BATCH_EVAL, NORM_INSTANCE, SAMPLE,  # noqa: F401
+from ._lib import (ENV_CVRP, ENV_CVRPTW, ENV_OP, ENV_PCTSP, ENV_PDP, ENV_SDVRP, ENV_TSP, EVALUATE, GREEDY, NORM_BATCH_EVAL, NORM_INSTANCE, SAMPLE,  # noqa: F401
                    ST_INFEASIBLE, ST_NAN_LOGITS, ST_STEP_OVERRUN)
 
 MODES = {"greedy": GREEDY, "sampling": SAMPLE, "evaluate": EVALUATE}
-ENVS = {"tsp": ENV_TSP, "cvrp": ENV_CVRP, "sdvrp": ENV_SDVRP, "pctsp": ENV_PCTSP, "op": ENV_OP, "cvrptw": ENV_CVRPTW}
+ENVS = {"tsp": ENV_TSP, "cvrp": ENV_CVRP, "sdvrp": ENV_SDVRP, "pctsp": ENV_PCTSP, "op": ENV_OP, "cvrptw": ENV_CVRPTW,
+        "pdp": ENV_PDP}
 
 
 def _need_gpu(t: torch.Tensor, name: str):
@@ -818,6 +819,50 @@ def pctsp_step_mask_(visited, prize_tot, pen_tot, prize, penalty, cur, istep, ac
     return mask
 
 
+def pdp_step_mask_(visited, to_deliver, cur, action, mask, done=None):
+    """PDPEnv._step and its mask in place (pdp/env.py:66-106); action None: mask only.  visited = ~available."""
+    lib = _lib.load()
+    R, M = visited.shape
+    if M < 3 or M % 2 == 0:
+        raise ValueError("pdp_step: the number of nodes (depot included) must be odd")
+    for t, nm in ((visited, "visited"), (to_deliver, "to_deliver")):
+        if t.dtype not in (torch.bool, torch.uint8):
+            raise TypeError(f"{nm} must be bool or uint8")
+        _chk(_bytes(t), nm, torch.uint8, (R, M))
+    _chk(mask, "action_mask", torch.bool, (R, M))
+    if action is not None:
+        _chk(cur, "current_node", torch.int64, (R,))
+        _chk(action, "action", torch.int64, (R,))
+        _chk(done, "done", torch.bool, (R,))
+    _lib.check(lib.eamrl_pdp_step_mask(_ptr(_bytes(visited)), _ptr(_bytes(to_deliver)), _ptr(cur), _ptr(action),
+                                       _ptr(_bytes(mask)), _ptr(_bytes(done)) if done is not None else None, R, M,
+                                       _stream(mask)), "eamrl_pdp_step_mask")
+    return mask
+
+
+def pdp_init_embedding(locs, Wd, bd, Wp, bp, Wl, bl, out=None):
+    """PDPInitEmbedding.forward in one launch (init.py:347-372): [B, M, E] from locs [B, M, 2]; equals the three `linear`
+    calls on the depot, pickup (x_p, y_p, x_d, y_d) and delivery features bit for bit."""
+    lib = _lib.load()
+    _chk(locs, "locs", torch.float32)
+    B, M, two = locs.shape
+    E = Wd.shape[0]
+    if two != 2 or M < 3 or M % 2 == 0:
+        raise ValueError("pdp_init_embedding: locs must be [B, N + 1, 2] with N even")
+    _chk(Wd, "init_embed_depot.weight", torch.float32, (E, 2))
+    _chk(Wp, "init_embed_pick.weight", torch.float32, (E, 4))
+    _chk(Wl, "init_embed_delivery.weight", torch.float32, (E, 2))
+    for b, nm in ((bd, "init_embed_depot.bias"), (bp, "init_embed_pick.bias"), (bl, "init_embed_delivery.bias")):
+        if b is not None:
+            _chk(b, nm, torch.float32, (E,))
+    if out is None:
+        out = torch.empty(B, M, E, device=locs.device, dtype=torch.float32)
+    _chk(out, "out", torch.float32, (B, M, E))
+    _lib.check(lib.eamrl_pdp_init_embedding(_ptr(locs), _ptr(Wd), _ptr(bd), _ptr(Wp), _ptr(bp), _ptr(Wl), _ptr(bl), _ptr(out),
+                                            B, M, E, _stream(locs)), "eamrl_pdp_init_embedding")
+    return out
+
+
 def cvrptw_step_mask_(visited, used, vcap, demand, cur, time, locs, tw, dur, action, mask, done=None):
     """CVRPTWEnv._step + get_action_mask in place (cvrptw/env.py:103-138); action None: mask only.
     tw [B, M, 2] and dur [B, M] as float32."""
@@ -1022,6 +1067,10 @@ def check_solution(env_name, actions, demand=None, vcap=None, num_loc=None):
     if env_name == "tsp":
         N, B = (T if num_loc is None else num_loc), R
         _lib.check(lib.eamrl_check_solution(ENV_TSP, _ptr(actions), None, None, R, B, N, T, _ptr(bad), _stream(actions)),
+                   "eamrl_check_solution")
+    elif env_name == "pdp":         # (not a permutation of 1..N, delivery before pickup); num_loc = N, T = N or N + 1
+        N = (T if num_loc is None else int(num_loc))
+        _lib.check(lib.eamrl_check_solution(ENV_PDP, _ptr(actions), None, None, R, R, N, T, _ptr(bad), _stream(actions)),
                    "eamrl_check_solution")
     elif env_name == "pctsp":       # demand = real_prize [B, N+1]
         _chk(demand, "real_prize", torch.float32)
@@ -1271,7 +1320,7 @@ class RolloutState:
         self.istep = torch.zeros(R, **i64)
         self.done = torch.zeros(R, dtype=torch.bool, device=device)
         self.mask = torch.ones(R, M, dtype=torch.bool, device=device)
-        self.used = self.vcap = self.visited = self.rem = None
+        self.used = self.vcap = self.visited = self.rem = self.to_deliver = None
         self.demand = demand
         self.locs = None                                                       # op, cvrptw: node coordinates [B, M, 2]
         self.time = self.tw = self.dur = None                                  # cvrptw: clock [R], windows, service times
@@ -1280,16 +1329,21 @@ class RolloutState:
         if env_name in ("cvrp", "sdvrp", "pctsp", "op", "cvrptw"):
             self.used = torch.zeros(R, dtype=torch.float32, device=device)     # pctsp: cur_total_prize; op: tour_length
             self.vcap = torch.ones(R, dtype=torch.float32, device=device)      # pctsp: prize_required; op: max_length[:, 0]
-        if env_name in ("cvrp", "pctsp", "op", "cvrptw"):
+        if env_name in ("cvrp", "pctsp", "op", "cvrptw", "pdp"):
             self.visited = torch.zeros(R, M, dtype=torch.uint8, device=device)
+        if env_name == "pdp":       # the reset state of PDPEnv: depot visited, depot and pickups to deliver, mask = their AND
+            self.visited[:, 0] = 1
+            self.to_deliver = torch.zeros(R, M, dtype=torch.uint8, device=device)
+            self.to_deliver[:, :(M - 1) // 2 + 1] = 1
+            self.mask = (self.visited == 0) & (self.to_deliver != 0)
         if env_name == "sdvrp":
             self.rem = torch.zeros(R, M, dtype=torch.float32, device=device)   # demand_with_depot
 
     def reorder_(self, idx):
         """Rows taken from rows `idx` (beam search: every beam continues the state of its parent beam).  vcap is
         per instance and the row order keeps r % B, so it needs no reordering, nor does demand."""
-        for name in ("first", "cur", "istep", "done", "mask", "used", "visited", "rem", "time"):
-            v = getattr(self, name)
+        for name in ("first", "cur", "istep", "done", "mask", "used", "visited", "rem", "time", "to_deliver"):
+            v = getattr(self, name, None)
             if v is not None:
                 setattr(self, name, v.index_select(0, idx).contiguous())
 
@@ -1303,6 +1357,8 @@ class RolloutState:
         s.locs = _ptr(getattr(self, "locs", None))
         s.time, s.tw, s.dur = (_ptr(getattr(self, k, None)) for k in ("time", "tw", "dur"))
         s.heads_out = _ptr(getattr(self, "heads_out", None))       # [R, t_max, E] or None (eamrl_state.heads_out)
+        td = getattr(self, "to_deliver", None)
+        s.to_deliver = _ptr(None if td is None else _bytes(td))
         return s
 
 
@@ -1316,6 +1372,11 @@ def _validate_state(st: RolloutState, cache: DecodeCache):
     if st.env_name == "tsp":
         _chk(st.first, "first_node", torch.int64, (R,))
         _chk(st.istep, "i", torch.int64, (R,))
+    elif st.env_name == "pdp":
+        if M < 3 or M % 2 == 0:
+            raise ValueError("decode: PDP needs an odd number of nodes (depot + pickups + deliveries)")
+        _chk(_bytes(st.visited), "visited", torch.uint8, (R, M))
+        _chk(_bytes(st.to_deliver), "to_deliver", torch.uint8, (R, M))
     else:
         _chk(st.used, "used_capacity", torch.float32, (R,))
         _chk(st.vcap, "vehicle_capacity", torch.float32, (R,))
@@ -1496,7 +1557,8 @@ def rollout(st: RolloutState, cache: DecodeCache, mode="greedy", noise=None, giv
     _validate_state(st, cache)
     R, M, dev = st.R, st.M, st.mask.device
     if t_max is None:
-        t_max = {"tsp": M, "cvrp": 2 * M + 1, "sdvrp": 3 * M + 1, "pctsp": M + 1, "op": M + 1, "cvrptw": 2 * M + 1}[st.env_name]
+        t_max = {"tsp": M, "cvrp": 2 * M + 1, "sdvrp": 3 * M + 1, "pctsp": M + 1, "op": M + 1, "cvrptw": 2 * M + 1,
+                 "pdp": M}[st.env_name]
     if mode == "sampling" and noise is None:
         if seed is None:
             raise ValueError("rollout: sampling needs `noise` or `seed`")

@@ -164,6 +164,25 @@ class OPInitEmbedding(nn.Module):
         return _depot_fused_spec(self, locs, torch.cat((locs[:, 1:, :], td["prize"][..., 1:, None]), -1))
 
 
+class PDPInitEmbedding(nn.Module):
+    """Depot, pickups (with their delivery's coordinates) and deliveries embedded by three Linears
+    (nn/env_embeddings/init.py:347-372); one launch (eamrl_pdp_init_embedding), bit-identical to the three `ops.linear` calls.
+    The result feeds the fused encoder through its h_in entry (no `fused_spec`: the in-kernel init embedding is one Linear
+    plus a depot row)."""
+
+    def __init__(self, embed_dim, linear_bias=True):
+        super().__init__()
+        self.init_embed_depot = nn.Linear(2, embed_dim, linear_bias)
+        self.init_embed_pick = nn.Linear(4, embed_dim, linear_bias)
+        self.init_embed_delivery = nn.Linear(2, embed_dim, linear_bias)
+
+    def forward(self, td):
+        d, p, l = self.init_embed_depot, self.init_embed_pick, self.init_embed_delivery
+        det = lambda t: None if t is None else t.detach().contiguous()
+        return ops.pdp_init_embedding(td["locs"].contiguous(), det(d.weight), det(d.bias), det(p.weight), det(p.bias),
+                                      det(l.weight), det(l.bias))
+
+
 class _Holder(nn.Module):
     """`.module` wrapper so that parameter names match the reference's SkipConnection(...)."""
 
@@ -349,7 +368,7 @@ class AttentionModelEncoder(nn.Module):
         if init_embedding is None:
             init_embedding = {"tsp": TSPInitEmbedding, "cvrp": VRPInitEmbedding, "sdvrp": VRPInitEmbedding,
                               "pctsp": PCTSPInitEmbedding, "op": OPInitEmbedding,
-                              "cvrptw": VRPTWInitEmbedding}[env_name](embed_dim)
+                              "cvrptw": VRPTWInitEmbedding, "pdp": PDPInitEmbedding}[env_name](embed_dim)
         self.init_embedding = init_embedding
         self.net = GraphAttentionNetwork(num_heads, embed_dim, num_layers, normalization, feedforward_hidden) \
             if net is None else net
@@ -426,7 +445,8 @@ class AttentionModelDecoder(nn.Module):
                                       "outside the MI355X rollout path (the routing AttentionModel family only)")
         assert embed_dim % num_heads == 0
         self.env_name, self.embed_dim, self.num_heads = env_name, embed_dim, num_heads
-        ctx_dim = {"tsp": 2 * embed_dim, "cvrptw": embed_dim + 2}.get(env_name, embed_dim + 1)   # node(s) + state columns
+        # node(s) + state columns; PDPContext (context.py:242-253) is the current node alone: a square project_context
+        ctx_dim = {"tsp": 2 * embed_dim, "cvrptw": embed_dim + 2, "pdp": embed_dim}.get(env_name, embed_dim + 1)
         self.context_embedding = _ContextParams(embed_dim, ctx_dim, placeholder=(env_name == "tsp"))
         self.dynamic_embedding = SDVRPDynamicEmbedding(embed_dim) if env_name == "sdvrp" else StaticEmbedding()
         self.is_dynamic_embedding = env_name == "sdvrp"
@@ -516,7 +536,8 @@ class AttentionModelDecoder(nn.Module):
             w = self.dynamic_embedding.projection.weight.detach().reshape(3, E)
             lw = ops.matmul_right(w[2:3].contiguous(), self.pointer.project_out.weight.contiguous())
             dyn = torch.cat((w[0:2], lw), 0).contiguous()
-        return ops.DecodeCache(self.env_name, buf, cvec.contiguous(), gctx, emb, self.num_heads, dyn=dyn, embed_dim=E)
+        return ops.DecodeCache(self.env_name, buf, None if cvec is None else cvec.contiguous(), gctx, emb, self.num_heads,
+                               dyn=dyn, embed_dim=E)
 
     def _weight_constants(self):
         """Tensors that depend on the weights only, recomputed when a parameter changes (optimizer step, load):
@@ -536,11 +557,12 @@ class AttentionModelDecoder(nn.Module):
             else:
                 Wb = None
                 # state columns: capacity (CVRP-like), prize / length left (PCTSP / OP); CVRPTW: capacity | time -> [2E]
-                cvec = Wctx[:, E:].t().reshape(-1).contiguous() if self.env_name == "cvrptw" else Wctx[:, E].contiguous()
+                cvec = (None if self.env_name == "pdp" else          # PDP: no state column (eamrl_cache.cvec = NULL)
+                        Wctx[:, E:].t().reshape(-1).contiguous() if self.env_name == "cvrptw" else Wctx[:, E].contiguous())
             # slot-major cache: K | V | L | Pa (| Pb) are adjacent slots, so one GEMM with the stacked weights writes them all
             # (each output element is the same k-ordered chain as with separate launches)
             w_cache = torch.cat([Wkvl.detach(), Wa.detach()] + ([Wb.detach()] if Wb is not None else []), 0).contiguous()
-            new = (Wa.detach(), None if Wb is None else Wb.detach(), cvec.detach())
+            new = (Wa.detach(), None if Wb is None else Wb.detach(), None if cvec is None else cvec.detach())
             old = getattr(self, "_wc", None)
             if old is not None and all((a is None) == (b is None) and (a is None or (a.shape == b.shape and a.device == b.device))
                                        for a, b in zip(old, new)) and self._w_cache.shape == w_cache.shape:
@@ -579,6 +601,8 @@ def _env_step_(st: ops.RolloutState, action):
                               st.mask, st.done)
     elif st.env_name == "op":
         ops.op_step_mask_(st.visited, st.used, None, None, st.locs, st.demand, st.cur, st.istep, action, st.mask, st.done)
+    elif st.env_name == "pdp":
+        ops.pdp_step_mask_(st.visited, st.to_deliver, st.cur, action, st.mask, st.done)
     else:
         ops.sdvrp_step_mask_(st.rem, st.used, st.vcap, st.cur, action, st.mask, st.done)
 
@@ -586,7 +610,8 @@ def _env_step_(st: ops.RolloutState, action):
 def _max_decode_steps(env_name, M, npre=0):
     """TSP: one step per remaining node; CVRP: every customer visit is followed by at most one depot visit; SDVRP: as
     CVRP plus at most one split delivery per trip."""
-    return {"tsp": M - npre, "cvrp": 2 * M + 1, "sdvrp": 3 * M + 1, "pctsp": M + 1, "op": M + 1, "cvrptw": 2 * M + 1}[env_name]
+    return {"tsp": M - npre, "cvrp": 2 * M + 1, "sdvrp": 3 * M + 1, "pctsp": M + 1, "op": M + 1, "cvrptw": 2 * M + 1,
+            "pdp": M - npre}[env_name]        # PDP: N steps, N + 1 with force_start_at_depot (`_enqueue` takes the exact count)
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -630,8 +655,11 @@ def state_from_td(env_name, td, num_starts: int = 0, copy: bool = True) -> ops.R
     done = td["done"] if "done" in td.keys() else torch.zeros(B, dtype=torch.bool, device=dev)
     st.done = rep(done, torch.bool)
     st.first = st.istep = st.used = st.vcap = st.visited = st.demand = st.rem = st.locs = None
-    st.time = st.tw = st.dur = None
-    if env_name == "tsp":
+    st.time = st.tw = st.dur = st.to_deliver = None
+    if env_name == "pdp":           # visited = ~available; no scalar state
+        st.visited = rep(~td["available"], torch.uint8)
+        st.to_deliver = rep(td["to_deliver"], torch.uint8)
+    elif env_name == "tsp":
         st.first = rep(td["first_node"], torch.int64)
         st.istep = rep(td["i"], torch.int64)
     elif env_name == "op":          # used = tour length, vcap = the instance's max_length[:, 0], demand = arrival limits
@@ -669,7 +697,9 @@ def state_to_td(env_name, st: ops.RolloutState, td, locs_rows=None):
     """TensorDict of the final state in the reference's post-step shapes."""
     R = st.R
     out = {"action_mask": st.mask, "done": st.done, "reward": torch.zeros_like(st.done)}
-    if env_name == "tsp":
+    if env_name == "pdp":           # "i" is advanced by `_finish`, which knows the number of steps
+        out.update({"current_node": st.cur.reshape(R, 1), "available": st.visited == 0, "to_deliver": st.to_deliver != 0})
+    elif env_name == "tsp":
         out.update({"first_node": st.first, "current_node": st.cur, "i": st.istep.reshape(R, 1)})
     elif env_name == "op":
         # current_total_prize is bookkeeping of env.step only (the reward is recomputed from the actions)
@@ -717,8 +747,8 @@ class AttentionModelPolicy(nn.Module):
             env_name = env_name.name
         self.env_alias = env_name            # the name the env must carry (e.g. "spctsp")
         env_name = _kind(env_name)           # the kernel / embedding family (e.g. "pctsp")
-        if env_name not in ("tsp", "cvrp", "cvrptw", "sdvrp", "pctsp", "op"):
-            raise NotImplementedError(f"env_name={env_name!r}: the MI355X rollout path covers 'tsp', 'cvrp', 'cvrptw', "
+        if env_name not in ("tsp", "cvrp", "cvrptw", "sdvrp", "pctsp", "op", "pdp"):
+            raise NotImplementedError(f"env_name={env_name!r}: the MI355X rollout path covers 'tsp', 'cvrp', 'cvrptw', 'pdp', "
                                       "'sdvrp', 'pctsp', 'spctsp' and 'op'")
         if moe_kwargs not in (None, {"encoder": None, "decoder": None}) or any(
                 x is not None for x in (sdpa_fn, sdpa_fn_encoder, sdpa_fn_decoder, encoder_network)):
@@ -968,6 +998,8 @@ class AttentionModelPolicy(nn.Module):
         # main decoding loop: one launch
         M = st.M
         t_max = _max_decode_steps(self.env_name, M, len(pre_actions))
+        if self.env_name == "pdp" and not getattr(env, "force_start_at_depot", False):
+            t_max -= 1              # every row takes exactly N steps: the arrays below carry no padding column
         t_max = int(max(1, min(t_max, max_steps)))
         given = None
         if actions is not None:
@@ -1013,7 +1045,7 @@ class AttentionModelPolicy(nn.Module):
         # x + 0 is exact in the lane tree), nor the log-likelihood sum, nor validity.
         actions_pad = torch.cat(pre_actions + [acts], 1) if pre_actions else acts
         logp_pad = torch.cat(pre_logps + [lps], 1) if pre_logps else lps
-        native_env = type(env).__name__ in ("TSPEnv", "CVRPEnv", "SDVRPEnv", "PCTSPEnv", "SPCTSPEnv", "OPEnv", "CVRPTWEnv") and type(env).__module__ == RL4COEnvBase.__module__
+        native_env = type(env).__name__ in ("TSPEnv", "CVRPEnv", "SDVRPEnv", "PCTSPEnv", "SPCTSPEnv", "OPEnv", "CVRPTWEnv", "PDPEnv") and type(env).__module__ == RL4COEnvBase.__module__
         fast = info is not None and native_env and not select_best
         reward_pad = ll_pad = bad = None
         one_launch = fast and self.env_name in ("tsp", "cvrp") and calc_reward
@@ -1035,6 +1067,7 @@ class AttentionModelPolicy(nn.Module):
                     reward_pad = ops.tour_length_reward(locs, actions_pad, with_depot=(self.env_name != "tsp"))
                 if env.check_solution and self.env_name not in ("sdvrp", "cvrptw"):   # those: checked in _finish
                     bad = (ops.check_solution("tsp", actions_pad) if self.env_name == "tsp" else
+                           ops.check_solution("pdp", actions_pad, num_loc=M - 1) if self.env_name == "pdp" else
                            ops.check_solution("pctsp", actions_pad, td["real_prize"].contiguous())
                            if self.env_name == "pctsp" else
                            ops.op_check_solution(actions_pad, locs, td["max_length"].contiguous())
@@ -1072,6 +1105,8 @@ class AttentionModelPolicy(nn.Module):
         actions_out = p["actions_pad"][:, :npre + T]
         logprobs = p["logp_pad"][:, :npre + T]
         td_out = state_to_td(self.env_name, st, td)
+        if self.env_name == "pdp" and "i" in td_out.keys():
+            td_out.set("i", td_out["i"] + (npre + T))
 
         if S > 0 and p["select_best"]:   # DecodingStrategy._select_best (decoding.py:419-427)
             rewards = env.get_reward(td_out, actions_out)
@@ -1094,6 +1129,9 @@ class AttentionModelPolicy(nn.Module):
                     elif self.env_name == "op":
                         assert bad_counts[0] == 0, "Duplicates"
                         assert bad_counts[1] == 0, "Max length exceeded"
+                    elif self.env_name == "pdp":
+                        assert bad_counts[0] == 0, "Not visiting all nodes"
+                        assert bad_counts[1] == 0, "Deliverying without pick-up"
                     else:
                         assert bad_counts[0] == 0, "Invalid tour"
                         assert bad_counts[1] == 0, "Used more than capacity"

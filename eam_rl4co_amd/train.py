@@ -215,6 +215,12 @@ def init_embedding_autograd(policy, td):
     native_init = locs.is_cuda and os.environ.get("EAMRL_TORCH_INIT_EMBED", "0") != "1"
     if policy.env_name == "tsp":
         h = _small_linear(locs, ie.init_embed.weight, ie.init_embed.bias)
+    elif policy.env_name == "pdp":      # depot | pickups with their deliveries' coordinates | deliveries (init.py:347-372)
+        half = (locs.shape[1] - 1) // 2
+        pick, deliv = locs[:, 1:half + 1], locs[:, half + 1:]
+        h = torch.cat((_small_linear(locs[:, :1], ie.init_embed_depot.weight, ie.init_embed_depot.bias),
+                       _small_linear(torch.cat((pick, deliv), -1), ie.init_embed_pick.weight, ie.init_embed_pick.bias),
+                       _small_linear(deliv, ie.init_embed_delivery.weight, ie.init_embed_delivery.bias)), 1)
     else:
         depot = _small_linear(locs[:, :1], ie.init_embed_depot.weight, ie.init_embed_depot.bias)
         if policy.env_name == "pctsp":
@@ -320,6 +326,29 @@ def _pctsp_states(actions, prize_rows, prize_required):
     return torch.stack(curs, 1), torch.stack(rems, 1), torch.stack(masks, 1)
 
 
+def _pdp_states(actions, available, to_deliver, mask0):
+    """-> cur [R,T], mask [R,T,M] before each step (pdp/env.py:66-106), replayed from the rows' reset state: available and
+    to_deliver [R,M] bool, mask0 the reset mask (with force_start_at_depot it is not their AND).  The partner index keeps the
+    reference's modulo: (a + N/2) % (N + 1)."""
+    R, T = actions.shape
+    M = available.shape[1]
+    dev = actions.device
+    cur = torch.zeros(R, dtype=torch.int64, device=dev)
+    ar = torch.arange(R, device=dev)
+    curs, masks = [], []
+    mask = mask0
+    for t in range(T):
+        masks.append(mask)
+        curs.append(cur)
+        a = actions[:, t]
+        available, to_deliver = available.clone(), to_deliver.clone()
+        available[ar, a] = False
+        to_deliver[ar, (a + (M - 1) // 2) % M] = True
+        mask = available & to_deliver
+        cur = a
+    return torch.stack(curs, 1), torch.stack(masks, 1)
+
+
 def _cvrptw_states(actions, demand_rows, vcap, locs_rows, tw_rows, dur_rows):
     """-> cur [R,T], free capacity [R,T], clock [R,T], mask [R,T,M] before each step (cvrptw/env.py:103-138).
     tw_rows [R,M,2] and dur_rows [R,M] as float32."""
@@ -410,7 +439,8 @@ def _sdvrp_states(actions, demand_rows, vcap, M):
 # ------------------------------------------------------------------------------------------------------------
 _STATE_KEYS = {"cvrp": ("demand", "vehicle_capacity"), "sdvrp": ("demand", "vehicle_capacity"),
                "cvrptw": ("demand", "vehicle_capacity", "locs", "time_windows", "durations"),
-               "op": ("locs", "max_length"), "pctsp": ("real_prize", "prize_required"), "tsp": ()}
+               "op": ("locs", "max_length"), "pctsp": ("real_prize", "prize_required"), "tsp": (),
+               "pdp": ("available", "to_deliver", "action_mask")}
 
 
 class shared_decoder_tensors:
@@ -544,6 +574,9 @@ def _logp_rows(env_name, t, static, act, nrep, multistart, H, temperature, clip,
         if env_name == "tsp":
             first, cur, mask = _tsp_states(act, M, multistart)
             rem = now = None
+        elif env_name == "pdp":
+            cur, mask = _pdp_states(act, rep(static["available"]), rep(static["to_deliver"]), rep(static["action_mask"]))
+            rem = now = None
         elif env_name == "cvrptw":
             cur, rem, now, mask = _cvrptw_states(act, rep(static["demand"]), rep(static["vehicle_capacity"].reshape(-1)),
                                                  rep(static["locs"]), rep(static["time_windows"].float()),
@@ -560,6 +593,8 @@ def _logp_rows(env_name, t, static, act, nrep, multistart, H, temperature, clip,
         ctx_in = torch.cat((embr[ar, first], embr[ar, cur]), -1)                       # [Rc, T, 2E]
         if not multistart:   # step 0 uses the learned placeholder (context.py:118-131)
             ctx_in = torch.cat((t["placeholder"].expand(Rc, 1, 2 * E), ctx_in[:, 1:]), 1)
+    elif env_name == "pdp":
+        ctx_in = embr[ar, cur]                                                           # [Rc, T, E]  (context.py:242-253)
     elif env_name == "cvrptw":
         ctx_in = torch.cat((embr[ar, cur], rem[..., None], now[..., None]), -1)          # [Rc, T, E+2]
     else:
@@ -631,7 +666,7 @@ class _ChunkedReeval(torch.autograd.Function):
 # ------------------------------------------------------------------------------------------------------------
 # native (HIP) re-evaluation: forward and backward of all decode steps on fp32 MFMA (csrc/reeval.hip)
 # ------------------------------------------------------------------------------------------------------------
-_NATIVE_ENVS = ("tsp", "cvrp", "pctsp", "op", "cvrptw", "sdvrp")
+_NATIVE_ENVS = ("tsp", "cvrp", "pctsp", "op", "cvrptw", "sdvrp")      # PDP: the PyTorch re-evaluation path (`_pdp_states`)
 
 
 def native_reeval_supported(policy, M: int) -> bool:

@@ -38,6 +38,7 @@ extern "C" {
 #define EAMRL_ENV_PCTSP 3 /* prize collecting TSP: return to the depot once the collected prize reaches 1 */
 #define EAMRL_ENV_OP 4    /* orienteering: collect prizes within a maximum tour length */
 #define EAMRL_ENV_CVRPTW 5 /* CVRP with time windows: a customer must be reached before its window closes */
+#define EAMRL_ENV_PDP 6    /* pickup and delivery: N/2 pickups, each to be visited before its delivery; M = N + 1 nodes */
 /* selection modes  [rl4co/utils/decoding.py:430-465] */
 #define EAMRL_GREEDY 0
 #define EAMRL_SAMPLE 1   /* argmax(p / noise), noise ~ Exp(1) supplied by the caller (== torch.multinomial) */
@@ -123,6 +124,25 @@ int eamrl_op_step_mask(uint8_t* visited, float* tour_len, float* prize_tot, cons
 int eamrl_cvrptw_step_mask(uint8_t* visited, float* used, const float* vcap, const float* demand, int64_t* cur, float* time,
                            const float* locs, const float* tw, const float* dur, const int64_t* action, uint8_t* mask,
                            uint8_t* done, int64_t R, int64_t B, int N, void* stream);
+
+/* PDPEnv._step and the mask it stores  [rl4co/envs/routing/pdp/env.py:66-106].  In place.  M = N + 1 nodes: depot 0, pickups
+ * 1 .. N/2, deliveries N/2 + 1 .. N (N even); pickup i pairs with delivery i + N/2.  visited [R][M] u8 = !available, to_deliver
+ * [R][M] u8, cur [R] i64, action [R] i64, mask [R][M] u8 (1 = feasible), done [R] u8.  The step marks the action visited, sets
+ * to_deliver[(action + N/2) % (N + 1)] -- the reference's modulo, kept as it is: for a delivery (or the depot) it lands on the
+ * depot or a pickup, whose bit is set already --, then mask = !visited & to_deliver and done = every node visited.
+ * action == NULL: only the mask is recomputed (cur and done may be NULL).  The reset state  [pdp/env.py:108-156]: visited = the
+ * depot alone, to_deliver = depot and pickups; force_start_at_depot: nothing visited and a mask that allows the depot only. */
+int eamrl_pdp_step_mask(uint8_t* visited, uint8_t* to_deliver, int64_t* cur, const int64_t* action, uint8_t* mask,
+                        uint8_t* done, int64_t R, int M, void* stream);
+
+/* PDPInitEmbedding.forward  [rl4co/models/nn/env_embeddings/init.py:347-372] in one launch: h [B][M][E] from locs [B][M][2]
+ * (depot first).  Row 0 = Linear(2 -> E) of the depot (Wd [E][2], bd), row i of the pickups = Linear(4 -> E) of the pickup's
+ * and its delivery's coordinates (x_p, y_p, x_d, y_d) (Wp [E][4], bp), row of a delivery = Linear(2 -> E) of its own
+ * coordinates (Wl [E][2], bl); biases may be NULL.  Every output is the k-ordered fma chain of eamrl_linear, so h equals the
+ * three eamrl_linear calls bit for bit.  h is what eamrl_encoder_fused / eamrl_encoder_fused16 / the unfused encoder calls take
+ * as h_in.  M odd (N even), M >= 3. */
+int eamrl_pdp_init_embedding(const float* locs, const float* Wd, const float* bd, const float* Wp, const float* bp,
+                             const float* Wl, const float* bl, float* h, int64_t B, int M, int E, void* stream);
 
 /* The time-window replay of CVRPTWEnv.check_solution_validity  [cvrptw/env.py:203-227] (arrival times truncated to
  * integers as there): bad[0] += rows that start a service after its window closed.  The CVRP part of the check is
@@ -418,7 +438,7 @@ typedef struct eamrl_cache {
     const float* Pa;   /* TSP: first-node half; CVRP: current-node part */
     const float* Pb;   /* TSP: current-node half; CVRP: NULL */
     const float* cvec; /* [E]  TSP: project_context(W_placeholder); CVRP: capacity column of project_context;
-                        * CVRPTW: [2][E] capacity and current-time columns */
+                        * CVRPTW: [2][E] capacity and current-time columns; PDP: NULL (project_context is square) */
     const float* gctx; /* [B][E] graph context or NULL (POMO: use_graph_context=False) */
     int64_t ld;        /* row stride of K/V/Lp/Pa/Pb in floats (>= E) */
     int64_t B;         /* instances */
@@ -450,6 +470,7 @@ typedef struct eamrl_state {
                         * logit projection, nn/attention.py:282-301) of every decode step -- the training graph's backward
                         * (eamrl_reeval.heads) then does not recompute it.  Written only where eamrl_rollout_rng_native() is 1
                         * (the start-sharing kernel); rows that are done, and steps after an instance's last, get zeros. */
+    uint8_t* to_deliver; /* [R][M] PDP to_deliver (1 = the node's turn has come), else NULL; `visited` holds !available */
 } eamrl_state;
 
 /* One decode step for R rows = AttentionModelDecoder.forward + DecodingStrategy.step
@@ -461,6 +482,9 @@ typedef struct eamrl_state {
  * double 1 - top_p rounded once to float32 [utils/decoding.py:110-136,170-176]; 0 = off.  Reads the state, does not modify it unless fuse_env_step != 0, in which
  * case it also applies TSPEnv._step / CVRPEnv._step / SDVRPEnv._step (+mask) with the selected action.
  * EAMRL_ENV_SDVRP: cache->dyn and state->rem are required (dynamic embedding of the remaining demand, see eamrl_cache).
+ * EAMRL_ENV_PDP  [nn/env_embeddings/context.py:242-253; envs/routing/pdp/env.py:66-106]: the query is Pa[cur] (+ gctx), there is
+ * no state column (cache->cvec, state->used / vcap / demand are not read); the fused step needs state->visited and
+ * state->to_deliver.  With force_start_at_depot the caller's reset mask allows the depot only and the same rule applies.
  * noise [R][M] (SAMPLE) / given [R] (EVALUATE) else NULL.  Outputs: action [R], logp [R];
  * optional logprobs_all [R][M] (store_all_logp) and logits_raw [R][M] (pre-clip decoder logits). */
 int eamrl_am_decode_step(int env, const eamrl_cache* cache_host, const eamrl_state* state_host, int64_t R,
@@ -474,7 +498,8 @@ int eamrl_am_decode_step(int env, const eamrl_cache* cache_host, const eamrl_sta
  * given [R][t_given].  steps_out (device int32): number of steps executed = max over rows.  top_k / top_p as in
  * eamrl_am_decode_step, bit for bit: a filtered call runs on the register-resident kernel's filtering variant for graphs
  * up to 112 nodes (E = 128, H = 8; multistart batches included -- the start-sharing kernel does not filter) and on the
- * streaming kernel otherwise. */
+ * streaming kernel otherwise.  EAMRL_ENV_PDP is not built into the start-sharing MFMA kernel: its multistart batches run on
+ * the register-resident kernel (which loops an instance's starts over the operands it keeps in registers) or stream. */
 int eamrl_am_rollout(int env, const eamrl_cache* cache_host, const eamrl_state* state_host, int64_t R, int mode,
                      const float* noise, const int64_t* given, int t_given, float tanh_clip, float temperature,
                      int top_k, double top_p, int t_max, int64_t* actions, float* logps, int32_t* steps_out,
@@ -532,7 +557,9 @@ int eamrl_sum_logp(const float* logp, int64_t ld, float* out, int64_t R, int T, 
 /* The epilogue of a TSP / CVRP rollout in one launch: reward[r] = get_reward [tsp/env.py:90-100, cvrp/env.py:146-155]
  * (as eamrl_tour_length), ll[r] = sum_t logp[r][t] (as eamrl_sum_logp), bad += check_solution_validity (as
  * eamrl_check_solution) -- each in the order of the single-purpose entry point, so the results are bit-identical.
- * locs [B][M][2] (CVRP: depot first, M = N + 1); demand [B][M-1], vcap [R] for CVRP; reward / ll / bad may be NULL. */
+ * locs [B][M][2] (CVRP: depot first, M = N + 1); demand [B][M-1], vcap [R] for CVRP; reward / ll / bad may be NULL.
+ * EAMRL_ENV_PDP [pdp/env.py:194-226]: the depot-closed length as for CVRP, demand / vcap unused, the verdict that of
+ * eamrl_check_solution(EAMRL_ENV_PDP) (a second launch when bad != NULL). */
 int eamrl_rollout_finish(int env, const float* locs, const int64_t* actions, const float* logp, int64_t ld,
                          const float* demand, const float* vcap, float* reward, float* ll, int32_t* bad, int64_t R,
                          int64_t B, int M, int T, void* stream);
@@ -552,6 +579,10 @@ int eamrl_multi_copy(int n, const void* const* src, void* const* dst, const int6
  * vector starts with the depot slot -capacity, which the first depot visit turns into 0: a row that never visits the
  * depot has demand left.  SDVRP replays every row to its end, so one row may be counted in both counters; the other envs
  * count a row once, for the first assertion of the reference that it fails.
+ * EAMRL_ENV_PDP [pdp/env.py:206-226]: demand / vcap unused, N = number of pickups and deliveries (even), T == N; bad[0] +=
+ * rows that are not a permutation of 1 .. N (a node repeated or missing, the depot inside, an id out of range), bad[1] +=
+ * permutations that visit a delivery before its pickup (pickup i pairs with delivery i + N/2).  T == N + 1: tours of
+ * force_start_at_depot, which hold the depot itself -- accepted, as by the reference, on the first or the last position.
  * An id < 0 or above the highest node id never indexes out of bounds: the validity check counts such a row as an invalid
  * tour, bad[0] += 1, and reads nothing through the id (SDVRP: its replay stops there).  The same holds for the checks of
  * eamrl_op_check_solution, eamrl_cvrptw_check_time and eamrl_rollout_finish; where a kernel also computes a length or a
