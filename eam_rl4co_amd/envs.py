@@ -19,7 +19,7 @@ from typing import Iterable, Optional
 import numpy as np
 import torch
 
-from . import ops
+from . import env_spec, ops
 from .tensordict_lite import TensorDict
 
 log = logging.getLogger(__name__)
@@ -395,8 +395,15 @@ class RL4COEnvBase:
             return sel.t().reshape(-1)                     # "b n -> (n b)"
         return sel + 1 if self.name in ("cvrp", "sdvrp", "pctsp", "spctsp", "op", "cvrptw") else sel
 
+    def _get_reward(self, td, actions):
+        rec = env_spec.spec(self.name)          # the reward and validity calls and messages of the env's record
+        return ops.call_spec(rec.reward, td, actions.contiguous())
+
     def check_solution_validity(self, td, actions) -> None:
-        raise NotImplementedError
+        rec = env_spec.spec(self.name)
+        bad = ops.call_spec(rec.check, td, actions.contiguous(), td.get("vehicle_capacity")).tolist()
+        assert bad[0] == 0, rec.messages[0]
+        assert bad[1] == 0, rec.messages[1]
 
     def replace_selected_actions(self, cur_actions, new_actions, selection_mask):
         raise NotImplementedError
@@ -507,13 +514,6 @@ class TSPEnv(RL4COEnvBase):
     def get_action_mask(self, td):
         return td["action_mask"]
 
-    def _get_reward(self, td, actions):
-        return ops.tour_length_reward(td["locs"].contiguous(), actions.contiguous(), with_depot=False)
-
-    def check_solution_validity(self, td, actions) -> None:
-        bad = ops.check_solution("tsp", actions.contiguous())
-        assert int(bad[0]) == 0, "Invalid tour"
-
     def replace_selected_actions(self, cur_actions, new_actions, selection_mask):
         cur_actions[selection_mask] = new_actions[selection_mask]
         return cur_actions
@@ -584,14 +584,6 @@ class CVRPEnv(RL4COEnvBase):
                        _flat(td["current_node"], torch.int64), mask)
         return mask
 
-    def _get_reward(self, td, actions):
-        return ops.tour_length_reward(td["locs"].contiguous(), actions.contiguous(), with_depot=True)
-
-    def check_solution_validity(self, td, actions) -> None:
-        bad = ops.check_solution("cvrp", actions.contiguous(), td["demand"].contiguous(), td["vehicle_capacity"]).tolist()
-        assert bad[0] == 0, "Invalid tour"
-        assert bad[1] == 0, "Used more than capacity"
-
     @staticmethod
     def load_data(fpath, batch_size=[]):
         """demand is stored unnormalised in the .npz wire format (cvrp/env.py:187-194)."""
@@ -655,8 +647,9 @@ class SDVRPEnv(CVRPEnv):
 
     def check_solution_validity(self, td, actions) -> None:
         bad = ops.check_solution("sdvrp", actions.contiguous(), td["demand"].contiguous(), td["vehicle_capacity"]).tolist()
-        assert bad[1] == 0, "Cannot visit depot twice if any nonzero demand"
-        assert bad[0] == 0, "All demand must be satisfied"
+        msg = env_spec.spec(self.name).messages
+        assert bad[1] == 0, msg[1]
+        assert bad[0] == 0, msg[0]
 
 
 class CVRPTWEnv(CVRPEnv):
@@ -793,12 +786,7 @@ class PCTSPEnv(RL4COEnvBase):
         if actions.size(-1) == 1:       # all tours return to the depot at once (env.py:168-171)
             assert bool((actions == 0).all()), "If all length 1 tours, they should be zero"
             return torch.zeros(actions.size(0), dtype=torch.float32, device=actions.device)
-        return ops.pctsp_reward(td["locs"].contiguous(), td["penalty"].contiguous(), actions.contiguous())
-
-    def check_solution_validity(self, td, actions) -> None:
-        bad = ops.check_solution("pctsp", actions.contiguous(), td["real_prize"].contiguous()).tolist()
-        assert bad[0] == 0, "Duplicates"
-        assert bad[1] == 0, "Total prize does not satisfy min total prize"
+        return super()._get_reward(td, actions)
 
 
 class SPCTSPEnv(PCTSPEnv):
@@ -866,14 +854,12 @@ class OPEnv(RL4COEnvBase):
         if actions.size(-1) == 1:       # all tours return to the depot at once (env.py:169-172)
             assert bool((actions == 0).all()), "If all length 1 tours, they should be zero"
             return torch.zeros(actions.size(0), dtype=torch.float32, device=actions.device)
-        return ops.op_reward(td["prize"].contiguous(), actions.contiguous())
+        return super()._get_reward(td, actions)
 
     def check_solution_validity(self, td, actions, add_distance_to_depot: bool = True) -> None:
         if not add_distance_to_depot:
             raise NotImplementedError("add_distance_to_depot=False is not built for MI355X")
-        bad = ops.op_check_solution(actions.contiguous(), td["locs"].contiguous(), td["max_length"].contiguous()).tolist()
-        assert bad[0] == 0, "Duplicates"
-        assert bad[1] == 0, "Max length exceeded"
+        super().check_solution_validity(td, actions)
 
 
 class PDPEnv(RL4COEnvBase):
@@ -929,15 +915,10 @@ class PDPEnv(RL4COEnvBase):
         mask = torch.empty(td["available"].shape, dtype=torch.bool, device=td["available"].device)
         return ops.pdp_step_mask_(~td["available"], td["to_deliver"].contiguous(), None, None, mask)
 
-    def _get_reward(self, td, actions):
-        return ops.tour_length_reward(td["locs"].contiguous(), actions.contiguous(), with_depot=True)
-
     def check_solution_validity(self, td, actions) -> None:
         n = td["locs"].shape[-2] - 1
-        assert actions.shape[-1] == n + int(self.force_start_at_depot), "Not visiting all nodes"
-        bad = ops.check_solution("pdp", actions.contiguous(), num_loc=n).tolist()
-        assert bad[0] == 0, "Not visiting all nodes"
-        assert bad[1] == 0, "Deliverying without pick-up"
+        assert actions.shape[-1] == n + int(self.force_start_at_depot), env_spec.spec(self.name).messages[0]
+        super().check_solution_validity(td, actions)
 
     def get_num_starts(self, td):
         """Only the pickups can be start nodes (pdp/env.py:228-230)."""

@@ -9,13 +9,12 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, env_spec
 from ._lib import (ENV_CVRP, ENV_CVRPTW, ENV_OP, ENV_PCTSP, ENV_PDP, ENV_SDVRP, ENV_TSP, EVALUATE, GREEDY, NORM_BATCH_EVAL, NORM_INSTANCE, SAMPLE,  # noqa: F401
                    ST_INFEASIBLE, ST_NAN_LOGITS, ST_STEP_OVERRUN)
 
 MODES = {"greedy": GREEDY, "sampling": SAMPLE, "evaluate": EVALUATE}
-ENVS = {"tsp": ENV_TSP, "cvrp": ENV_CVRP, "sdvrp": ENV_SDVRP, "pctsp": ENV_PCTSP, "op": ENV_OP, "cvrptw": ENV_CVRPTW,
-        "pdp": ENV_PDP}
+ENVS = {name: spec.abi_id for name, spec in env_spec.ENV_SPECS.items()}
 
 
 def _need_gpu(t: torch.Tensor, name: str):
@@ -507,7 +506,7 @@ def replay_states(st, actions, B):
     if R != st.R or st.env_name not in ("cvrp", "cvrptw", "pctsp", "op") or st.M > 1024:
         raise ValueError("replay_states: cvrp / cvrptw / pctsp / op states of at most 1024 nodes, one action row per state row")
     dev = actions.device
-    NC = 2 if st.env_name == "cvrptw" else 1
+    NC = env_spec.ENV_SPECS[st.env_name].n_state_cols
     # (graphs above 112 nodes: the chunked layout of the key-chunked re-evaluation kernels)
     bits = torch.empty((R, T, -(-st.M // 112), 4) if st.M > 112 else (R, T, 4), dtype=torch.int32, device=dev)
     idxA = torch.empty(R, T, dtype=torch.int32, device=dev)
@@ -1028,6 +1027,13 @@ def multi_copy_(pairs):
         _lib.check(lib.eamrl_multi_copy(n, srcs, dsts, nbytes, _stream(part[0][0])), "eamrl_multi_copy")
 
 
+def call_spec(entry, td, actions, vcap=None):
+    """A `reward` / `check` entry (ops function, arguments) of an env_spec record on the tours `actions` [R, T]."""
+    special = {env_spec.ACTION: actions, env_spec.NUM_LOC: td["locs"].shape[-2] - 1, env_spec.VCAP: vcap}
+    return globals()[entry[0]](*(a if not isinstance(a, str) else special[a] if a in special else a[1:] if a[0] == "="
+                                 else td[a].contiguous() for a in entry[1]))
+
+
 def rollout_finish(env_name, locs, actions, logp=None, demand=None, vcap=None, want_reward=True, bad=None):
     """Reward, summed log-likelihood and validity counters of TSP / CVRP tours in one launch (eamrl_rollout_finish):
     bit-identical to tour_length_reward / sum_logp / check_solution.  bad: int32[2] device tensor to add to, or None.
@@ -1305,60 +1311,46 @@ class DecodeCache:
 
 
 def slot_map(env_name):
-    names = ["K", "V", "L", "Pa", "Pb", "Lp"] if env_name == "tsp" else ["K", "V", "L", "Pa", "Lp"]
+    names = ["K", "V", "L", "Pa", "Pb", "Lp"] if env_spec.ENV_SPECS[env_name].has_pb else ["K", "V", "L", "Pa", "Lp"]
     return {n: i for i, n in enumerate(names)}
 
 
 class RolloutState:
-    """Flat per-row state tensors (struct eamrl_state) for R = S*B rows."""
+    """Flat per-row state tensors (struct eamrl_state) for R = S*B rows.  Every slot of the struct is an attribute, None
+    where the env does not use it; which slots an env uses, and what they mean there, is env_spec.ENV_SPECS[env].fields."""
+    first = cur = istep = used = vcap = demand = mask = visited = done = rem = locs = time = tw = dur = None
+    heads_out = to_deliver = None           # heads_out: [R, t_max, E] while `rollout` captures the glimpse outputs
 
     def __init__(self, env_name, R, M, device, demand=None):
         self.env_name, self.R, self.M = env_name, R, M
-        i64 = dict(dtype=torch.int64, device=device)
-        self.first = torch.zeros(R, **i64)
-        self.cur = torch.zeros(R, **i64)
-        self.istep = torch.zeros(R, **i64)
         self.done = torch.zeros(R, dtype=torch.bool, device=device)
         self.mask = torch.ones(R, M, dtype=torch.bool, device=device)
-        self.used = self.vcap = self.visited = self.rem = self.to_deliver = None
+        # (the per-instance tensors are the caller's: `demand`; locs, tw, dur set afterwards)
+        for f in filter(lambda f: f.per_row, env_spec.ENV_SPECS[env_name].fields):
+            v = (torch.ones if f.reset == "ones" else torch.zeros)(
+                (R,) + env_spec.dims(f.shape, M, device=True), device=device,
+                dtype=torch.uint8 if f.dtype == torch.bool else f.dtype)        # (bool planes are passed as bytes anyway)
+            if f.reset.startswith("depot"):
+                v[:, :1 if f.reset == "depot" else (M - 1) // 2 + 1] = 1
+            setattr(self, f.slot, v)
         self.demand = demand
-        self.locs = None                                                       # op, cvrptw: node coordinates [B, M, 2]
-        self.time = self.tw = self.dur = None                                  # cvrptw: clock [R], windows, service times
-        if env_name == "cvrptw":
-            self.time = torch.zeros(R, dtype=torch.float32, device=device)
-        if env_name in ("cvrp", "sdvrp", "pctsp", "op", "cvrptw"):
-            self.used = torch.zeros(R, dtype=torch.float32, device=device)     # pctsp: cur_total_prize; op: tour_length
-            self.vcap = torch.ones(R, dtype=torch.float32, device=device)      # pctsp: prize_required; op: max_length[:, 0]
-        if env_name in ("cvrp", "pctsp", "op", "cvrptw", "pdp"):
-            self.visited = torch.zeros(R, M, dtype=torch.uint8, device=device)
-        if env_name == "pdp":       # the reset state of PDPEnv: depot visited, depot and pickups to deliver, mask = their AND
-            self.visited[:, 0] = 1
-            self.to_deliver = torch.zeros(R, M, dtype=torch.uint8, device=device)
-            self.to_deliver[:, :(M - 1) // 2 + 1] = 1
+        if self.to_deliver is not None:     # the reset state of PDPEnv: depot visited, depot and pickups to deliver, mask = their AND
             self.mask = (self.visited == 0) & (self.to_deliver != 0)
-        if env_name == "sdvrp":
-            self.rem = torch.zeros(R, M, dtype=torch.float32, device=device)   # demand_with_depot
 
     def reorder_(self, idx):
         """Rows taken from rows `idx` (beam search: every beam continues the state of its parent beam).  vcap is
-        per instance and the row order keeps r % B, so it needs no reordering, nor does demand."""
-        for name in ("first", "cur", "istep", "done", "mask", "used", "visited", "rem", "time", "to_deliver"):
-            v = getattr(self, name, None)
-            if v is not None:
-                setattr(self, name, v.index_select(0, idx).contiguous())
+        per instance and the row order keeps r % B, so it needs no reordering, nor do the per-instance tensors.  Every
+        per-row slot of the env must be set (as `__init__` and `policy.state_from_td` leave it)."""
+        rows = [f.slot for f in env_spec.ENV_SPECS[self.env_name].fields if f.per_row and f.slot != "vcap"]
+        for name in ["mask", "done"] + rows:
+            setattr(self, name, getattr(self, name).index_select(0, idx).contiguous())
 
     def struct(self):
         s = _lib.State()
-        s.first, s.cur, s.istep = _ptr(self.first), _ptr(self.cur), _ptr(self.istep)
-        s.used, s.vcap, s.demand = _ptr(self.used), _ptr(self.vcap), _ptr(self.demand)
-        s.mask, s.done = _ptr(_bytes(self.mask)), _ptr(_bytes(self.done))
-        s.visited = _ptr(None if self.visited is None else _bytes(self.visited))
-        s.rem = _ptr(getattr(self, "rem", None))
-        s.locs = _ptr(getattr(self, "locs", None))
-        s.time, s.tw, s.dur = (_ptr(getattr(self, k, None)) for k in ("time", "tw", "dur"))
-        s.heads_out = _ptr(getattr(self, "heads_out", None))       # [R, t_max, E] or None (eamrl_state.heads_out)
-        td = getattr(self, "to_deliver", None)
-        s.to_deliver = _ptr(None if td is None else _bytes(td))
+        for name, _ in s._fields_:
+            t = getattr(self, name)
+            if t is not None:               # (a bool tensor and its uint8 view share the address)
+                setattr(s, name, t.data_ptr())
         return s
 
 
@@ -1366,43 +1358,20 @@ def _validate_state(st: RolloutState, cache: DecodeCache):
     R, M = st.R, st.M
     if M != cache.M or R % cache.B:
         raise ValueError("decode: state / cache shape mismatch")
+    spec = env_spec.ENV_SPECS[st.env_name]
     _chk(st.mask, "action_mask", torch.bool, (R, M))
-    _chk(st.cur, "current_node", torch.int64, (R,))
     _chk(st.done, "done", torch.bool, (R,))
-    if st.env_name == "tsp":
-        _chk(st.first, "first_node", torch.int64, (R,))
-        _chk(st.istep, "i", torch.int64, (R,))
-    elif st.env_name == "pdp":
-        if M < 3 or M % 2 == 0:
-            raise ValueError("decode: PDP needs an odd number of nodes (depot + pickups + deliveries)")
-        _chk(_bytes(st.visited), "visited", torch.uint8, (R, M))
-        _chk(_bytes(st.to_deliver), "to_deliver", torch.uint8, (R, M))
-    else:
-        _chk(st.used, "used_capacity", torch.float32, (R,))
-        _chk(st.vcap, "vehicle_capacity", torch.float32, (R,))
-        if st.env_name == "sdvrp":
-            _chk(st.rem, "demand_with_depot", torch.float32, (R, M))
-            _chk(cache.dyn, "dynamic embedding vectors", torch.float32, (3, cache.E))
-        elif st.env_name == "pctsp":
-            _chk(_bytes(st.visited), "visited", torch.uint8, (R, M))
-            _chk(st.demand, "real_prize", torch.float32, (cache.B, M))
-            _chk(st.istep, "i", torch.int64, (R,))
-        elif st.env_name == "cvrptw":
-            _chk(st.visited, "visited", torch.uint8, (R, M))
-            _chk(st.demand, "demand", torch.float32, (cache.B, M - 1))
-            _chk(st.time, "current_time", torch.float32, (R,))
-            _chk(st.locs, "locs", torch.float32, (cache.B, M, 2))
-            _chk(st.tw, "time_windows", torch.float32, (cache.B, M, 2))
-            _chk(st.dur, "durations", torch.float32, (cache.B, M))
-            _chk(cache.cvec, "context state columns", torch.float32, (2 * cache.E,))
-        elif st.env_name == "op":
-            _chk(_bytes(st.visited), "visited", torch.uint8, (R, M))
-            _chk(st.demand, "max_length", torch.float32, (cache.B, M))
-            _chk(st.locs, "locs", torch.float32, (cache.B, M, 2))
-            _chk(st.istep, "i", torch.int64, (R,))
-        else:
-            _chk(st.visited, "visited", torch.uint8, (R, M))
-            _chk(st.demand, "demand", torch.float32, (cache.B, M - 1))
+    if st.to_deliver is not None and (M < 3 or M % 2 == 0):
+        raise ValueError("decode: PDP needs an odd number of nodes (depot + pickups + deliveries)")
+    for f in spec.fields:
+        t, dtype = getattr(st, f.slot), f.dtype
+        if dtype == torch.bool and isinstance(t, torch.Tensor):     # bool planes: bool or their uint8 storage
+            t, dtype = _bytes(t), torch.uint8
+        _chk(t, f.key, dtype, (R if f.per_row else cache.B,) + env_spec.dims(f.shape, M, device=True))
+    if st.rem is not None:      # the remaining demands are what the dynamic embedding multiplies
+        _chk(cache.dyn, "dynamic embedding vectors", torch.float32, (3, cache.E))
+    if spec.n_state_cols > 1:
+        _chk(cache.cvec, "context state columns", torch.float32, (spec.n_state_cols * cache.E,))
 
 
 def decode_step(st: RolloutState, cache: DecodeCache, mode="greedy", noise=None, given=None, clip=10.0, temp=1.0,
@@ -1557,8 +1526,7 @@ def rollout(st: RolloutState, cache: DecodeCache, mode="greedy", noise=None, giv
     _validate_state(st, cache)
     R, M, dev = st.R, st.M, st.mask.device
     if t_max is None:
-        t_max = {"tsp": M, "cvrp": 2 * M + 1, "sdvrp": 3 * M + 1, "pctsp": M + 1, "op": M + 1, "cvrptw": 2 * M + 1,
-                 "pdp": M}[st.env_name]
+        t_max = env_spec.max_steps(st.env_name, M)
     if mode == "sampling" and noise is None:
         if seed is None:
             raise ValueError("rollout: sampling needs `noise` or `seed`")

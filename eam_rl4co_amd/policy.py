@@ -20,7 +20,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .envs import RL4COEnvBase, get_env
+from .env_spec import ACTION, ALIASES, ENV_SPECS, max_steps
+from .envs import ENV_REGISTRY, RL4COEnvBase, get_env
 from .tensordict_lite import TensorDict  # noqa: F401
 from .utils import unbatchify, unbatchify_and_gather
 
@@ -32,15 +33,10 @@ DECODE_TYPES = ("greedy", "sampling", "multistart_greedy", "multistart_sampling"
 PRECISIONS = {"32-true": None, "16-mixed": torch.float16, "bf16-mixed": torch.bfloat16}
 
 
-# envs that share kernels, embeddings and state layout with another one: SPCTSP is PCTSP whose collected prize is the
-# stochastic one (the policy sees the expected prize either way)
-_ENV_KIND = {"spctsp": "pctsp"}
-
-
 def _kind(env_name):
     if isinstance(env_name, RL4COEnvBase):
         env_name = env_name.name
-    return _ENV_KIND.get(env_name, env_name)
+    return ALIASES.get(env_name, env_name)
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -465,7 +461,7 @@ class AttentionModelDecoder(nn.Module):
         E = self.embed_dim
         self._weight_constants()
         slots = ops.slot_map(self.env_name)
-        nproj = 5 if self.env_name == "tsp" else 4
+        nproj = len(slots) - 1      # K, V, L, Pa (, Pb): all but Lp
         Wout = self.pointer.project_out.weight
         key = (self._wc_key, Wout.data_ptr(), Wout._version)
         if dtype is not None:       # 16-bit packs: slots of their own per dtype, refreshed in place like the fp32 ones
@@ -520,7 +516,7 @@ class AttentionModelDecoder(nn.Module):
         else:
             buf = torch.empty(B, M, len(slots) * E, device=emb.device, dtype=torch.float32)
             flat = buf.view(B * M, -1)
-            nproj = 5 if self.env_name == "tsp" else 4           # K, V, L, Pa (, Pb): slots 0 .. nproj-1
+            nproj = len(slots) - 1          # K, V, L, Pa (, Pb): slots 0 .. nproj-1, all but Lp
             assert slots["Pa"] == 3 and slots.get("Pb", 4) == 4
             ops.linear(emb, self._w_cache, out=flat[:, 0:nproj * E])
             ops.matmul_right(flat[:, slots["L"] * E:(slots["L"] + 1) * E], self.pointer.project_out.weight.contiguous(),
@@ -590,28 +586,11 @@ class AttentionModelDecoder(nn.Module):
 
 def _env_step_(st: ops.RolloutState, action):
     """The env transition (+ mask) of `st.env_name` on the flat state, in place."""
-    if st.env_name == "tsp":
-        ops.tsp_step_(st.mask, st.first, st.cur, st.istep, action, st.done)
-    elif st.env_name == "cvrp":
-        ops.cvrp_step_mask_(st.visited, st.used, st.vcap, st.demand, st.cur, action, st.mask, st.done)
-    elif st.env_name == "pctsp":
-        ops.pctsp_step_mask_(st.visited, st.used, None, st.demand, None, st.cur, st.istep, action, st.mask, st.done)
-    elif st.env_name == "cvrptw":
-        ops.cvrptw_step_mask_(st.visited, st.used, st.vcap, st.demand, st.cur, st.time, st.locs, st.tw, st.dur, action,
-                              st.mask, st.done)
-    elif st.env_name == "op":
-        ops.op_step_mask_(st.visited, st.used, None, None, st.locs, st.demand, st.cur, st.istep, action, st.mask, st.done)
-    elif st.env_name == "pdp":
-        ops.pdp_step_mask_(st.visited, st.to_deliver, st.cur, action, st.mask, st.done)
-    else:
-        ops.sdvrp_step_mask_(st.rem, st.used, st.vcap, st.cur, action, st.mask, st.done)
+    fn, args = ENV_SPECS[st.env_name].step
+    getattr(ops, fn)(*(action if a == ACTION else a if a is None else getattr(st, a) for a in args))
 
 
-def _max_decode_steps(env_name, M, npre=0):
-    """TSP: one step per remaining node; CVRP: every customer visit is followed by at most one depot visit; SDVRP: as
-    CVRP plus at most one split delivery per trip."""
-    return {"tsp": M - npre, "cvrp": 2 * M + 1, "sdvrp": 3 * M + 1, "pctsp": M + 1, "op": M + 1, "cvrptw": 2 * M + 1,
-            "pdp": M - npre}[env_name]        # PDP: N steps, N + 1 with force_start_at_depot (`_enqueue` takes the exact count)
+_max_decode_steps = max_steps        # (env_name, M, npre=0): the bound of the env's record
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -621,7 +600,8 @@ def state_from_td(env_name, td, num_starts: int = 0, copy: bool = True) -> ops.R
     """Flat state tensors for R = max(S,1)*B rows, replicated in the reference's (s b) order for multistart
     (utils/ops.py:13-33 batchify).  The kernels update the state in place, so the tensors are copies: like the
     reference's rollout, a policy call leaves the caller's TensorDict as it was (the same td can be rolled out again,
-    e.g. by a rollout baseline).  copy=False hands out views of the td's own tensors (read-only uses)."""
+    e.g. by a rollout baseline).  copy=False hands out views of the td's own tensors (read-only uses).
+    Which key lands in which slot, as what: env_spec.ENV_SPECS[env_name].fields."""
     mask = td["action_mask"]
     B, M = mask.shape
     S = max(int(num_starts), 1)
@@ -651,43 +631,12 @@ def state_from_td(env_name, td, num_starts: int = 0, copy: bool = True) -> ops.R
         return t.reshape(-1) if t.dim() == 2 and t.shape[1] == 1 else t
 
     st.mask = rep(mask, torch.bool)
-    st.cur = rep(td["current_node"], torch.int64)
     done = td["done"] if "done" in td.keys() else torch.zeros(B, dtype=torch.bool, device=dev)
     st.done = rep(done, torch.bool)
-    st.first = st.istep = st.used = st.vcap = st.visited = st.demand = st.rem = st.locs = None
-    st.time = st.tw = st.dur = st.to_deliver = None
-    if env_name == "pdp":           # visited = ~available; no scalar state
-        st.visited = rep(~td["available"], torch.uint8)
-        st.to_deliver = rep(td["to_deliver"], torch.uint8)
-    elif env_name == "tsp":
-        st.first = rep(td["first_node"], torch.int64)
-        st.istep = rep(td["i"], torch.int64)
-    elif env_name == "op":          # used = tour length, vcap = the instance's max_length[:, 0], demand = arrival limits
-        st.used = rep(td["tour_length"], torch.float32)
-        st.vcap = rep(td["max_length"][..., 0], torch.float32)
-        st.demand = td["max_length"].contiguous()
-        st.locs = td["locs"].contiguous()
-        st.visited = rep(td["visited"], torch.bool)
-        st.istep = rep(td["i"], torch.int64)
-    elif env_name == "pctsp":       # used = collected prize, vcap = required prize, demand = prize per node (depot slot 0)
-        st.used = rep(td["cur_total_prize"], torch.float32)
-        st.vcap = rep(td["prize_required"], torch.float32)
-        st.demand = td["real_prize"].contiguous()
-        st.visited = rep(td["visited"], torch.bool)
-        st.istep = rep(td["i"], torch.int64)
-    else:
-        st.used = rep(td["used_capacity"], torch.float32)
-        st.vcap = rep(td["vehicle_capacity"], torch.float32)
-        st.demand = td["demand"].contiguous()
-        if env_name in ("cvrp", "cvrptw"):
-            st.visited = rep(td["visited"], torch.uint8)
-        else:
-            st.rem = rep(td["demand_with_depot"], torch.float32)
-        if env_name == "cvrptw":
-            st.time = rep(td["current_time"], torch.float32)
-            st.locs = td["locs"].contiguous()
-            st.tw = td["time_windows"].to(torch.float32).contiguous()
-            st.dur = td["durations"].to(torch.float32).contiguous()
+    for f in ENV_SPECS[env_name].fields:
+        t = td[f.key]
+        t = t[..., 0] if f.transform == "col0" else ~t if f.transform == "not" else t
+        setattr(st, f.slot, rep(t, f.dtype) if f.per_row else (t if t.dtype == f.dtype else t.to(f.dtype)).contiguous())
     if clones:
         ops.multi_copy_(clones)
     return st
@@ -697,23 +646,11 @@ def state_to_td(env_name, st: ops.RolloutState, td, locs_rows=None):
     """TensorDict of the final state in the reference's post-step shapes."""
     R = st.R
     out = {"action_mask": st.mask, "done": st.done, "reward": torch.zeros_like(st.done)}
-    if env_name == "pdp":           # "i" is advanced by `_finish`, which knows the number of steps
-        out.update({"current_node": st.cur.reshape(R, 1), "available": st.visited == 0, "to_deliver": st.to_deliver != 0})
-    elif env_name == "tsp":
-        out.update({"first_node": st.first, "current_node": st.cur, "i": st.istep.reshape(R, 1)})
-    elif env_name == "op":
-        # current_total_prize is bookkeeping of env.step only (the reward is recomputed from the actions)
-        out.update({"current_node": st.cur.reshape(R, 1), "tour_length": st.used, "visited": st.visited, "i": st.istep})
-    elif env_name == "pctsp":
-        # cur_total_penalty is bookkeeping of env.step only (no decision reads it): the fused rollout does not carry it
-        out.update({"current_node": st.cur, "cur_total_prize": st.used, "prize_required": st.vcap, "visited": st.visited,
-                    "i": st.istep})
-    else:
-        out.update({"current_node": st.cur.reshape(R, 1), "used_capacity": st.used.reshape(R, 1),
-                    "vehicle_capacity": st.vcap.reshape(R, 1)})
-        out.update({"visited": st.visited} if env_name in ("cvrp", "cvrptw") else {"demand_with_depot": st.rem})
-        if env_name == "cvrptw":
-            out["current_time"] = st.time.reshape(R, 1)
+    for f in ENV_SPECS[env_name].fields:
+        if f.per_row and f.emit:
+            v = getattr(st, f.slot)
+            v = v == 0 if f.transform == "not" else v != 0 if f.src_dtype == torch.bool else v
+            out[f.key] = v.reshape(R, 1) if f.shape == (1,) else v     # (the state's scalars are flat [R])
     B = td.batch_size[0]
     S = R // B
     for k, v in td.items():
@@ -1045,7 +982,7 @@ class AttentionModelPolicy(nn.Module):
         # x + 0 is exact in the lane tree), nor the log-likelihood sum, nor validity.
         actions_pad = torch.cat(pre_actions + [acts], 1) if pre_actions else acts
         logp_pad = torch.cat(pre_logps + [lps], 1) if pre_logps else lps
-        native_env = type(env).__name__ in ("TSPEnv", "CVRPEnv", "SDVRPEnv", "PCTSPEnv", "SPCTSPEnv", "OPEnv", "CVRPTWEnv", "PDPEnv") and type(env).__module__ == RL4COEnvBase.__module__
+        native_env = type(env) in ENV_REGISTRY.values()
         fast = info is not None and native_env and not select_best
         reward_pad = ll_pad = bad = None
         one_launch = fast and self.env_name in ("tsp", "cvrp") and calc_reward
@@ -1057,22 +994,11 @@ class AttentionModelPolicy(nn.Module):
                                                     td["demand"].contiguous() if self.env_name == "cvrp" else None,
                                                     st.vcap, bad=bad)
         elif fast:
-            locs = td["locs"].contiguous()
             if calc_reward:
-                if self.env_name == "pctsp":        # depot padding: zero-length legs and zero penalties, exact
-                    reward_pad = ops.pctsp_reward(locs, td["penalty"].contiguous(), actions_pad)
-                elif self.env_name == "op":         # depot padding adds zero prizes
-                    reward_pad = ops.op_reward(td["prize"].contiguous(), actions_pad)
-                else:
-                    reward_pad = ops.tour_length_reward(locs, actions_pad, with_depot=(self.env_name != "tsp"))
-                if env.check_solution and self.env_name not in ("sdvrp", "cvrptw"):   # those: checked in _finish
-                    bad = (ops.check_solution("tsp", actions_pad) if self.env_name == "tsp" else
-                           ops.check_solution("pdp", actions_pad, num_loc=M - 1) if self.env_name == "pdp" else
-                           ops.check_solution("pctsp", actions_pad, td["real_prize"].contiguous())
-                           if self.env_name == "pctsp" else
-                           ops.op_check_solution(actions_pad, locs, td["max_length"].contiguous())
-                           if self.env_name == "op" else
-                           ops.check_solution("cvrp", actions_pad, td["demand"].contiguous(), st.vcap))
+                spec = ENV_SPECS[self.env_name]
+                reward_pad = ops.call_spec(spec.reward, td, actions_pad)
+                if env.check_solution and spec.check_padded != "no":        # "no": checked in _finish, on the exact slice
+                    bad = ops.call_spec(spec.check, td, actions_pad, st.vcap)
             if return_sum_log_likelihood and "mask" not in td.keys():
                 ll_pad = ops.sum_logp(logp_pad)
         flags = None
@@ -1118,30 +1044,16 @@ class AttentionModelPolicy(nn.Module):
 
         if p["calc_reward"]:
             if p["reward_pad"] is not None:
-                if bad_counts is not None:
-                    if self.env_name == "tsp" and npre + T != p["actions_pad"].shape[1]:
-                        # node 0 is a real city in TSP, so zero padding cannot be checked in place: the (rare)
-                        # short episode is re-checked on the exact slice
-                        env.check_solution_validity(td_out, actions_out.contiguous())
-                    elif self.env_name == "pctsp":
-                        assert bad_counts[0] == 0, "Duplicates"
-                        assert bad_counts[1] == 0, "Total prize does not satisfy min total prize"
-                    elif self.env_name == "op":
-                        assert bad_counts[0] == 0, "Duplicates"
-                        assert bad_counts[1] == 0, "Max length exceeded"
-                    elif self.env_name == "pdp":
-                        assert bad_counts[0] == 0, "Not visiting all nodes"
-                        assert bad_counts[1] == 0, "Deliverying without pick-up"
-                    else:
-                        assert bad_counts[0] == 0, "Invalid tour"
-                        assert bad_counts[1] == 0, "Used more than capacity"
-                elif self.env_name == "cvrptw" and env.check_solution:
-                    env.check_solution_validity(td_out, actions_out.contiguous())      # CVRP part + time-window replay
-                elif self.env_name == "sdvrp" and env.check_solution:
-                    # the reference's replay starts from (-capacity, demand...) and its verdict depends on where the
-                    # action tensor ends, so it runs on the exact [R, T] slice rather than on the padded one
+                spec = ENV_SPECS[self.env_name]
+                # if_full (TSP): node 0 is a real city, so zero padding can be neither checked nor measured in place:
+                # the (rare) short episode is re-checked and its reward recomputed on the exact slice
+                short = spec.check_padded == "if_full" and npre + T != p["actions_pad"].shape[1]
+                if bad_counts is not None and not short:
+                    assert bad_counts[0] == 0, spec.messages[0]
+                    assert bad_counts[1] == 0, spec.messages[1]
+                elif env.check_solution and (short or spec.check_padded == "no"):
                     env.check_solution_validity(td_out, actions_out.contiguous())
-                if self.env_name == "tsp" and npre + T != p["actions_pad"].shape[1]:
+                if short:
                     td_out.set("reward", env.get_reward(td_out, actions_out.contiguous(), check_solution=False))
                 else:
                     td_out.set("reward", p["reward_pad"])

@@ -25,6 +25,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .env_spec import ENV_SPECS
 from .utils import unbatchify
 
 
@@ -437,10 +438,7 @@ def _sdvrp_states(actions, demand_rows, vcap, M):
 # ------------------------------------------------------------------------------------------------------------
 # differentiable decoder inputs and the per-chunk log-probabilities
 # ------------------------------------------------------------------------------------------------------------
-_STATE_KEYS = {"cvrp": ("demand", "vehicle_capacity"), "sdvrp": ("demand", "vehicle_capacity"),
-               "cvrptw": ("demand", "vehicle_capacity", "locs", "time_windows", "durations"),
-               "op": ("locs", "max_length"), "pctsp": ("real_prize", "prize_required"), "tsp": (),
-               "pdp": ("available", "to_deliver", "action_mask")}
+_STATE_KEYS = {name: spec.reeval_static for name, spec in ENV_SPECS.items()}
 
 
 class shared_decoder_tensors:
@@ -719,7 +717,7 @@ def replay_states(policy, td, actions, S: int, multistart: bool):
         bits, idxA, sc = ops.replay_states(st, actions, B)
         return dict(maskbits=bits, idxA=idxA, idxB=None, sc=sc, tstart=1 if multistart else 0, placeholder=False)
     st = state_from_td(env_name, td, S)                         # (the step-by-step form, kept as the cross-check)
-    NC = 2 if env_name == "cvrptw" else 1
+    NC = ENV_SPECS[env_name].n_state_cols
     bits = torch.empty((R, T, -(-st.M // ops.KEY_CHUNK), 4) if big else (R, T, 4), dtype=torch.int32, device=dev)
     idxA = torch.empty(R, T, dtype=torch.int32, device=dev)
     sc = torch.empty(NC, R, T, dtype=torch.float32, device=dev)

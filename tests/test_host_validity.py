@@ -164,8 +164,20 @@ def test_out_of_range_ids_are_invalid_tours_in_the_restatement():
 
 
 def test_messages_are_the_ones_the_envs_raise():
+    """The messages of an env's two counters are stated once, in env_spec, in the order of the counters; the env classes
+    assert with exactly those.  The time-window message is the env class's own."""
+    from eam_rl4co_amd import envs
+    from eam_rl4co_amd.env_spec import spec
+
     with open(os.path.join(ROOT, "eam_rl4co_amd", "envs.py")) as f:
         text = f.read()
     for env in ENVS:
-        for msg in vr.MESSAGE[env].values():
-            assert re.search(re.escape(f'"{msg}'), text), msg
+        own = spec(envs.ENV_REGISTRY[env].name).messages
+        for code, msg in vr.MESSAGE[env].items():
+            if code == vr.LATE:
+                assert re.search(re.escape(f'"{msg}'), text), msg
+            else:
+                assert msg in own, msg
+    # no second copy of a counter message in the env classes
+    for msg in {m for env in ENVS for m in spec(env).messages}:
+        assert f'"{msg}' not in text, msg
