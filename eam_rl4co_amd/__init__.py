@@ -6,6 +6,7 @@ from .policy import (AttentionModelDecoder, AttentionModelEncoder, AttentionMode
                      load_reference_checkpoint, random_policy, rollout)
 from .attention import PointerAttention, scaled_dot_product_attention  # noqa: F401
 from .evolution import EA, EACvrpDraws, EAPrizeDraws, EADraws, evolution_worker, generate_batch_population  # noqa: F401
+from .search import EAS, EASEmb, EASLay, eas_loss_coefficients  # noqa: F401
 from .tensordict_lite import TensorDict  # noqa: F401
 from .utils import batchify, gather_by_index, unbatchify  # noqa: F401
 

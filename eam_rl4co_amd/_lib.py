@@ -111,6 +111,7 @@ PROTOTYPES = {
     "eamrl_tsp_mask_bits_chunked": [_vp, _vp, _i64, _i32, _i32, _vp],
     "eamrl_reeval_forward": [_vp, _vp],
     "eamrl_reeval_backward": [_vp, _vp],
+    "eamrl_reeval_backward_lp": [_vp, _vp],
     "eamrl_pack_mask_bits": [_vp, _vp, _i64, _i32, _i32, _i32, _vp],
     "eamrl_tsp_mask_bits": [_vp, _vp, _i64, _i32, _i32, _vp],
     "eamrl_mean_nodes": [_vp, _vp, _i64, _i32, _i32, _vp],

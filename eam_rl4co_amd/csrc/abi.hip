@@ -499,6 +499,27 @@ __attribute__((visibility("default"))) int eamrl_reeval_backward(const eamrl_ree
     return launched(launch_reeval_bwd(*p, (hipStream_t)stream), "eamrl_reeval_backward");
 }
 
+// (its own argument check: check_reeval(bwd = true) demands the gradient pointers this entry never touches)
+__attribute__((visibility("default"))) int eamrl_reeval_backward_lp(const eamrl_reeval* p, void* stream)
+{
+    const char* what = "eamrl_reeval_backward_lp";
+    REQUIRE(p, what);
+    REQUIRE(p->M >= 1 && p->M <= 112 && p->nkc <= 1 && !p->dyn && !p->rem, what);       // single chunk, no dynamic embedding
+    REQUIRE(p->Lp && p->maskbits && p->actions && p->logp && p->glogp && p->dLp, what);
+    REQUIRE(p->B > 0 && p->S > 0 && p->T > 0 && p->R == p->B * p->S && p->nchunk >= 1 && p->nchunk <= p->S, what);
+    REQUIRE(p->ld >= 128 && p->ld % 4 == 0 && p->ldg >= 128 && p->temp > 0.0f && p->tstart >= 0, what);
+    REQUIRE((uintptr_t)p->maskbits % 16 == 0 && p->R * (int64_t)p->T < (int64_t)1 << 31, what);
+    if (p->heads) {
+        REQUIRE(p->heads_T > 0 && (uintptr_t)p->heads % 16 == 0, what);
+    } else {            // the glimpse is recomputed
+        REQUIRE(p->K && p->V && p->Pa && p->idxA && ((p->idxB == nullptr) == (p->Pb == nullptr) || p->Pb), what);
+        REQUIRE(p->NC >= 0 && p->NC <= 2 && (p->NC == 0 || (p->Cvec && p->sc)), what);
+        REQUIRE(((uintptr_t)p->Pa % 16 == 0) && (!p->Pb || (uintptr_t)p->Pb % 16 == 0) && (!p->gctx || (uintptr_t)p->gctx % 16 == 0) &&
+                    (!p->Cvec || (uintptr_t)p->Cvec % 16 == 0), what);
+    }
+    return launched(launch_reeval_bwd_lp(*p, (hipStream_t)stream), what);
+}
+
 __attribute__((visibility("default"))) int eamrl_replay_states(int env, const eamrl_state* s, int64_t R, int64_t B, int M,
                                                               const int64_t* actions, int T, uint32_t* bits, int32_t* idxA,
                                                               float* sc, void* stream)

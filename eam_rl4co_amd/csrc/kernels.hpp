@@ -71,6 +71,7 @@ int launch_pack_mask_bits_chunked(const uint8_t* mask, uint32_t* bits, int64_t R
 int launch_tsp_mask_bits_chunked(const int64_t* actions, uint32_t* bits, int64_t R, int M, int T, hipStream_t st);
 int launch_reeval_fwd(const ReevalArgs& a, hipStream_t st);
 int launch_reeval_bwd(const ReevalArgs& a, hipStream_t st);
+int launch_reeval_bwd_lp(const ReevalArgs& a, hipStream_t st);      // dLp only (single chunk, no dynamic embedding)
 bool mha_encoder_bwd_supports(int N, int E, int H);
 int launch_mha_encoder_bwd(const float* qkv, const float* dout, float* dqkv, int64_t B, int N, hipStream_t st);
 // the same for 113 <= N <= 1024 (encoder_attn_bwd_mfma.hip; launch_mha_encoder_bwd dispatches to it)

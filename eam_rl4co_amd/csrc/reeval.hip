@@ -1043,6 +1043,174 @@ __global__ __launch_bounds__(512, 2) void k_reeval_bwd_logits(ReevalArgs a)
         }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// backward, logit key only (eamrl_reeval_backward_lp): dLp[n][e] += sum_q du[q][n] heads[q][e] and nothing else -- what an
+// adapted logit key needs (EAS-Emb: rl4co/models/zoo/eas/search.py:202-259 with eas_emb_cache_keys = ["logit_key"]).  L enters
+// the log-probs through u = heads . Lp / sqrt(E) alone and nothing upstream of the glimpse output depends on it, so the other
+// products of k_reeval_bwd_logits fall away exactly: no Lp^T fragments in LDS, no dheads product, no dheads write, and no
+// glimpse / gather kernels behind it.  Same grid, tiles and software pipeline as k_reeval_bwd_logits (two barriers per tile,
+// three when the normaliser is derived from the rollout's log-probs); single-chunk graphs, no dynamic embedding.
+// LDS: HTB [2][16][TS] | DU [16 RTT][DS] | LSE [16] and, when the glimpse is recomputed, QTB [2][16][TS] | CV [2][128].
+// ---------------------------------------------------------------------------------------------------------------------
+template <int RTT, bool HEADS>
+__global__ __launch_bounds__(512, 2) void k_reeval_bwd_lp(ReevalArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float* HTB = lds;                               // [2][16][TS]   heads tiles (A layout)
+    float* DU = HTB + 2 * 16 * TS;                  // [16 RTT][DS]
+    float* LSE = DU + 16 * RTT * DS;                // [16]
+    float* QTB = LSE + 16;                          // !HEADS: [2][16][TS]   q~ tiles
+    float* CV = QTB + 2 * 16 * TS;                  // !HEADS: [2][128] state-column vectors
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int j = lane & 15, G = lane >> 4;
+    const int jq = tid >> 5, e4 = tid & 31;
+    const Blk blk = decode_block(a);
+    const int64_t b = blk.b;
+    const int ch = blk.ch;
+    const int s0 = (int)((int64_t)a.S * ch / a.nchunk), s1 = (int)((int64_t)a.S * (ch + 1) / a.nchunk);
+    const int ns = s1 - s0, T = a.T;
+    const int ntiles = (ns * T + 15) / 16;
+    const bool derive_lse = a.lse == nullptr;       // logp = the rollout's log-probs: the normaliser is z[action] - logp
+
+    float kf[RTT][4], vtf[4 * RTT], lpf[32];
+    if (!HEADS) load_head_frags<RTT>(a, b, wv, lane, kf, vtf);
+    load_lp_frags(a, b, wv < RTT ? wv : RTT - 1, lane, lpf);       // (waves >= RTT compute no logits)
+    float4 gc = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!HEADS) {
+        for (int i = tid; i < 2 * RE; i += blockDim.x) CV[i] = i < a.NC * RE ? a.Cvec[i] : 0.0f;
+        if (a.gctx) gc = *reinterpret_cast<const float4*>(a.gctx + b * RE + 4 * e4);
+    }
+    f32x4 dLp[RTT];
+#pragma unroll
+    for (int nt = 0; nt < RTT; ++nt) dLp[nt] = z4();
+    const float inv_temp = 1.0f / a.temp;
+
+    auto qi_of = [&](const QWalk& w) -> int { return w.sl < ns ? ((s0 + w.sl) * (int)a.B + (int)b) * T + w.t : -1; };
+    auto load_heads = [&](const QWalk& w, RowPre& p) {
+        const int qi = qi_of(w);
+        const int64_t r = (int64_t)(s0 + min(w.sl, ns - 1)) * a.B + b;
+        const int th = max(w.t - a.tstart, 0);
+        p.fl = (qi >= 0 ? 1 : 0) | (w.t >= a.tstart && th < a.heads_T ? 8 : 0);
+        p.dh = *reinterpret_cast<const float4*>(a.heads + (r * a.heads_T + min(th, a.heads_T - 1)) * RE + 4 * e4);
+    };
+    auto stage_heads = [&](const RowPre& p, int buf) {
+        const bool ok = (p.fl & 9) == 9;
+        float* dp = HTB + buf * 16 * TS + jq * TS + e4;
+        dp[0] = ok ? p.dh.x : 0.0f; dp[TG] = ok ? p.dh.y : 0.0f; dp[2 * TG] = ok ? p.dh.z : 0.0f; dp[3 * TG] = ok ? p.dh.w : 0.0f;
+    };
+    // ---- prologue: tile 0 staged, indices of tile 1 in flight --------------------------------------------------------
+    QWalk wr, wj;                       // the staging role (query jq) and the MFMA role (query j) of this thread
+    wr.init(jq, T);
+    wj.init(j, T);
+    int qr = qi_of(wr), ia = -1, ib = -1;
+    {
+        RowPre pre;
+        if (HEADS) {
+            load_heads(wr, pre);
+            stage_heads(pre, 0);
+        } else {
+            load_idx(a, qr, ia, ib);
+            load_rows<false>(a, b, e4, qr, wr.t, ia, ib, pre);
+            __syncthreads();            // CV
+            stage_rows<false>(pre, gc, CV, QTB, nullptr, jq, e4);
+        }
+    }
+    wr.next(T);
+    qr = qi_of(wr);
+    if (!HEADS) load_idx(a, qr, ia, ib);    // tile 1
+    int qj = qi_of(wj), tj = wj.t;      // tile 0
+    uint4 mb = load_mask_words(a, qj);
+
+    // iteration `tile`: logits, du and the dLp product of tile `tile`, then the glimpse of tile + 1 (iteration -1: only that)
+    for (int tile = -1; tile < ntiles; ++tile) {
+        const int cur = tile & 1, nxt = cur ^ 1;
+        const float* HT = HTB + cur * 16 * TS;
+        uint4 mbn = mb;
+        int qjn = qj, tjn = tj;
+        if (tile >= 0) {
+            RowPre pre;
+            if (HEADS) {
+                load_heads(wr, pre);                                // heads rows of tile + 1
+                wr.next(T);
+            } else {
+                load_rows<false>(a, b, e4, qr, wr.t, ia, ib, pre);  // rows of tile + 1 (indices fetched one iteration ago)
+                wr.next(T);
+                qr = qi_of(wr);
+                load_idx(a, qr, ia, ib);                            // indices of tile + 2
+            }
+            const int qjc = max(qj, 0);
+            const bool live = qj >= 0 && tj >= a.tstart;
+            const int act_l = (int)a.actions[qjc];
+            const float g_l = a.glogp[qjc], lse_l = derive_lse ? a.logp[qjc] : a.lse[qjc];
+            wj.next(T);
+            qjn = qi_of(wj);
+            tjn = wj.t;
+            mbn = load_mask_words(a, qjn);
+            __syncthreads();            // heads of this tile complete; the previous tile's du has been consumed
+            f32x4 u = z4();
+            if (wv < RTT) u = logit_tile(lpf, HT, lane);
+            const int act = qj >= 0 ? act_l : -1;
+            const float g = live ? g_l : 0.0f;
+            float lse = live ? lse_l : 0.0f;
+            float zr[4] = {0.f, 0.f, 0.f, 0.f}, dz[4] = {0.f, 0.f, 0.f, 0.f};
+            if (wv < RTT) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) zr[r] = process_logit(u[r], a.clip, inv_temp, dz[r]);
+            }
+            if (derive_lse) {           // the lane that owns the chosen node publishes z[action] - logp for its query
+                if (wv < RTT) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (16 * wv + 4 * r + G == act && g != 0.0f) LSE[j] = zr[r] - lse;
+                }
+                __syncthreads();
+                if (g != 0.0f) lse = LSE[j];
+            }
+            if (wv < RTT) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int n0 = 16 * wv + 4 * r;
+                    const uint32_t w = (n0 >> 5) == 0 ? mb.x : (n0 >> 5) == 1 ? mb.y : (n0 >> 5) == 2 ? mb.z : mb.w;
+                    const bool ok = (w >> ((n0 & 31) + G)) & 1u;
+                    float du = 0.0f;
+                    if (ok && g != 0.0f) {
+                        const float p = fexp(zr[r] - lse);
+                        du = g * ((n0 + G == act ? 1.0f : 0.0f) - p) * dz[r];
+                    }
+                    DU[(n0 + G) * DS + j] = du;
+                }
+            }
+            if (HEADS) stage_heads(pre, nxt);
+            else stage_rows<false>(pre, gc, CV, QTB + nxt * 16 * TS, nullptr, jq, e4);
+            __syncthreads();            // du of this tile and the rows of the next one visible
+            // wave wv: embedding columns 16 wv .. 16 wv + 15 of every key tile
+            float hb[4];
+            const int c = 16 * wv + j;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) hb[t] = HT[(4 * t + G) * TS + (c & 3) * TG + (c >> 2)];
+#pragma unroll
+            for (int nt = 0; nt < RTT; ++nt)
+#pragma unroll
+                for (int t = 0; t < 4; ++t) dLp[nt] = mf(DU[(16 * nt + j) * DS + 4 * t + G], hb[t], dLp[nt]);
+        } else {
+            __syncthreads();            // q~ (or heads) of tile 0 visible
+        }
+        mb = mbn; qj = qjn; tj = tjn;
+        if (!HEADS && tile + 1 < ntiles)
+            glimpse_tile<RTT>(kf, vtf, QTB + nxt * 16 * TS, HTB + nxt * 16 * TS, wv, lane, mb, a.M);
+    }
+    // dLp: lane (column 16 wv + j, G), register r -> key 16 nt + 4 G + r.  The caller's buffer is accumulated into and nchunk
+    // workgroups share an instance: float atomics, as k_reeval_bwd_logits
+#pragma unroll
+    for (int nt = 0; nt < RTT; ++nt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int n = 16 * nt + 4 * G + r;
+            if (n < a.M) atomicAdd(a.dLp + (b * a.M + n) * a.ldg + 16 * wv + j, dLp[nt][r]);
+        }
+}
+
 // One tile (16 queries) of attention backward for head h, shared by the glimpse backward (queries = decode steps) and the
 // encoder self-attention backward (queries = the instance's nodes): recomputes a = softmax(K q~ | mask), then
 //   da = V dO,  ds = a (da - sum a da),  dq~ = K^T ds (handed to store_dq as soon as it exists, so that its global store
@@ -1514,6 +1682,27 @@ int launch_reeval_bwd(const ReevalArgs& a0, hipStream_t st)
     if (a.M <= 32) return launch_bwd_t<2>(a, st);
     if (a.M <= 64) return launch_bwd_t<4>(a, st);
     return launch_bwd_t<7>(a, st);
+}
+
+template <int RTT>
+static int launch_bwd_lp_t(const ReevalArgs& a, hipStream_t st)
+{
+    const bool heads = a.heads != nullptr;
+    const size_t lds = (2 * 16 * (size_t)TS + 16 * RTT * DS + 16 + (heads ? 0 : 2 * 16 * TS + 2 * RE)) * sizeof(float);
+    auto k = heads ? k_reeval_bwd_lp<RTT, true> : k_reeval_bwd_lp<RTT, false>;
+    hipLaunchKernelGGL(k, dim3((unsigned)(a.B * a.nchunk)), dim3(512), lds, st, a);
+    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
+}
+
+int launch_reeval_bwd_lp(const ReevalArgs& a0, hipStream_t st)
+{
+    if (a0.B <= 0 || a0.S <= 0 || a0.T <= 0) return 0;
+    if (a0.M > KCH || a0.dyn) return EAMRL_E_LAUNCH;       // (checked by the caller)
+    ReevalArgs a = a0;
+    a.nkc = 1; a.mc_koff = 0; a.mc_mstride = 4;
+    if (a.M <= 32) return launch_bwd_lp_t<2>(a, st);
+    if (a.M <= 64) return launch_bwd_lp_t<4>(a, st);
+    return launch_bwd_lp_t<7>(a, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

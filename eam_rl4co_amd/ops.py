@@ -711,6 +711,21 @@ class ReevalPlan:
         _lib.check(lib.eamrl_reeval_backward(C.byref(s), _stream(self.buf)), "eamrl_reeval_backward")
         return dbuf, dg, dc
 
+    def backward_lp(self, glogp, out=None):
+        """-> dLp [B, M, E] = d(sum glogp * logp)/dLp and nothing else (eamrl_reeval_backward_lp): the gradient of an adapted logit
+        key (EAS-Emb).  `out` is accumulated into (+=).  Single-chunk graphs without a dynamic embedding (the library refuses any
+        other plan before it launches anything); works on a plan that reads a decoder cache in place (slots=)."""
+        lib = _lib.load()
+        glogp = glogp.contiguous()
+        _chk(glogp, "grad of logp", torch.float32, (self.R, self.T))
+        if out is None:
+            out = torch.zeros(self.B, self.M, self.E, dtype=torch.float32, device=self.buf.device)
+        _chk(out, "dLp", torch.float32, (self.B, self.M, self.E))
+        s = self._struct()
+        s.glogp, s.dLp, s.ldg = _ptr(glogp), _ptr(out), self.E
+        _lib.check(lib.eamrl_reeval_backward_lp(C.byref(s), _stream(self.buf)), "eamrl_reeval_backward_lp")
+        return out
+
 
 # ------------------------------------------------------------------------------------------------------
 # environment transitions

@@ -416,6 +416,11 @@ int eamrl_reeval_supported(int M, int E, int H);                  /* 1 for M <= 
 int64_t eamrl_reeval_scratch_floats(int64_t R, int T, int M);     /* 0 for M <= 112 */
 int eamrl_reeval_forward(const eamrl_reeval* p, void* stream);    /* -> logp, lse (lse may be NULL) [, entropy] */
 int eamrl_reeval_backward(const eamrl_reeval* p, void* stream);   /* glogp, lse (or rollout logp) -> dK dV dLp dPa dPb dgctx dCvec */
+/* d(sum glogp * logp)/dLp only: the gradient an adapted logit key needs (EAS-Emb).  Same struct as
+ * eamrl_reeval_backward; reads K V Pa Pb gctx Cvec idx* sc only when p->heads == NULL (glimpse recomputed); writes
+ * nothing but dLp (accumulated, +=, row stride ldg).  dK dV dPa dPb dgctx dCvec dheads may be NULL.
+ * Single-chunk graphs only (M <= 112, nkc <= 1), no dynamic embedding (dyn == NULL). */
+int eamrl_reeval_backward_lp(const eamrl_reeval* p, void* stream);
 
 /* bits[(r * T + t) * 4 + n / 32] bit (n % 32) = mask[r][n] for step t (call after every replayed env transition). */
 int eamrl_pack_mask_bits(const uint8_t* mask, uint32_t* bits, int64_t R, int M, int T, int t, void* stream);
