@@ -80,83 +80,111 @@ __device__ __forceinline__ float2 lds_read_b64(const float* p)
     return make_float2(v.x, v.y);
 }
 
+// One global_load_dwordx4 of packed weights.  The address space is spelled out: a weight pointer that is carried from one
+// phase to the next (the early loads below) is a generic pointer to the compiler, and a flat load counts on the LDS counter
+// too, so every wait for an A fragment would also wait for the weights just requested.
+__device__ __forceinline__ float4 global_load_b128(const float* p)
+{
+    typedef const __attribute__((address_space(1))) f32x4* global_ptr;
+    const f32x4 v = *(global_ptr)(p);
+    return make_float4(v[0], v[1], v[2], v[3]);
+}
+
 // First group of B fragments of a pass: issued early (before the previous phase's epilogue / barrier) so that the L2 latency
 // of a pass's first weights is not paid behind the barrier.
 template <int CT>
 __device__ __forceinline__ void load_b0(float4 (&b0)[CT], const float* const (&wp)[CT])
 {
 #pragma unroll
-    for (int ct = 0; ct < CT; ++ct) b0[ct] = *reinterpret_cast<const float4*>(wp[ct]);
+    for (int ct = 0; ct < CT; ++ct) b0[ct] = global_load_b128(wp[ct]);
+}
+
+// First group of A fragments of a pass ([rt][0]: k-steps 0, 1; [rt][1]: k-steps 2, 3).  Where the A buffer is not written by the
+// phase before the pass (HB in P1 and P4) they are read ahead of that phase's closing barrier, like the first weights; where
+// the barrier publishes the buffer (P3, P5, the Lp pass) right behind it.
+template <int RTW, int S>
+__device__ __forceinline__ void load_a0(float2 (&a0)[RTW][2], const float* arow, int nrt)
+{
+#pragma unroll
+    for (int rt = 0; rt < RTW; ++rt)
+        if (rt < nrt) {
+            a0[rt][0] = lds_read_b64(arow + rt * 16 * S);
+            a0[rt][1] = lds_read_b64(arow + rt * 16 * S + 2);
+        }
 }
 
 // acc[rt][ct] += A[rows of tile rt][k] * B[k][cols of tile ct] over NU groups of 4 k-steps (16 k values each).
 //   arow: LDS address of this lane's A row of tile 0 (+ g * G), tiles 16 * S floats apart; NU groups start at float offset 0
 //   wp[ct]: this lane's float4 of the first group of column tile ct; consecutive groups are 256 floats apart
-//   b0: the first group, already loaded (load_b0)
-// Software pipeline: the A fragments (LDS) and B fragments (L2) of group u + 1 are requested before the MFMAs of group u.
+//   b0, a0: the first group, already loaded (load_b0, load_a0)
+// Software pipeline: the A fragments (LDS) and B fragments (L2) of group u + 1 are requested during the MFMAs of group u, into
+// a second set of registers.  The compiler's scheduler, left alone, sinks every one of those loads down to its first use (an
+// exposed LDS latency every four MFMAs and an exposed L2 latency per group), so the order is pinned: nothing crosses a group
+// boundary (sched_barrier), and inside a group the weight loads come first, then one ds_read_b64 behind every second MFMA (a
+// block of 2 NRT reads in front of the MFMAs would itself be a bubble), then the remaining MFMAs.
 // SWAP: the MFMA takes the weight fragment as A and the activation fragment as B, so that acc[rt][ct] holds the TRANSPOSED
 // tile (lane = node row, registers = 4 consecutive output columns): the same products in the same k order, laid out for
 // float4 stores to row-major memory.
 // NRT: this wave's row tiles as a compile-time value (round 3: as a run-time count every k-step group carried a uniform branch
 // around the last tile's loads and MFMAs plus the register copies that merge the two paths)
-template <int RTW, int CT, int S, bool SWAP, int NRT>
+template <int RTW, int CT, int S, bool SWAP, int NRT, int NU>
 __device__ __forceinline__ void gemm_pass_n(f32x4 (&acc)[RTW][CT], const float* arow, const float* const (&wp)[CT],
-                                            int NU, const float4 (&b0)[CT])
+                                            const float4 (&b0)[CT], const float2 (&a0)[RTW][2])
 {
-    constexpr int nrt = NRT;
-    float4 bn[CT];
-    float2 an0[RTW], an1[RTW];
+    float4 b[2][CT];
+    float2 a[2][NRT][2];
 #pragma unroll
-    for (int ct = 0; ct < CT; ++ct) bn[ct] = b0[ct];
+    for (int ct = 0; ct < CT; ++ct) b[0][ct] = b0[ct];
 #pragma unroll
-    for (int rt = 0; rt < RTW; ++rt)
-        if (rt < nrt) {
-            an0[rt] = lds_read_b64(arow + rt * 16 * S);
-            an1[rt] = lds_read_b64(arow + rt * 16 * S + 2);
-        }
+    for (int rt = 0; rt < NRT; ++rt) { a[0][rt][0] = a0[rt][0]; a[0][rt][1] = a0[rt][1]; }
+#pragma unroll
     for (int u = 0; u < NU; ++u) {
-        float4 b[CT];
-        float2 a0[RTW], a1[RTW];
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) b[ct] = bn[ct];
-#pragma unroll
-        for (int rt = 0; rt < RTW; ++rt) { a0[rt] = an0[rt]; a1[rt] = an1[rt]; }
+        const int c = u & 1, n = c ^ 1;
+        __builtin_amdgcn_sched_barrier(0);
         if (u + 1 < NU) {
 #pragma unroll
-            for (int ct = 0; ct < CT; ++ct) bn[ct] = *reinterpret_cast<const float4*>(wp[ct] + (u + 1) * 256);
+            for (int ct = 0; ct < CT; ++ct) b[n][ct] = global_load_b128(wp[ct] + (u + 1) * 256);
 #pragma unroll
-            for (int rt = 0; rt < RTW; ++rt)
-                if (rt < nrt) {
-                    an0[rt] = lds_read_b64(arow + rt * 16 * S + 4 * (u + 1));
-                    an1[rt] = lds_read_b64(arow + rt * 16 * S + 4 * (u + 1) + 2);
-                }
+            for (int rt = 0; rt < NRT; ++rt) {
+                a[n][rt][0] = lds_read_b64(arow + rt * 16 * S + 4 * (u + 1));
+                a[n][rt][1] = lds_read_b64(arow + rt * 16 * S + 4 * (u + 1) + 2);
+            }
         }
 #pragma unroll
-        for (int rt = 0; rt < RTW; ++rt)
-            if (rt < nrt) {
+        for (int rt = 0; rt < NRT; ++rt) {
 #pragma unroll
-                for (int ct = 0; ct < CT; ++ct)
-                    acc[rt][ct] = SWAP ? mfma4(b[ct].x, a0[rt].x, acc[rt][ct]) : mfma4(a0[rt].x, b[ct].x, acc[rt][ct]);
+            for (int ct = 0; ct < CT; ++ct)
+                acc[rt][ct] = SWAP ? mfma4(b[c][ct].x, a[c][rt][0].x, acc[rt][ct]) : mfma4(a[c][rt][0].x, b[c][ct].x, acc[rt][ct]);
 #pragma unroll
-                for (int ct = 0; ct < CT; ++ct)
-                    acc[rt][ct] = SWAP ? mfma4(b[ct].y, a0[rt].y, acc[rt][ct]) : mfma4(a0[rt].y, b[ct].y, acc[rt][ct]);
+            for (int ct = 0; ct < CT; ++ct)
+                acc[rt][ct] = SWAP ? mfma4(b[c][ct].y, a[c][rt][0].y, acc[rt][ct]) : mfma4(a[c][rt][0].y, b[c][ct].y, acc[rt][ct]);
 #pragma unroll
-                for (int ct = 0; ct < CT; ++ct)
-                    acc[rt][ct] = SWAP ? mfma4(b[ct].z, a1[rt].x, acc[rt][ct]) : mfma4(a1[rt].x, b[ct].z, acc[rt][ct]);
+            for (int ct = 0; ct < CT; ++ct)
+                acc[rt][ct] = SWAP ? mfma4(b[c][ct].z, a[c][rt][1].x, acc[rt][ct]) : mfma4(a[c][rt][1].x, b[c][ct].z, acc[rt][ct]);
 #pragma unroll
-                for (int ct = 0; ct < CT; ++ct)
-                    acc[rt][ct] = SWAP ? mfma4(b[ct].w, a1[rt].y, acc[rt][ct]) : mfma4(a1[rt].y, b[ct].w, acc[rt][ct]);
+            for (int ct = 0; ct < CT; ++ct)
+                acc[rt][ct] = SWAP ? mfma4(b[c][ct].w, a[c][rt][1].y, acc[rt][ct]) : mfma4(a[c][rt][1].y, b[c][ct].w, acc[rt][ct]);
+        }
+        if (u + 1 < NU) {       // SchedGroupMask: 0x8 MFMA, 0x20 VMEM read, 0x100 DS read
+            __builtin_amdgcn_sched_group_barrier(0x20, CT, 0);
+#pragma unroll
+            for (int i = 0; i < 2 * NRT; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x8, 2, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
             }
+            __builtin_amdgcn_sched_group_barrier(0x8, 4 * NRT * (CT - 1), 0);
+        }
     }
+    __builtin_amdgcn_sched_barrier(0);
 }
 
 // nrt is one of two values per kernel variant: RTW (the first row half) or NLOW (the second)
-template <int RTW, int CT, int S, bool SWAP = false, int NLOW = RTW>
+template <int RTW, int CT, int S, int NU, bool SWAP = false, int NLOW = RTW>
 __device__ __forceinline__ void gemm_pass(f32x4 (&acc)[RTW][CT], const float* arow, int nrt, const float* const (&wp)[CT],
-                                          int NU, const float4 (&b0)[CT])
+                                          const float4 (&b0)[CT], const float2 (&a0)[RTW][2])
 {
-    if (NLOW == RTW || nrt == RTW) gemm_pass_n<RTW, CT, S, SWAP, RTW>(acc, arow, wp, NU, b0);
-    else gemm_pass_n<RTW, CT, S, SWAP, NLOW>(acc, arow, wp, NU, b0);
+    if (NLOW == RTW || nrt == RTW) gemm_pass_n<RTW, CT, S, SWAP, RTW, NU>(acc, arow, wp, b0, a0);
+    else gemm_pass_n<RTW, CT, S, SWAP, NLOW, NU>(acc, arow, wp, b0, a0);
 }
 
 // y = norm(res + acc) for the two column tiles of a wave, written back to HB in place (batch norm: per-column affine;
@@ -165,6 +193,7 @@ template <int RTW>
 __device__ __forceinline__ void residual_norm_store(const f32x4 (&acc)[RTW][2], float* HB, int row0, int nrt, int cw, int j, int G,
                                                     int norm, const float* cst /* LDS: scale [E] | shift [E] */)
 {
+    asm volatile("" : "+v"(j), "+v"(G));       // addresses rebuilt here, not carried through the layer (see P1's epilogue)
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct) {
         const int c = 32 * cw + 16 * ct + j;
@@ -209,6 +238,7 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
     const int row0 = rw ? 16 * RTA : 0;         // first row of this wave's tiles
     const int nrt = rw ? RTT - RTA : RTA;       // this wave's row tiles
     const int64_t inst = blockIdx.x;
+    const float* hrow = HB + (row0 + j) * SA + G * GA;          // this lane's A row of HB, tile 0
 #ifdef EAMRL_STAMPS
     unsigned long long st_acc[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_t = __builtin_readcyclecounter();
 #endif
@@ -221,6 +251,15 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
 
     for (int layer = 0; layer < a.nlayers; ++layer) {
         const eamrl_encoder_layer& Ly = a.L[layer];
+        // P1 of head group 0: its first weights and A fragments are requested ahead of the constants' barrier (h is stable
+        // since the barrier that ended the previous layer); those of group 1 ahead of P3 of group 0
+        const float* wp1[3];
+        float4 b1[3];
+        float2 a1[RTW][2];
+#pragma unroll
+        for (int x = 0; x < 3; ++x) wp1[x] = Ly.Wqkv + ((int64_t)(8 * x + cw) * (FE / 16)) * 256 + lane * 4;
+        load_b0<3>(b1, wp1);
+        load_a0<RTW, SA>(a1, hrow, nrt);
         // ---- the layer's biases and normalisation constants -> LDS (one exposed L2 latency per layer instead of one per
         //      pass: every accumulator is initialised with its bias before the first MFMA can issue) ------------------------
         for (int i = tid; i < NCST; i += blockDim.x) {
@@ -267,11 +306,6 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
             {
                 f32x4 acc[RTW][3];
                 const int ctq = 4 * hg + cw;
-                const float* wp[3];
-                float4 b0[3];
-#pragma unroll
-                for (int x = 0; x < 3; ++x) wp[x] = Ly.Wqkv + ((int64_t)(8 * x + ctq) * (FE / 16)) * 256 + lane * 4;
-                load_b0<3>(b0, wp);
 #pragma unroll
                 for (int x = 0; x < 3; ++x) {
                     const float b = CST[C_BQKV + 16 * (8 * x + ctq) + j];
@@ -279,17 +313,22 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
                     for (int rt = 0; rt < RTW; ++rt) acc[rt][x] = splat4(b);
                 }
                 ESTAMP(16);
-                gemm_pass<RTW, 3, SA, false, RTT - RTA>(acc, HB + (row0 + j) * SA + G * GA, nrt, wp, FE / 16, b0);
+                gemm_pass<RTW, 3, SA, FE / 16, false, RTT - RTA>(acc, hrow, nrt, wp1, b1, a1);
                 ESTAMP(17);
                 load_b0<2>(b3, wp3);
+                // The lane's coordinates behind an opaque copy: addresses built from j and G are loop invariants, which the
+                // compiler otherwise computes once per kernel and carries through P1 -- the phase with the most live registers
+                // (RTT = 7: 80 accumulators + two sets of fragments) -- in some 45 VGPRs
+                int je = j, Ge = G;
+                asm volatile("" : "+v"(je), "+v"(Ge));
                 // q (scaled) and k in the A layout of the 64-column buffers: column 16 cw + j -> (g = j & 3, t = 4 cw + (j >> 2))
-                float* qcol = QA + (j & 3) * 16 + 4 * cw + (j >> 2);
-                float* kcol = KB + (j & 3) * 16 + 4 * cw + (j >> 2);
-                float* vrow = VT + (16 * cw + j) * SV;
+                float* qcol = QA + (je & 3) * 16 + 4 * cw + (je >> 2);
+                float* kcol = KB + (je & 3) * 16 + 4 * cw + (je >> 2);
+                float* vrow = VT + (16 * cw + je) * SV;
 #pragma unroll
                 for (int rt = 0; rt < RTW; ++rt)
                     if (rt < nrt) {
-                        const int rbase = row0 + 16 * rt + 4 * G;
+                        const int rbase = row0 + 16 * rt + 4 * Ge;
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             qcol[(rbase + r) * SQ] = acc[rt][0][r] * 0.25f;
@@ -304,13 +343,15 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
             ESTAMP(2);
             // ---- P2: attention of head cw (of this group), query tiles of this wave half -----------------------------
             {
+                int jp = j, Gp = G;            // as in P1's epilogue: P2's addresses are not carried through P1
+                asm volatile("" : "+v"(jp), "+v"(Gp));
                 // key on MFMA row rho of a key tile: 4 * (rho & 3) + (rho >> 2)  -> accumulator reg r of lane group G holds
                 // key 4 r + G, i.e. the B operand of value k-step r
-                const int pi = 4 * (j & 3) + (j >> 2);
+                const int pi = 4 * (jp & 3) + (jp >> 2);
                 float kf[RTT][4];
 #pragma unroll
                 for (int kt = 0; kt < RTT; ++kt) {
-                    const float* p = KB + (16 * kt + pi) * SQ + G * 16 + 4 * cw;
+                    const float* p = KB + (16 * kt + pi) * SQ + Gp * 16 + 4 * cw;
                     const float2 lo = *reinterpret_cast<const float2*>(p), hi = *reinterpret_cast<const float2*>(p + 2);
                     kf[kt][0] = lo.x; kf[kt][1] = lo.y; kf[kt][2] = hi.x; kf[kt][3] = hi.y;
                 }
@@ -318,10 +359,10 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
                 const int NT = (M + 3) >> 2;             // value k-steps (4 keys each)
                 constexpr int FULLT = RTT == 7 ? 4 : RTT == 4 ? 2 : 0;       // launch_fused: M > 64 / M > 32 / any
 #pragma unroll
-                for (int t = 0; t < 4 * RTT; ++t) vf[t] = (t < NT) ? VT[(16 * cw + j) * SV + 4 * t + G] : 0.0f;
+                for (int t = 0; t < 4 * RTT; ++t) vf[t] = (t < NT) ? VT[(16 * cw + jp) * SV + 4 * t + Gp] : 0.0f;
                 for (int q = 0; q < nrt; ++q) {
-                    const int qrow = row0 + 16 * q + j;
-                    const float* qp = QA + qrow * SQ + G * 16 + 4 * cw;
+                    const int qrow = row0 + 16 * q + jp;
+                    const float* qp = QA + qrow * SQ + Gp * 16 + 4 * cw;
                     const float2 qlo = *reinterpret_cast<const float2*>(qp), qhi = *reinterpret_cast<const float2*>(qp + 2);
                     f32x4 s[RTT];
                     float m = -INFINITY;
@@ -341,7 +382,7 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
                         if (kt >= FULLT && 16 * kt + 16 > M) {
 #pragma unroll
                             for (int r = 0; r < 4; ++r)
-                                if (16 * kt + 4 * r + G >= M) s[kt][r] = -INFINITY;
+                                if (16 * kt + 4 * r + Gp >= M) s[kt][r] = -INFINITY;
                         }
                         m = vmax5_raw(m, s[kt][0], s[kt][1], s[kt][2], s[kt][3]);      // two v_max3_f32, one asm statement
                     }
@@ -378,7 +419,7 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
                             for (int r = 0; r < 4; ++r) o = mfma4(vf[4 * kt + r], s[kt][r], o);
                         }
                     // o: lane (query j, G), reg r -> head column e = 4 G + r -> A layout (g = r, t = 4 cw + G); overwrites q
-                    float* op = QA + qrow * SQ + 4 * cw + G;
+                    float* op = QA + qrow * SQ + 4 * cw + Gp;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) op[r * 16] = o[r] / zp;
                 }
@@ -387,11 +428,26 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
             __syncthreads();
             ESTAMP(4);
             // ---- P3: out_proj partial over the 64 attention columns of this head group ------------------------------
-            gemm_pass<RTW, 2, SQ, false, RTT - RTA>(acc_o, QA + (row0 + j) * SQ + G * 16, nrt, wp3, 4, b3);
+            float2 a3[RTW][2];
+            load_a0<RTW, SQ>(a3, QA + (row0 + j) * SQ + G * 16, nrt);
+            if (hg == 0) {                     // P1 of head group 1 starts behind P3's barrier, which leaves h alone
+#pragma unroll
+                for (int x = 0; x < 3; ++x) wp1[x] += 4 * (FE / 16) * 256;
+                load_b0<3>(b1, wp1);
+                load_a0<RTW, SA>(a1, hrow, nrt);
+            }
+            gemm_pass<RTW, 2, SQ, 4, false, RTT - RTA>(acc_o, QA + (row0 + j) * SQ + G * 16, nrt, wp3, b3, a3);
             ESTAMP(5);
             __syncthreads();
             ESTAMP(6);
         }
+        // P4 of chunk 0: first weights now; its first A fragments are h1, which the barrier below publishes
+        const float* wp4[2];
+        float4 b4[2];
+        float2 a4[RTW][2];
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) wp4[ct] = Ly.W1 + ((int64_t)(2 * cw + ct) * (FE / 16)) * 256 + lane * 4;
+        load_b0<2>(b4, wp4);
         // ---- h1 = norm1(h + out_proj) -> HB ----------------------------------------------------------------------------
         residual_norm_store<RTW>(acc_o, HB, row0, nrt, cw, j, G, a.norm, CST + C_N1);
         __syncthreads();
@@ -399,6 +455,7 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
             instance_norm(L, M, a.eps, CST + C_N1);
             __syncthreads();
         }
+        load_a0<RTW, SA>(a4, hrow, nrt);
         ESTAMP(7);
         // ---- FFN: 4 chunks of 128 hidden units ---------------------------------------------------------------------------
         f32x4 acc_f[RTW][2];
@@ -416,11 +473,6 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
                 wp5[ct] = Ly.W2 + ((int64_t)(2 * cw + ct) * (FF / 16) + 8 * ch) * 256 + lane * 4;
             {   // P4: hidden chunk = relu(h1 W1_ch^T + b1) -> HID
                 f32x4 acc[RTW][2];
-                const float* wp[2];
-                float4 b0[2];
-#pragma unroll
-                for (int ct = 0; ct < 2; ++ct) wp[ct] = Ly.W1 + ((int64_t)(8 * ch + 2 * cw + ct) * (FE / 16)) * 256 + lane * 4;
-                load_b0<2>(b0, wp);
 #pragma unroll
                 for (int ct = 0; ct < 2; ++ct) {
                     const float b = CST[C_B1 + 16 * (8 * ch + 2 * cw + ct) + j];
@@ -428,7 +480,7 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
                     for (int rt = 0; rt < RTW; ++rt) acc[rt][ct] = splat4(b);
                 }
                 ESTAMP(14);
-                gemm_pass<RTW, 2, SA, false, RTT - RTA>(acc, HB + (row0 + j) * SA + G * GA, nrt, wp, FE / 16, b0);
+                gemm_pass<RTW, 2, SA, FE / 16, false, RTT - RTA>(acc, hrow, nrt, wp4, b4, a4);
                 ESTAMP(15);
                 load_b0<2>(b5, wp5);           // P5's first weights fly during the epilogue and the barrier
 #pragma unroll
@@ -450,7 +502,15 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
             __syncthreads();
             ESTAMP(9);
             // P5: ffn2 accumulators += hidden chunk x W2[:, 128 ch .. 128 ch + 127]^T
-            gemm_pass<RTW, 2, SA, false, RTT - RTA>(acc_f, HID + (row0 + j) * SA + G * GA, nrt, wp5, 8, b5);
+            float2 a5[RTW][2];
+            load_a0<RTW, SA>(a5, HID + (row0 + j) * SA + G * GA, nrt);
+            if (ch + 1 < FF / 128) {           // P4 of the next chunk starts behind P5's barrier, which leaves h1 alone
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct) wp4[ct] += 8 * (FE / 16) * 256;
+                load_b0<2>(b4, wp4);
+                load_a0<RTW, SA>(a4, hrow, nrt);
+            }
+            gemm_pass<RTW, 2, SA, 8, false, RTT - RTA>(acc_f, HID + (row0 + j) * SA + G * GA, nrt, wp5, b5, a5);
             ESTAMP(10);
             __syncthreads();
             ESTAMP(11);
@@ -486,7 +546,10 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
 #pragma unroll
                 for (int rt = 0; rt < RTW; ++rt) acc[rt][ct] = splat4(0.0f);
             if (lp) __syncthreads();               // every wave's part of L is in STG
-            gemm_pass<RTW, 2, SA, true, RTT - RTA>(acc, (lp ? STG : HB) + (row0 + j) * SA + G * GA, nrt, wp, FE / 16, b0);
+            const float* arow = (lp ? STG : HB) + (row0 + j) * SA + G * GA;
+            float2 a0[RTW][2];
+            load_a0<RTW, SA>(a0, arow, nrt);
+            gemm_pass<RTW, 2, SA, FE / 16, true, RTT - RTA>(acc, arow, nrt, wp, b0, a0);
             // transposed tiles: lane = node row0 + 16 rt + j, registers = output columns 32 cw + 16 ct + 4 G + (0..3)
 #pragma unroll
             for (int rt = 0; rt < RTW; ++rt)
