@@ -13,6 +13,7 @@
 // lane = column (512 B contiguous per node); K and Lp are read as float4 runs of 64 B / 128 B per
 // lane, consecutive lanes consecutive runs, so every fetched line is fully used.
 #include "kernels.hpp"
+#include "env_rule.hpp"
 
 namespace eamrl {
 
@@ -466,7 +467,7 @@ __device__ bool env_step_row(const DecArgs& a, const RowLds& l, uint8_t* vis, fl
         // PDPEnv._step (pdp/env.py:66-106): visit the node, open its partner (a + N/2) % (N + 1) -- the reference's modulo, which
         // for a delivery lands on the depot or a pickup, already open --, mask = unvisited and to deliver
         uint8_t* tdl = reinterpret_cast<uint8_t*>(rem);
-        const int64_t d = (act + (M - 1) / 2) % M;
+        const int64_t d = rule::pdp_partner(act, M);
         s.cur = act;
         if (tid == 0) { vis[act] = 1; tdl[d] = 1; }
         __syncthreads();
@@ -479,48 +480,42 @@ __device__ bool env_step_row(const DecArgs& a, const RowLds& l, uint8_t* vis, fl
         return __syncthreads_and(all_vis) != 0;
     } else if (ENV == EAMRL_ENV_SDVRP) {
         // SDVRPEnv._step + get_action_mask (sdvrp/env.py:58-92,137-146): deliver min(remaining demand, free capacity)
-        const float sel = rem[act];
-        const float free_cap = s.vcap - s.used;
-        const float delivered = sel < free_cap ? sel : free_cap;
-        s.used = (s.used + delivered) * (act != 0 ? 1.0f : 0.0f);
+        float left;
+        rule::sdvrp_deliver(rem[act], s.used, s.vcap, act == 0, s.used, left);
         s.cur = act;
         __syncthreads();  // everyone has read rem[act]
-        if (tid == 0) rem[act] = sel + (-delivered);
+        if (tid == 0) rem[act] = left;
         __syncthreads();
-        const bool full = s.used >= s.vcap;
+        const bool full = rule::sdvrp_full(s.used, s.vcap);
         int any_free = 0, any_rem = 0;
         for (int n = tid; n < M; n += BLOCK) {
             const float rv = rem[n];
-            any_rem |= rv > 0.0f;
+            any_rem |= rule::sdvrp_has_demand(rv);
             if (n >= 1) {
-                const int blocked = (rv == 0.0f) | full;
+                const int blocked = rule::sdvrp_blocked(rv, full);
                 l.msk[n] = !blocked;
                 any_free |= !blocked;
             }
         }
         any_free = __syncthreads_or(any_free);
         any_rem = __syncthreads_or(any_rem);
-        if (tid == 0) l.msk[0] = !((s.cur == 0) && any_free);
+        if (tid == 0) l.msk[0] = rule::depot_open(s.cur == 0, any_free != 0);
         return any_rem == 0;
     } else if (ENV == EAMRL_ENV_OP) {
         // OPEnv._step + get_action_mask (op/env.py:69-102,149-165); a.demand = per-node arrival limit, s.used = tour length
         const float* L = a.locs + (r % a.B) * (int64_t)M * 2;
         const float* ml = a.demand + (r % a.B) * (int64_t)M;
         const float cx = L[2 * act], cy = L[2 * act + 1];
-        {
-            const float dx = cx - L[2 * s.cur], dy = cy - L[2 * s.cur + 1];
-            s.used = s.used + __builtin_sqrtf(fma_(dy, dy, dx * dx));
-        }
-        const bool done = (act == 0) && (s.istep > 0);
+        s.used = s.used + rule::leg(cx, cy, L[2 * s.cur], L[2 * s.cur + 1]);
+        const bool done = rule::tour_ends(act == 0, s.istep);
         s.cur = act;
         s.istep += 1;
         if (tid == 0) vis[act] = 1;
         __syncthreads();
         const int v0 = vis[0] != 0;
         for (int n = 1 + tid; n < M; n += BLOCK) {
-            const float dx = L[2 * n] - cx, dy = L[2 * n + 1] - cy;
-            const int exceeds = (s.used + __builtin_sqrtf(fma_(dy, dy, dx * dx))) > ml[n];
-            l.msk[n] = !((vis[n] != 0) | v0 | exceeds);
+            const int over = rule::op_exceeds(s.used, rule::leg(L[2 * n], L[2 * n + 1], cx, cy), ml[n]);
+            l.msk[n] = !((vis[n] != 0) | v0 | over);
         }
         if (tid == 0) l.msk[0] = 1;
         return done;
@@ -528,7 +523,7 @@ __device__ bool env_step_row(const DecArgs& a, const RowLds& l, uint8_t* vis, fl
         // PCTSPEnv._step + get_action_mask (pctsp/env.py:64-97,156-163); a.demand = real_prize [B][M]
         const float* prize = a.demand + (r % a.B) * M;
         s.used = s.used + prize[act];
-        const bool done = (s.istep > 0) && (act == 0);
+        const bool done = rule::tour_ends(act == 0, s.istep);
         s.cur = act;
         s.istep += 1;
         if (tid == 0) vis[act] = 1;
@@ -541,7 +536,7 @@ __device__ bool env_step_row(const DecArgs& a, const RowLds& l, uint8_t* vis, fl
             unvisited |= !v;
         }
         unvisited = __syncthreads_or(unvisited);
-        if (tid == 0) l.msk[0] = !((s.used < 1.0f) && unvisited);
+        if (tid == 0) l.msk[0] = rule::pctsp_depot_open(s.used, unvisited != 0);
         return done;
     } else if (ENV == EAMRL_ENV_TSP) {
         if (s.istep == 0) s.first = act;
@@ -562,28 +557,23 @@ __device__ bool env_step_row(const DecArgs& a, const RowLds& l, uint8_t* vis, fl
         float cx = 0.0f, cy = 0.0f;
         if (TW) {
             cx = L[2 * act]; cy = L[2 * act + 1];
-            const float dx = L[2 * s.cur] - cx, dy = L[2 * s.cur + 1] - cy;
-            const float arrive = s.now + __builtin_sqrtf(fma_(dy, dy, dx * dx));
-            const float start = arrive > W[2 * act] ? arrive : W[2 * act];
-            s.now = (act != 0 ? 1.0f : 0.0f) * (start + a.dur[bi * (int64_t)M + act]);
+            s.now = rule::tw_clock_after(s.now, rule::leg(L[2 * s.cur], L[2 * s.cur + 1], cx, cy), W[2 * act],
+                                         a.dur[bi * (int64_t)M + act], act == 0);
         }
         int64_t di = act - 1;
         di = di < 0 ? 0 : (di > N - 1 ? N - 1 : di);
-        s.used = (s.used + dem[di]) * (act != 0 ? 1.0f : 0.0f);
+        s.used = rule::cvrp_load_after(s.used, dem[di], act == 0);
         s.cur = act;
         if (tid == 0) vis[act] = 1;
         __syncthreads();
-        const float lim = s.vcap + 1e-5f;
+        const float lim = rule::cvrp_limit(s.vcap);
         int any_free = 0, all_vis = vis[0] != 0;
         for (int j = tid; j < N; j += BLOCK) {
             const int v = vis[j + 1] != 0;
-            const float load = dem[j] + s.used;
-            const int blocked = v | (load > lim);
+            const int blocked = rule::cvrp_blocked(v, dem[j], s.used, lim);
             int ok = !blocked;
-            if (TW) {       // reachable before the window closes
-                const float dx = cx - L[2 * (j + 1)], dy = cy - L[2 * (j + 1) + 1];
-                ok &= (s.now + __builtin_sqrtf(fma_(dy, dy, dx * dx))) <= W[2 * (j + 1) + 1];
-            }
+            if (TW)         // reachable before the window closes
+                ok &= rule::tw_in_time(s.now, rule::leg(cx, cy, L[2 * (j + 1)], L[2 * (j + 1) + 1]), W[2 * (j + 1) + 1]);
             l.msk[j + 1] = ok;
             any_free |= !blocked;        // the depot rule looks at the CVRP mask only
             all_vis &= v;
@@ -591,11 +581,8 @@ __device__ bool env_step_row(const DecArgs& a, const RowLds& l, uint8_t* vis, fl
         any_free = __syncthreads_or(any_free);
         all_vis = __syncthreads_and(all_vis);
         if (tid == 0) {
-            int ok0 = !((s.cur == 0) && any_free);
-            if (TW) {
-                const float dx = cx - L[0], dy = cy - L[1];
-                ok0 &= (s.now + __builtin_sqrtf(fma_(dy, dy, dx * dx))) <= W[1];
-            }
+            int ok0 = rule::depot_open(s.cur == 0, any_free != 0);
+            if (TW) ok0 &= rule::tw_in_time(s.now, rule::leg(cx, cy, L[0], L[1]), W[1]);
             l.msk[0] = ok0;
         }
         return all_vis != 0;

@@ -10,7 +10,11 @@
 //
 // One 64-lane wavefront per row: the row's mask / visited bytes are read as one coalesced run, the
 // "any / all" reductions are wave ballots, and the tour length uses the canonical lane tree.
+// The step, mask and replay kernels walk the rows in this layout; the comparisons and transitions they apply (capacity
+// epsilon, window, prize, arrival limit, split delivery, end of a tour, the leg) are the functions of env_rule.hpp.
+// The k_check_* kernels restate check_solution_validity, whose own tolerances stay here.
 #include "kernels.hpp"
+#include "env_rule.hpp"
 
 namespace eamrl {
 
@@ -55,17 +59,16 @@ __device__ __forceinline__ void cvrp_step_mask_row(uint8_t* visited, float* used
         a = act;
         int64_t di = a - 1;
         di = di < 0 ? 0 : (di > N - 1 ? N - 1 : di);
-        u = (u + dem[di]) * (a != 0 ? 1.0f : 0.0f);
+        u = rule::cvrp_load_after(u, dem[di], a == 0);
         c = a;
     }
-    const float lim = vcap[rs] + 1e-5f;
+    const float lim = rule::cvrp_limit(vcap[rs]);
     int any_free = 0;
     int all_vis = 1;
     for (int j = lane; j < N; j += 64) {
         int v = vis[j + 1] != 0;
         if (STEP && j + 1 == a) { v = 1; vis[j + 1] = 1; }
-        const float load = dem[j] + u;
-        const int blocked = v | (load > lim);
+        const int blocked = rule::cvrp_blocked(v, dem[j], u, lim);
         mask[rs * M + 1 + j] = !blocked;
         any_free |= !blocked;
         all_vis &= v;
@@ -75,7 +78,7 @@ __device__ __forceinline__ void cvrp_step_mask_row(uint8_t* visited, float* used
     if (lane == 0) {
         int v0 = vis[0] != 0;
         if (STEP && a == 0) { v0 = 1; vis[0] = 1; }
-        mask[rs * M] = !((c == 0) && any);
+        mask[rs * M] = rule::depot_open(c == 0, any);
         if (STEP) {
             used[rs] = u;
             cur[rs] = c;
@@ -113,21 +116,17 @@ __global__ __launch_bounds__(EB) void k_sdvrp_step_mask(float* rem, float* used,
     if (STEP) {
         a = action[r];
         a = a < 0 ? 0 : (a > M - 1 ? M - 1 : a);     // an out-of-range action must not become an out-of-bounds access
-        const float sel = rr[a];
-        const float free_cap = cap - u;
-        const float delivered = sel < free_cap ? sel : free_cap;
-        u = (u + delivered) * (a != 0 ? 1.0f : 0.0f);
-        left = sel + (-delivered);
+        rule::sdvrp_deliver(rr[a], u, cap, a == 0, u, left);
         c = a;
     }
-    const bool full = u >= cap;
+    const bool full = rule::sdvrp_full(u, cap);
     int any_free = 0, any_rem = 0;
     for (int n = lane; n < M; n += 64) {
         float rv = rr[n];
         if (STEP && n == a) { rv = left; rr[n] = left; }
-        any_rem |= rv > 0.0f;
+        any_rem |= rule::sdvrp_has_demand(rv);
         if (n >= 1) {
-            const int blocked = (rv == 0.0f) | full;
+            const int blocked = rule::sdvrp_blocked(rv, full);
             mask[r * M + n] = !blocked;
             any_free |= !blocked;
         }
@@ -135,7 +134,7 @@ __global__ __launch_bounds__(EB) void k_sdvrp_step_mask(float* rem, float* used,
     const bool anyf = __ballot(any_free != 0) != 0ull;
     const bool anyr = __ballot(any_rem != 0) != 0ull;
     if (lane == 0) {
-        mask[r * M] = !((c == 0) && anyf);
+        mask[r * M] = rule::depot_open(c == 0, anyf);
         if (STEP) {
             used[r] = u;
             cur[r] = c;
@@ -189,13 +188,6 @@ __global__ __launch_bounds__(EB) void k_check_sdvrp(const int64_t* actions, cons
     if (twice) atomicAdd(&bad[1], 1);
 }
 
-// torch's norm(p=2, dim=-1) of a 2-vector on the CPU, bit for bit (OP): sqrtf(fmaf(dy, dy, dx * dx))
-__device__ __forceinline__ float dist2(float ax, float ay, float bx, float by)
-{
-    const float dx = ax - bx, dy = ay - by;
-    return __builtin_sqrtf(fma_(dy, dy, dx * dx));
-}
-
 // OP: one wavefront per row.  STEP = 0: mask only; STEP = 1: move (tour length += leg), mark visited, then mask.
 template <int STEP>
 __device__ __forceinline__ void op_step_mask_row(uint8_t* visited, float* tour_len, float* prize_tot, const float* prize,
@@ -213,7 +205,7 @@ __device__ __forceinline__ void op_step_mask_row(uint8_t* visited, float* tour_l
     if (STEP) {
         a = act;
         a = a < 0 ? 0 : (a > M - 1 ? M - 1 : a);     // an out-of-range action must not become an out-of-bounds access
-        tl = tl + dist2(L[2 * a], L[2 * a + 1], L[2 * c], L[2 * c + 1]);
+        tl = tl + rule::leg(L[2 * a], L[2 * a + 1], L[2 * c], L[2 * c + 1]);
         c = a;
         if (a == 0) v0 = 1;
     }
@@ -221,8 +213,8 @@ __device__ __forceinline__ void op_step_mask_row(uint8_t* visited, float* tour_l
     for (int n = 1 + lane; n < M; n += 64) {
         int v = vis[n] != 0;
         if (STEP && n == a) { v = 1; vis[n] = 1; }
-        const int exceeds = (tl + dist2(L[2 * n], L[2 * n + 1], cx, cy)) > ml[n];
-        mask[rs * M + n] = !(v | v0 | exceeds);
+        const int over = rule::op_exceeds(tl, rule::leg(L[2 * n], L[2 * n + 1], cx, cy), ml[n]);
+        mask[rs * M + n] = !(v | v0 | over);
     }
     if (lane == 0) {
         mask[rs * M] = 1;                             // the depot can always be visited
@@ -231,7 +223,7 @@ __device__ __forceinline__ void op_step_mask_row(uint8_t* visited, float* tour_l
             tour_len[rs] = tl;
             if (prize_tot) prize_tot[rs] = prize_tot[rs] + prize[bi * M + a];
             const int64_t i = istep[rs];
-            done[rs] = (a == 0 && i > 0) ? 1 : 0;
+            done[rs] = rule::tour_ends(a == 0, i) ? 1 : 0;
             cur[rs] = a;
             istep[rs] = i + 1;
         }
@@ -268,22 +260,21 @@ __device__ __forceinline__ void cvrptw_step_mask_row(uint8_t* visited, float* us
     if (STEP) {
         a = act;
         a = a < 0 ? 0 : (a > M - 1 ? M - 1 : a);     // an out-of-range action must not become an out-of-bounds access
-        const float arrive = now + dist2(L[2 * c], L[2 * c + 1], L[2 * a], L[2 * a + 1]);
-        const float start = arrive > W[2 * a] ? arrive : W[2 * a];
-        now = (a != 0 ? 1.0f : 0.0f) * (start + dur[bi * (int64_t)M + a]);
+        now = rule::tw_clock_after(now, rule::leg(L[2 * c], L[2 * c + 1], L[2 * a], L[2 * a + 1]), W[2 * a],
+                                   dur[bi * (int64_t)M + a], a == 0);
         int64_t di = a - 1;
         di = di < 0 ? 0 : (di > N - 1 ? N - 1 : di);
-        u = (u + dem[di]) * (a != 0 ? 1.0f : 0.0f);
+        u = rule::cvrp_load_after(u, dem[di], a == 0);
         c = a;
     }
     const float cx = L[2 * c], cy = L[2 * c + 1];
-    const float lim = vcap[rs] + 1e-5f;
+    const float lim = rule::cvrp_limit(vcap[rs]);
     int any_free = 0, all_vis = 1;
     for (int j = lane; j < N; j += 64) {
         int v = vis[j + 1] != 0;
         if (STEP && j + 1 == a) { v = 1; vis[j + 1] = 1; }
-        const int blocked = v | ((dem[j] + u) > lim);
-        const int in_time = (now + dist2(cx, cy, L[2 * (j + 1)], L[2 * (j + 1) + 1])) <= W[2 * (j + 1) + 1];
+        const int blocked = rule::cvrp_blocked(v, dem[j], u, lim);
+        const int in_time = rule::tw_in_time(now, rule::leg(cx, cy, L[2 * (j + 1)], L[2 * (j + 1) + 1]), W[2 * (j + 1) + 1]);
         mask[rs * M + 1 + j] = (!blocked) & in_time;
         any_free |= !blocked;                        // the depot rule looks at the CVRP mask only
         all_vis &= v;
@@ -293,8 +284,8 @@ __device__ __forceinline__ void cvrptw_step_mask_row(uint8_t* visited, float* us
     if (lane == 0) {
         int v0 = vis[0] != 0;
         if (STEP && a == 0) { v0 = 1; vis[0] = 1; }
-        const int in_time0 = (now + dist2(cx, cy, L[0], L[1])) <= W[1];
-        mask[rs * M] = (!((c == 0) && any)) & in_time0;
+        const int in_time0 = rule::tw_in_time(now, rule::leg(cx, cy, L[0], L[1]), W[1]);
+        mask[rs * M] = rule::depot_open(c == 0, any) & in_time0;
         if (STEP) {
             used[rs] = u;
             time[rs] = now;
@@ -330,7 +321,7 @@ __global__ void k_check_cvrptw_time(const int64_t* actions, const float* locs, c
     for (int t = 0; t < T; ++t) {
         const int64_t nx = actions[r * T + t];
         if (nx < 0 || nx >= M) { late = 1; break; }
-        int ct = (int)(curr + dist2(L[2 * node], L[2 * node + 1], L[2 * nx], L[2 * nx + 1]));
+        int ct = (int)(curr + rule::leg(L[2 * node], L[2 * node + 1], L[2 * nx], L[2 * nx + 1]));
         const int ws = (int)W[2 * nx];
         ct = ws > ct ? ws : ct;
         if ((float)ct > W[2 * nx + 1]) late = 1;
@@ -387,7 +378,7 @@ __global__ __launch_bounds__(EB) void k_check_op(const int64_t* actions, const f
                 if (atomicOr(&seen[a0 >> 5], bit) & bit) bad_lane = 1;
             }
             a1 = a1 < 0 ? 0 : (a1 >= M ? M - 1 : a1);
-            d = dist2(L[2 * a1], L[2 * a1 + 1], L[2 * a0], L[2 * a0 + 1]);
+            d = rule::leg(L[2 * a1], L[2 * a1 + 1], L[2 * a0], L[2 * a0 + 1]);
         }
         const float s = wave_tree_sum(d);
         length = (b0 == 0) ? s : length + s;
@@ -396,7 +387,7 @@ __global__ __launch_bounds__(EB) void k_check_op(const int64_t* actions, const f
     int ex = 0;
     const float* ml = maxlen + (r % B) * (int64_t)M;
     for (int n = lane; n < M; n += 64) {
-        const float lim = ((ml[n] + dist2(L[0], L[1], L[2 * n], L[2 * n + 1])) + 1e-6f) + 1e-5f;
+        const float lim = ((ml[n] + rule::leg(L[0], L[1], L[2 * n], L[2 * n + 1])) + 1e-6f) + 1e-5f;
         ex |= !(length <= lim);
     }
     const bool over = __ballot(ex != 0) != 0ull;
@@ -432,13 +423,13 @@ __device__ __forceinline__ void pctsp_step_mask_row(uint8_t* visited, float* pri
     }
     const bool unv = __ballot(unvisited != 0) != 0ull;
     if (lane == 0) {
-        mask[rs * M] = !((pt < 1.0f) && unv);
+        mask[rs * M] = rule::pctsp_depot_open(pt, unv);
         if (STEP) {
             if (a == 0) vis[0] = 1;
             prize_tot[rs] = pt;
             if (pen_tot) pen_tot[rs] = pen_tot[rs] + penalty[bi * M + a];
             const int64_t i = istep[rs];
-            done[rs] = (i > 0 && a == 0) ? 1 : 0;
+            done[rs] = rule::tour_ends(a == 0, i) ? 1 : 0;
             cur[rs] = a;
             istep[rs] = i + 1;
         }
@@ -765,11 +756,11 @@ __global__ __launch_bounds__(EB) void k_replay_sdvrp(const float* __restrict__ r
     int c = (int)cur[r];
     for (int t = 0; t < T; ++t) {
         // ---- record: mask (get_action_mask), current node, free capacity, the remaining demands -------------------------------
-        const bool full = u >= cap;
-        const bool ok0 = n0 >= 1 && n0 < M && !((r0 == 0.0f) | full), ok1 = n1 < M && !((r1 == 0.0f) | full);
+        const bool full = rule::sdvrp_full(u, cap);
+        const bool ok0 = n0 >= 1 && n0 < M && !rule::sdvrp_blocked(r0, full), ok1 = n1 < M && !rule::sdvrp_blocked(r1, full);
         unsigned long long b0 = __ballot(ok0), b1 = __ballot(ok1);
         const bool any_free = (b0 | b1) != 0ull;
-        if (!((c == 0) && any_free)) b0 |= 1ull;                         // the depot
+        if (rule::depot_open(c == 0, any_free)) b0 |= 1ull;                        // the depot
         const int64_t q = r * T + t;
         if (lane == 0) {
             *reinterpret_cast<uint4*>(bits + q * 4) = make_uint4((uint32_t)b0, (uint32_t)(b0 >> 32), (uint32_t)b1, (uint32_t)(b1 >> 32));
@@ -782,10 +773,8 @@ __global__ __launch_bounds__(EB) void k_replay_sdvrp(const float* __restrict__ r
         int a = __builtin_amdgcn_readfirstlane((int)actions[q]);
         a = a < 0 ? 0 : (a > M - 1 ? M - 1 : a);
         const float sel = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, a < 64 ? r0 : r1), a & 63));
-        const float free_cap = cap - u;
-        const float delivered = sel < free_cap ? sel : free_cap;
-        u = (u + delivered) * (a != 0 ? 1.0f : 0.0f);
-        const float left = sel + (-delivered);
+        float left;
+        rule::sdvrp_deliver(sel, u, cap, a == 0, u, left);
         if (n0 == a) r0 = left;
         if (n1 == a) r1 = left;
         c = a;
@@ -814,18 +803,18 @@ __global__ __launch_bounds__(EB) void k_replay_sdvrp_big(const float* __restrict
     int c = (int)cur[r];
     for (int t = 0; t < T; ++t) {
         const int64_t q = r * T + t;
-        const bool full = u >= cap;
+        const bool full = rule::sdvrp_full(u, cap);
         bool any_free = false;
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
             const int n = lane + 64 * k;
-            const bool ok = n >= 1 && n < M && !((rr[k] == 0.0f) | full);
+            const bool ok = n >= 1 && n < M && !rule::sdvrp_blocked(rr[k], full);
             s_ok[wv][n] = ok;
             any_free |= __ballot(ok) != 0ull;
             if (n < M) rem_out[(q * nkc + n / 112) * 128 + n % 112] = rr[k];
         }
         if (lane == 0) {
-            s_ok[wv][0] = !((c == 0) && any_free);                         // the depot
+            s_ok[wv][0] = rule::depot_open(c == 0, any_free);                        // the depot
             idxA[q] = c;
             sc[q] = cap - u;
         }
@@ -848,10 +837,8 @@ __global__ __launch_bounds__(EB) void k_replay_sdvrp_big(const float* __restrict
         for (int k = 0; k < 16; ++k)
             if ((a >> 6) == k) selv = rr[k];
         const float sel = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, selv), a & 63));
-        const float free_cap = cap - u;
-        const float delivered = sel < free_cap ? sel : free_cap;
-        u = (u + delivered) * (a != 0 ? 1.0f : 0.0f);
-        const float left = sel + (-delivered);
+        float left;
+        rule::sdvrp_deliver(sel, u, cap, a == 0, u, left);
 #pragma unroll
         for (int k = 0; k < 16; ++k)
             if (lane + 64 * k == a) rr[k] = left;

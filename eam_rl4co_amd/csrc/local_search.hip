@@ -23,7 +23,7 @@ namespace eamrl {
 
 enum { TWO_OPT_COORDS = 0, TWO_OPT_MATRIX_LDS = 1, TWO_OPT_MATRIX_GLOBAL = 2 };
 
-// the canonical leg (env_reward.hip dist2)
+// the canonical leg (env_rule.hpp rule::leg)
 __device__ __forceinline__ float leg2(float2 a, float2 b)
 {
     const float dx = a.x - b.x, dy = a.y - b.y;

@@ -8,6 +8,7 @@
 // two byte sets per row, visited (= !available) and to_deliver; a node is feasible iff it is unvisited and to deliver.
 // One 64-lane wavefront per row for the integer kernels, as in env_reward.hip.
 #include "kernels.hpp"
+#include "env_rule.hpp"
 
 namespace eamrl {
 
@@ -31,7 +32,7 @@ __global__ __launch_bounds__(PB) void k_pdp_step_mask(uint8_t* visited, uint8_t*
     if (STEP) {
         a = action[r];
         a = a < 0 ? 0 : (a > M - 1 ? M - 1 : a);      // an out-of-range action must not become an out-of-bounds access
-        d = (a + (M - 1) / 2) % M;
+        d = rule::pdp_partner(a, M);
     }
     int all_vis = 1;
     for (int n = lane; n < M; n += 64) {

@@ -24,6 +24,7 @@
 // Reference loop replaced: rl4co/models/common/constructive/base.py:236-250 with the multistart layout of
 // rl4co/utils/decoding.py:284-344 and rl4co/models/zoo/am/decoder.py:183-198 (K/V/L shared by the S queries of an instance).
 #include "kernels.hpp"
+#include "env_rule.hpp"
 
 namespace eamrl {
 
@@ -683,7 +684,12 @@ __global__ __launch_bounds__(512, 2) void k_rollout_ms_mfma(DecArgs a, int S, in
                 }
                 // ---- depot envs: the env's _step + get_action_mask (cvrp/env.py:68-144, cvrptw/env.py:103-138, pctsp/env.py:64-97,156-163,
                 // op/env.py:69-102,149-165; the expressions of k_rollout_resident's finish): every lane of the half-wavefront knows the
-                // pick, lane l tests nodes l, l + 32, l + 64, l + 96, the ballots are the new mask words ----------------------------------
+                // pick, lane l tests nodes l, l + 32, l + 64, l + 96, the ballots are the new mask words.  The comparisons and transitions
+                // are env_rule.hpp's.  Three lines stay written out and name the rule:: function they restate (the clock, the load, the
+                // depot's bit): their flag `sl == 0` as an argument shares one compare with the others, the run-time-chunk CVRPTW
+                // instantiation <7, 0> then spills 15 more SGPRs (697 -> 712), which takes a 12th lane-spill VGPR that the 256 do not
+                // have (5 VGPRs to scratch, reloaded in the step loop).  OP's test sits inside `cust &&` for the same kind of reason:
+                // as a named value before it the branch is flattened and the OP instantiations take 2-4 VGPRs more. --------------------------
                 if (DEP && live2) {
                     const int s = s2, sl = sel, hw = lane >> 5;
                     const float lpv = LPSEL[jq2];
@@ -703,38 +709,33 @@ __global__ __launch_bounds__(512, 2) void k_rollout_ms_mfma(DecArgs a, int S, in
                     float sd_left = 0.0f;
                     if (SD) {           // SDVRPEnv._step (sdvrp/env.py:58-92): deliver min(remaining demand, free capacity)
                         const float selrem = SREM[s * (16 * RTT) + rperm(sl)];
-                        const float free_cap = s_cap[s] - u;
-                        const float delivered = selrem < free_cap ? selrem : free_cap;
-                        u = (u + delivered) * (sl != 0 ? 1.0f : 0.0f);
-                        sd_left = selrem + (-delivered);
+                        rule::sdvrp_deliver(selrem, u, s_cap[s], sl == 0, u, sd_left);
                         done_new = false;       // (set from the remaining demands below)
                     } else if (OP) {
                         ist = s_istep[s];
-                        const float dx = cx - s_xy[2 * curn], dy = cy - s_xy[2 * curn + 1];
-                        u = u + __builtin_sqrtf(fma_(dy, dy, dx * dx));
-                        done_new = (sl == 0) && (ist > 0);
+                        u = u + rule::leg(cx, cy, s_xy[2 * curn], s_xy[2 * curn + 1]);
+                        done_new = rule::tour_ends(sl == 0, ist);
                     } else if (PC) {
                         ist = s_istep[s];
                         u = u + s_dem[sl];
-                        done_new = (ist > 0) && (sl == 0);
+                        done_new = rule::tour_ends(sl == 0, ist);
                         cnt += (sl != 0 && !was_vis);
                     } else {
-                        if (TW) {       // clock (cvrptw/env.py:118-138)
+                        if (TW) {       // clock (cvrptw/env.py:118-138): restates rule::tw_clock_after
                             now = s_time[s];
-                            const float dx = s_xy[2 * curn] - cx, dy = s_xy[2 * curn + 1] - cy;
-                            const float arrive = now + __builtin_sqrtf(fma_(dy, dy, dx * dx));
+                            const float arrive = now + rule::leg(s_xy[2 * curn], s_xy[2 * curn + 1], cx, cy);
                             const float ws = s_tw0[sl];
                             const float start = arrive > ws ? arrive : ws;
                             now = (sl != 0 ? 1.0f : 0.0f) * (start + s_dur[sl]);
                         }
                         int di = sl - 1;
                         di = di < 0 ? 0 : (di > M - 2 ? M - 2 : di);
-                        u = (u + s_dem[di + 1]) * (sl != 0 ? 1.0f : 0.0f);
+                        u = (u + s_dem[di + 1]) * (sl != 0 ? 1.0f : 0.0f);       // restates rule::cvrp_load_after
                         cnt += was_vis ? 0 : 1;
                         done_new = cnt == M;
                     }
                     const bool v0 = (vw.x & 1u) != 0;               // the depot has been visited (after this step)
-                    const float lim = s_cap[s] + 1e-5f;
+                    const float lim = rule::cvrp_limit(s_cap[s]);
                     uint32_t nb[4], fr = 0, anyrem = 0;
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
@@ -746,22 +747,17 @@ __global__ __launch_bounds__(512, 2) void k_rollout_ms_mfma(DecArgs a, int S, in
                         if (SD) {       // get_action_mask (sdvrp/env.py:137-146): nothing left to deliver there, or the vehicle is full
                             float rv = (n < 16 * RTT) ? SREM[s * (16 * RTT) + rperm(n)] : 0.0f;
                             rv = n == sl ? sd_left : rv;
-                            freeb = cust && !((rv == 0.0f) | (u >= s_cap[s]));
+                            freeb = cust && !rule::sdvrp_blocked(rv, rule::sdvrp_full(u, s_cap[s]));
                             ok = freeb;
-                            anyrem |= (uint32_t)(__ballot(n < M && rv > 0.0f) >> (32 * hw));
+                            anyrem |= (uint32_t)(__ballot(n < M && rule::sdvrp_has_demand(rv)) >> (32 * hw));
                         } else if (PC) {
                             ok = cust && !(vis_n | v0);
                         } else if (OP) {
-                            const float dx = s_xy[2 * n] - cx, dy = s_xy[2 * n + 1] - cy;
-                            const bool exceeds = (u + __builtin_sqrtf(fma_(dy, dy, dx * dx))) > s_dem[n];
-                            ok = cust && !(vis_n | v0 | exceeds);
+                            ok = cust && !(vis_n | v0 | rule::op_exceeds(u, rule::leg(s_xy[2 * n], s_xy[2 * n + 1], cx, cy), s_dem[n]));
                         } else {
-                            freeb = cust && !(vis_n | ((s_dem[n] + u) > lim));
+                            freeb = cust && !rule::cvrp_blocked(vis_n, s_dem[n], u, lim);
                             ok = freeb;
-                            if (TW) {
-                                const float dx = cx - s_xy[2 * n], dy = cy - s_xy[2 * n + 1];
-                                ok = ok && (now + __builtin_sqrtf(fma_(dy, dy, dx * dx))) <= s_tw1[n];
-                            }
+                            if (TW) ok = ok && rule::tw_in_time(now, rule::leg(cx, cy, s_xy[2 * n], s_xy[2 * n + 1]), s_tw1[n]);
                         }
                         nb[k] = (uint32_t)(__ballot(ok) >> (32 * hw));
                         if (CV || SD) fr |= (uint32_t)(__ballot(freeb) >> (32 * hw));
@@ -769,15 +765,12 @@ __global__ __launch_bounds__(512, 2) void k_rollout_ms_mfma(DecArgs a, int S, in
                     if (SD) done_new = anyrem == 0u;            // done = no demand left anywhere (sdvrp/env.py:84-86)
                     // the depot's bit
                     if (PC) {
-                        if (!((u < 1.0f) && (cnt < M - 1))) nb[0] |= 1u;     // opens once the prize is collected (or everyone visited)
+                        if (rule::pctsp_depot_open(u, cnt < M - 1)) nb[0] |= 1u;    // opens once the prize is collected (or everyone visited)
                     } else if (OP) {
                         nb[0] |= 1u;                                          // always feasible (and ends the episode)
                     } else {
-                        bool ok0 = !((sl == 0) && fr != 0u);                  // closed only while at it with customers left
-                        if (TW) {
-                            const float dx = cx - s_xy[0], dy = cy - s_xy[1];
-                            ok0 = ok0 && (now + __builtin_sqrtf(fma_(dy, dy, dx * dx))) <= s_tw1[0];
-                        }
+                        bool ok0 = !((sl == 0) && fr != 0u);                  // restates rule::depot_open
+                        if (TW) ok0 = ok0 && rule::tw_in_time(now, rule::leg(cx, cy, s_xy[0], s_xy[1]), s_tw1[0]);
                         if (ok0) nb[0] |= 1u;
                     }
                     if (l32 == 0) {

@@ -25,6 +25,7 @@
 // rl4co/models/zoo/am/decoder.py:161-198, rl4co/models/nn/attention.py:282-328,
 // rl4co/utils/decoding.py:140-190,346-465 and rl4co/envs/routing/{tsp,cvrp,sdvrp}/env.py step functions.
 #include "kernels.hpp"
+#include "env_rule.hpp"
 
 namespace eamrl {
 
@@ -577,11 +578,8 @@ __global__ __launch_bounds__(RB, 2) void k_rollout_resident(DecArgs a, int S, in
             } else if (OP) {
                 // OPEnv._step + get_action_mask (op/env.py:69-102,149-165)
                 const float cx = l.xy[2 * sel], cy = l.xy[2 * sel + 1];
-                {
-                    const float dx = cx - l.xy[2 * cur], dy = cy - l.xy[2 * cur + 1];
-                    used = used + __builtin_sqrtf(fma_(dy, dy, dx * dx));
-                }
-                done = (sel == 0) && (istep > 0);
+                used = used + rule::leg(cx, cy, l.xy[2 * cur], l.xy[2 * cur + 1]);
+                done = rule::tour_ends(sel == 0, istep);
                 cur = sel;
                 istep += 1;
                 __builtin_amdgcn_wave_barrier();
@@ -594,16 +592,15 @@ __global__ __launch_bounds__(RB, 2) void k_rollout_resident(DecArgs a, int S, in
                 for (int k = 0; k < 2; ++k) {
                     const int nn = lane + 64 * k;
                     if (nn >= 1 && nn < M) {
-                        const float dx = l.xy[2 * nn] - cx, dy = l.xy[2 * nn + 1] - cy;
-                        const int exceeds = (used + __builtin_sqrtf(fma_(dy, dy, dx * dx))) > l.dem[nn];
-                        l.msk[nn] = !((l.vis[nn] != 0) | v0 | exceeds);
+                        const int over = rule::op_exceeds(used, rule::leg(l.xy[2 * nn], l.xy[2 * nn + 1], cx, cy), l.dem[nn]);
+                        l.msk[nn] = !((l.vis[nn] != 0) | v0 | over);
                     }
                 }
                 if (lane == 0) l.msk[0] = 1;
             } else if (PC) {
                 // PCTSPEnv._step + get_action_mask (pctsp/env.py:64-97,156-163)
                 used = used + l.dem[sel];
-                done = (istep > 0) && (sel == 0);
+                done = rule::tour_ends(sel == 0, istep);
                 cur = sel;
                 istep += 1;
                 count += (sel != 0 && l.vis[sel] == 0);
@@ -619,11 +616,11 @@ __global__ __launch_bounds__(RB, 2) void k_rollout_resident(DecArgs a, int S, in
                     const int nn = lane + 64 * k;
                     if (nn >= 1 && nn < M) l.msk[nn] = !((l.vis[nn] != 0) | v0);
                 }
-                if (lane == 0) l.msk[0] = !((used < 1.0f) && (count < M - 1));
+                if (lane == 0) l.msk[0] = rule::pctsp_depot_open(used, count < M - 1);
             } else if (PD) {
                 // PDPEnv._step (pdp/env.py:66-106): visit the node, open its partner (sel + N/2) % (N + 1) -- the reference's modulo,
                 // which for a delivery lands on the depot or a pickup, already open --, mask = unvisited and to deliver
-                const int d = (sel + (M - 1) / 2) % M;
+                const int d = rule::pdp_partner(sel, M);
                 cur = sel;
                 if (sel < 64) pvis[0] |= 1ull << sel; else pvis[1] |= 1ull << (sel - 64);
                 if (d < 64) ptd[0] |= 1ull << d; else ptd[1] |= 1ull << (d - 64);
@@ -639,26 +636,24 @@ __global__ __launch_bounds__(RB, 2) void k_rollout_resident(DecArgs a, int S, in
             } else if (SD) {
                 // SDVRPEnv._step + get_action_mask (sdvrp/env.py:58-92,137-146): deliver min(remaining demand, free capacity)
                 const float selrem = l.dem[sel];
-                const float free_cap = vcap - used;
-                const float delivered = selrem < free_cap ? selrem : free_cap;
-                used = (used + delivered) * (sel != 0 ? 1.0f : 0.0f);
+                float left;
+                rule::sdvrp_deliver(selrem, used, vcap, sel == 0, used, left);
                 cur = sel;
-                const float left = selrem + (-delivered);
                 __builtin_amdgcn_wave_barrier();
                 if (lane == 0) l.dem[sel] = left;
                 __builtin_amdgcn_wave_barrier();
 #pragma unroll
                 for (int k = 0; k < 2; ++k) l.q[lane + 64 * k] = fma_(cv[k], vcap - used, Plds[cur * RE + lane + 64 * k]) + gq[k];
-                const bool full = used >= vcap;
+                const bool full = rule::sdvrp_full(used, vcap);
                 int free_n = 0, rem_n = 0;
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
                     const int nn = lane + 64 * k;
                     if (nn < M) {
                         const float rv = l.dem[nn];
-                        rem_n |= rv > 0.0f;
+                        rem_n |= rule::sdvrp_has_demand(rv);
                         if (nn >= 1) {
-                            const int blocked = (rv == 0.0f) | full;
+                            const int blocked = rule::sdvrp_blocked(rv, full);
                             l.msk[nn] = !blocked;
                             free_n |= !blocked;
                         }
@@ -666,21 +661,19 @@ __global__ __launch_bounds__(RB, 2) void k_rollout_resident(DecArgs a, int S, in
                 }
                 const bool any_free = __ballot(free_n) != 0ull;
                 done = __ballot(rem_n) == 0ull;
+                // restates rule::depot_open: through the call the CP = CR = 8 and 16 instantiations take one VGPR more (207 -> 208, 239 -> 240)
                 if (lane == 0) { l.msk[0] = !((cur == 0) && any_free); l.done = done; }
             } else {
                 const int N = M - 1;
                 float cx = 0.0f, cy = 0.0f;
                 if (TW) {       // clock (cvrptw/env.py:118-138)
                     cx = l.xy[2 * sel]; cy = l.xy[2 * sel + 1];
-                    const float dx = l.xy[2 * cur] - cx, dy = l.xy[2 * cur + 1] - cy;
-                    const float arrive = now + __builtin_sqrtf(fma_(dy, dy, dx * dx));
-                    const float ws = l.twv[sel];
-                    const float start = arrive > ws ? arrive : ws;
-                    now = (sel != 0 ? 1.0f : 0.0f) * (start + l.twv[2 * RNP + sel]);
+                    now = rule::tw_clock_after(now, rule::leg(l.xy[2 * cur], l.xy[2 * cur + 1], cx, cy), l.twv[sel],
+                                               l.twv[2 * RNP + sel], sel == 0);
                 }
                 int di = sel - 1;
                 di = di < 0 ? 0 : (di > N - 1 ? N - 1 : di);
-                used = (used + l.dem[di]) * (sel != 0 ? 1.0f : 0.0f);
+                used = rule::cvrp_load_after(used, l.dem[di], sel == 0);
                 cur = sel;
                 count += (l.vis[sel] == 0);
                 done = (count == M);
@@ -693,29 +686,23 @@ __global__ __launch_bounds__(RB, 2) void k_rollout_resident(DecArgs a, int S, in
                     if (TW) qv = fma_(cv2[k], now, qv);
                     l.q[lane + 64 * k] = qv + gq[k];
                 }
-                const float lim = vcap + 1e-5f;
+                const float lim = rule::cvrp_limit(vcap);
                 int free_n = 0;
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
                     const int nn = lane + 64 * k;
                     if (nn >= 1 && nn < M) {
-                        const int blocked = (l.vis[nn] != 0) | ((mydem[k] + used) > lim);
+                        const int blocked = rule::cvrp_blocked(l.vis[nn] != 0, mydem[k], used, lim);
                         int ok = !blocked;
-                        if (TW) {
-                            const float dx = cx - l.xy[2 * nn], dy = cy - l.xy[2 * nn + 1];
-                            ok &= (now + __builtin_sqrtf(fma_(dy, dy, dx * dx))) <= l.twv[RNP + nn];
-                        }
+                        if (TW) ok &= rule::tw_in_time(now, rule::leg(cx, cy, l.xy[2 * nn], l.xy[2 * nn + 1]), l.twv[RNP + nn]);
                         l.msk[nn] = ok;
                         free_n |= !blocked;
                     }
                 }
                 const bool any_free = __ballot(free_n) != 0ull;
                 if (lane == 0) {
-                    int ok0 = !((cur == 0) && any_free);
-                    if (TW) {
-                        const float dx = cx - l.xy[0], dy = cy - l.xy[1];
-                        ok0 &= (now + __builtin_sqrtf(fma_(dy, dy, dx * dx))) <= l.twv[RNP];
-                    }
+                    int ok0 = rule::depot_open(cur == 0, any_free);
+                    if (TW) ok0 &= rule::tw_in_time(now, rule::leg(cx, cy, l.xy[0], l.xy[1]), l.twv[RNP]);
                     l.msk[0] = ok0;
                 }
             }
