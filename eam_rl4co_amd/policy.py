@@ -994,7 +994,9 @@ class AttentionModelPolicy(nn.Module):
                                                     td["demand"].contiguous() if self.env_name == "cvrp" else None,
                                                     st.vcap, bad=bad)
         elif fast:
-            if calc_reward:
+            # a one-step episode (max_steps = 1, or one given column) of PCTSP / OP is the reference's "length 1 tours"
+            # special case, which lives in the env classes: `_finish` then asks env.get_reward on the exact slice
+            if calc_reward and not (actions_pad.shape[1] == 1 and self.env_name in ("pctsp", "op")):
                 spec = ENV_SPECS[self.env_name]
                 reward_pad = ops.call_spec(spec.reward, td, actions_pad)
                 if env.check_solution and spec.check_padded != "no":        # "no": checked in _finish, on the exact slice

@@ -691,13 +691,14 @@ def write_npz(path, arrays):
 
 
 def load_groups(path):
-    """-> list of group dicts of a validity_<env>.npz (also used by the tests)."""
+    """-> list of group dicts of a validity_<env>.npz or reward_<env>.npz (also used by the tests)."""
     with np.load(path) as z:
         n = int(z["groups"].reshape(-1)[0])
         groups = [{k[len(f"g{i}_"):]: z[k] for k in z.files if k.startswith(f"g{i}_")} for i in range(n)]
     for g in groups:
         for k in ("actions", "inst", "verdict"):
-            g[k] = g[k].astype(np.int64)
+            if k in g:
+                g[k] = g[k].astype(np.int64)
     return groups
 
 
