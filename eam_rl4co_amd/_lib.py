@@ -94,6 +94,10 @@ PROTOTYPES = {
     "eamrl_mha_encoder": [_vp, _vp, _i64, _i32, _i32, _i32, _vp],
     "eamrl_mha_encoder_backward_supported": [_i32, _i32, _i32],
     "eamrl_mha_encoder_backward": [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp],
+    "eamrl_hetero_mha_supported": [_i32, _i32, _i32],
+    "eamrl_hetero_mha": [_vp, _vp, _i64, _i32, _i32, _i32, _vp],
+    "eamrl_hetero_mha_backward_supported": [_i32, _i32, _i32],
+    "eamrl_hetero_mha_backward": [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp],
     "eamrl_normalize": [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp],
     "eamrl_batchnorm_train": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _i64, _vp],
     "eamrl_pointer_attention": [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp],

@@ -264,6 +264,35 @@ __attribute__((visibility("default"))) int eamrl_linear_wgrad(const float* dy, i
                     "eamrl_linear_wgrad");
 }
 
+__attribute__((visibility("default"))) int eamrl_hetero_mha_supported(int M, int E, int H)
+{
+    return hetero_mha_supports(M, E, H) ? 1 : 0;
+}
+
+__attribute__((visibility("default"))) int eamrl_hetero_mha(const float* proj, float* out, int64_t B, int M, int E, int H,
+                                                           void* stream)
+{
+    REQUIRE(proj && out && B >= 0 && B <= 0x0fffffff, "eamrl_hetero_mha");
+    REQUIRE(hetero_mha_supports(M, E, H), "eamrl_hetero_mha");
+    REQUIRE((uintptr_t)proj % 16 == 0 && (uintptr_t)out % 16 == 0, "eamrl_hetero_mha");
+    if (B == 0) return 0;
+    return launched(launch_hetero_mha(proj, out, B, M, (hipStream_t)stream), "eamrl_hetero_mha");
+}
+
+__attribute__((visibility("default"))) int eamrl_hetero_mha_backward_supported(int M, int E, int H)
+{
+    return hetero_mha_bwd_supports(M, E, H) ? 1 : 0;
+}
+
+__attribute__((visibility("default"))) int eamrl_hetero_mha_backward(const float* proj, const float* dout, float* dproj, int64_t B,
+                                                                    int M, int E, int H, void* stream)
+{
+    REQUIRE(proj && dout && dproj && B >= 0 && B <= 0x0fffffff, "eamrl_hetero_mha_backward");
+    REQUIRE(hetero_mha_bwd_supports(M, E, H), "eamrl_hetero_mha_backward");
+    if (B == 0) return 0;
+    return launched(launch_hetero_mha_bwd(proj, dout, dproj, B, M, (hipStream_t)stream), "eamrl_hetero_mha_backward");
+}
+
 __attribute__((visibility("default"))) int eamrl_mha_encoder(const float* qkv, float* out, int64_t B, int N, int E, int H,
                                                             void* stream)
 {

@@ -429,16 +429,22 @@ constexpr int DPP_XOR1 = 0xB1, DPP_XOR2 = 0x4E, DPP_HALF_MIRROR = 0x141, DPP_MIR
 // Sum over the 64 lanes of a wavefront as an adjacent-pair tree (xor butterfly); every lane gets the
 // total.  This is the "lane tree" of the canonical order: level w adds the partial sums of lane groups
 // [i, i+w) and [i+w, i+2w).
+// The last two levels on their own: the sum over the four 16-lane groups (lanes l, l^16, l^32, l^48), (G0 + G1) + (G2 + G3).
+// The MFMA attention kernels reduce with it over the lane groups that share a query row.
+__device__ __forceinline__ float lane_groups_sum(float v)
+{
+    auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    return __uint_as_float(s[0]) + __uint_as_float(s[1]);
+}
 __device__ __forceinline__ float wave_tree_sum(float v)
 {
     v = v + dpp_f<DPP_XOR1>(v);
     v = v + dpp_f<DPP_XOR2>(v);
     v = v + dpp_f<DPP_HALF_MIRROR>(v);
     v = v + dpp_f<DPP_MIRROR>(v);
-    auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-    auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(s[0]) + __uint_as_float(s[1]);
+    return lane_groups_sum(v);
 }
 
 // max(a, b) as the single v_max_f32 it is (the builtin adds two canonicalising v_max x,x per call)
@@ -467,16 +473,21 @@ __device__ __forceinline__ float vmax5_raw(float m, float v0, float v1, float v2
 // after the VALU write of its source (the compiler does not see hazards inside inline asm)
 #define EAMRL_MAX_DPP(v, ctrl) asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 " ctrl " row_mask:0xf bank_mask:0xf" : "=v"(v) : "v"(v))
 
+// the maximum over the four 16-lane groups (lanes l, l^16, l^32, l^48), as lane_groups_sum
+__device__ __forceinline__ float lane_groups_max(float v)
+{
+    auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    v = vmax_raw(__uint_as_float(r[0]), __uint_as_float(r[1]));
+    auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    return vmax_raw(__uint_as_float(s[0]), __uint_as_float(s[1]));
+}
 __device__ __forceinline__ float wave_max(float v)
 {
     EAMRL_MAX_DPP(v, "quad_perm:[1,0,3,2]");
     EAMRL_MAX_DPP(v, "quad_perm:[2,3,0,1]");
     EAMRL_MAX_DPP(v, "row_half_mirror");
     EAMRL_MAX_DPP(v, "row_mirror");
-    auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = vmax_raw(__uint_as_float(r[0]), __uint_as_float(r[1]));
-    auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return vmax_raw(__uint_as_float(s[0]), __uint_as_float(s[1]));
+    return lane_groups_max(v);
 }
 
 // argmax with torch.argmax's tie rule (lowest index); every lane gets the winner.

@@ -103,12 +103,7 @@ __global__ __launch_bounds__(512, 2) void k_mha_encoder_mfma(const float* __rest
 #pragma unroll
             for (int u = 0; u < 4; ++u) m = vmax3_raw(m, vmax_raw(s[u][0], s[u][1]), vmax_raw(s[u][2], s[u][3]));
         }
-        {   // the four lane groups G share a query: max over lanes l, l^16, l^32, l^48
-            auto r16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(m), __float_as_uint(m), false, false);
-            m = vmax_raw(__uint_as_float(r16[0]), __uint_as_float(r16[1]));
-            auto r32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
-            m = vmax_raw(__uint_as_float(r32[0]), __uint_as_float(r32[1]));
-        }
+        m = lane_groups_max(m);                         // the four lane groups G share a query: lanes l, l^16, l^32, l^48
         // ---- pass 2: weights, Z partial (this lane's keys are one residue class mod 4, ascending), value product ------------------
         f32x4 o = (f32x4){0.f, 0.f, 0.f, 0.f};
         float zp = 0.0f;
@@ -129,12 +124,7 @@ __global__ __launch_bounds__(512, 2) void k_mha_encoder_mfma(const float* __rest
                 }
             }
         }
-        {   // (P0 + P1) + (P2 + P3) over the lane groups
-            auto r16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(zp), __float_as_uint(zp), false, false);
-            zp = __uint_as_float(r16[0]) + __uint_as_float(r16[1]);
-            auto r32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(zp), __float_as_uint(zp), false, false);
-            zp = __uint_as_float(r32[0]) + __uint_as_float(r32[1]);
-        }
+        zp = lane_groups_sum(zp);                       // (P0 + P1) + (P2 + P3) over the lane groups
         // o: lane (query j, G), register r -> head column 4 G + r
         if (qrow < N)
             *reinterpret_cast<float4*>(out + (b * N + qrow) * (int64_t)E + h * D + 4 * G) =

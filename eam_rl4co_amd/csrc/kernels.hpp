@@ -42,6 +42,11 @@ int launch_augment_xy(const float* xy, const float* cs, const int32_t* code, flo
                       hipStream_t st);
 bool mha_encoder_mfma_supports(int N, int E, int H);
 int launch_mha_encoder_mfma(const float* qkv, float* out, int64_t B, int N, int E, int H, hipStream_t st);
+// heterogeneous attention of the HAM encoder (hetero_attn.hip)
+bool hetero_mha_supports(int M, int E, int H);
+int launch_hetero_mha(const float* proj, float* out, int64_t B, int M, hipStream_t st);
+bool hetero_mha_bwd_supports(int M, int E, int H);
+int launch_hetero_mha_bwd(const float* proj, const float* dout, float* dproj, int64_t B, int M, hipStream_t st);
 bool encoder_fused_supports(int M, int E, int H, int FFdim, int nlayers);
 // dtype DTYPE_F32: k_encoder_fused (encoder_fused.hip); EAMRL_DTYPE_F16 / EAMRL_DTYPE_BF16: the opt-in 16-bit k_encoder_fused16
 // (encoder_fused16.hip), whose packed weights come from launch_pack_mfma_b16

@@ -227,6 +227,50 @@ def mha_encoder_backward(qkv, dout, num_heads):
     return dqkv
 
 
+# the text of HeterogenousMHA.forward's assertion on an even graph size (zoo/ham/attention.py:69-72: a continued string literal)
+ODD_NODES_MESSAGE = ("Graph size should have odd number of nodes due to pickup-delivery problem  " + " " * 37
+                     + "(n/2 pickup, n/2 delivery, 1 depot)")
+
+
+def hetero_mha_supported(M: int, E: int, H: int) -> bool:
+    return bool(_lib.load().eamrl_hetero_mha_supported(int(M), int(E), int(H)))
+
+
+def _hetero_proj_shape(proj, what):
+    """(B, M, E) of a packed HAM projection [B, M, 6E] on the GPU; an even M raises the reference's assertion."""
+    _chk(proj, "proj", torch.float32)
+    if proj.dim() != 3 or proj.shape[2] % 6:
+        raise ValueError(f"{what}: proj must be [B, M, 6E], got {tuple(proj.shape)}")
+    B, M, E6 = proj.shape
+    assert M % 2 == 1, ODD_NODES_MESSAGE
+    return B, M, E6 // 6
+
+
+def hetero_mha(proj, num_heads):
+    """The heads [B, M, E] of the HAM encoder's heterogeneous attention for proj [B, M, 6E] = q | k | v | qpair | qsame |
+    qother (eamrl_hetero_mha); M = 2P + 1 nodes: depot, P pickups, P deliveries."""
+    lib = _lib.load()
+    B, M, E = _hetero_proj_shape(proj, "hetero_mha")
+    out = torch.empty(B, M, E, device=proj.device, dtype=torch.float32)
+    _lib.check(lib.eamrl_hetero_mha(_ptr(proj), _ptr(out), B, M, E, num_heads, _stream(proj)), "eamrl_hetero_mha")
+    return out
+
+
+def hetero_mha_backward_supported(M: int, E: int, H: int) -> bool:
+    return bool(_lib.load().eamrl_hetero_mha_backward_supported(int(M), int(E), int(H)))
+
+
+def hetero_mha_backward(proj, dout, num_heads):
+    """dproj [B, M, 6E] of hetero_mha(proj) for the output gradient dout [B, M, E] (eamrl_hetero_mha_backward)."""
+    lib = _lib.load()
+    B, M, E = _hetero_proj_shape(proj, "hetero_mha_backward")
+    _chk(dout, "dout", torch.float32, (B, M, E))
+    dproj = torch.empty_like(proj)
+    _lib.check(lib.eamrl_hetero_mha_backward(_ptr(proj), _ptr(dout), _ptr(dproj), B, M, E, num_heads, _stream(proj)),
+               "eamrl_hetero_mha_backward")
+    return dproj
+
+
 def normalize_(x, kind, gamma, beta, mean=None, var=None, eps=1e-5):
     lib = _lib.load()
     _chk(x, "x", torch.float32)

@@ -387,6 +387,154 @@ class AttentionModelEncoder(nn.Module):
         return h, init_h
 
 
+# ------------------------------------------------------------------------------------------------------------
+# Heterogeneous Attention Model (HAM) encoder for pickup and delivery (zoo/ham/{attention,encoder,policy}.py)
+# ------------------------------------------------------------------------------------------------------------
+class HeterogenousMHA(nn.Module):
+    """Parameters of the reference's HeterogenousMHA (zoo/ham/attention.py:7-51, its spelling): W_query, W_key, W_val and the
+    six role queries W1..W6 as [H, E, D], W_out as [H, D, E], no biases, the reference's uniform(+-1/sqrt(last dim)) init.
+    `forward` is projections (eamrl_linear on the packed weights), eamrl_hetero_mha, W_out."""
+
+    def __init__(self, num_heads, input_dim, embed_dim=None, val_dim=None, key_dim=None):
+        super().__init__()
+        if val_dim is None and embed_dim is None:
+            raise ValueError("HeterogenousMHA: give embed_dim (head width = embed_dim // num_heads) or val_dim")
+        head = embed_dim // num_heads if val_dim is None else val_dim
+        key_dim = head if key_dim is None else key_dim
+        if embed_dim != input_dim or key_dim != head or num_heads * head != input_dim:
+            raise NotImplementedError("HeterogenousMHA: only embed_dim = input_dim = num_heads * key_dim (= val_dim) is built "
+                                      "for MI355X (the HAM encoder's configuration)")
+        self.num_heads, self.input_dim, self.embed_dim, self.val_dim, self.key_dim = num_heads, input_dim, embed_dim, head, key_dim
+        self.norm_factor = key_dim ** -0.5
+        for name in ("W_query", "W_key", "W_val", "W1_query", "W2_query", "W3_query", "W4_query", "W5_query", "W6_query"):
+            setattr(self, name, nn.Parameter(torch.empty(num_heads, input_dim, key_dim)))
+        self.W_out = nn.Parameter(torch.empty(num_heads, key_dim, embed_dim))
+        self.init_parameters()
+
+    def init_parameters(self):
+        """Uniform in +-1/sqrt(last dimension), the reference's distribution.  Through nn.init, so that the version counters
+        move and `packed()` sees a later re-initialisation."""
+        with torch.no_grad():
+            for w in self.parameters():
+                nn.init.uniform_(w, -w.shape[-1] ** -0.5, w.shape[-1] ** -0.5)
+
+    PACKS = (("qkv", ("W_query", "W_key", "W_val")), ("pick", ("W1_query", "W2_query", "W3_query")),
+             ("deliv", ("W4_query", "W5_query", "W6_query")))
+
+    def packed(self):
+        """{"qkv", "pick", "deliv": [3E, E] Linear weights ([(h d), E] per projection, stacked), "out": [E, E] = W_out.view(H D,
+        E) transposed}: persistent buffers, repacked IN PLACE when a parameter's (data_ptr, _version) changes (a captured HIP
+        graph keeps reading them), as GraphAttentionNetwork._fused_layers keeps its packs."""
+        slots = self.__dict__.setdefault("_packed", {})
+        E = self.input_dim
+        out = {}
+        for name, keys in self.PACKS + (("out", ("W_out",)),):
+            ws = [getattr(self, k) for k in keys]
+            key = tuple((w.data_ptr(), w._version, w.device) for w in ws)
+            slot = slots.get(name)
+            if slot is None or slot[0] != key:
+                with torch.no_grad():
+                    if name == "out":
+                        new = ws[0].detach().reshape(-1, self.embed_dim).t()                    # [E, (h d)]
+                    else:
+                        new = torch.cat([w.detach().permute(0, 2, 1).reshape(-1, E) for w in ws], 0)      # [3 (h d), E]
+                    if slot is not None and slot[1].device == new.device and slot[1].shape == new.shape:
+                        slot[1].copy_(new)
+                        slots[name] = slot = (key, slot[1])
+                    else:
+                        slots[name] = slot = (key, new.contiguous())
+            out[name] = slot[1]
+        return out
+
+    def project(self, h):
+        """proj [B, M, 6E] = q | k | v | qpair | qsame | qother by three GEMMs: all nodes on the stacked W_query | W_key | W_val,
+        the pickups on W1 | W2 | W3, the deliveries on W4 | W5 | W6.  The role rows of a batch have no single row stride, so
+        they are gathered role-major ([2, B, P, E], one copy) and the role queries scattered back (one copy).  The depot's last
+        3E stay unwritten: the kernel never reads them."""
+        B, M, E = h.shape
+        assert M % 2 == 1, ops.ODD_NODES_MESSAGE
+        assert E == self.input_dim, "Wrong embedding dimension of input"
+        P = (M - 1) // 2
+        w = self.packed()
+        proj = torch.empty(B, M, 6 * E, device=h.device, dtype=torch.float32)
+        ops.linear(h, w["qkv"], out=proj.view(B * M, 6 * E)[:, 0:3 * E])
+        if B * P:
+            roles = h[:, 1:].view(B, 2, P, E).permute(1, 0, 2, 3).contiguous()                  # [2, B, P, E]
+            extra = torch.empty(2, B, P, 3 * E, device=h.device, dtype=torch.float32)
+            ops.linear(roles[0], w["pick"], out=extra[0])
+            ops.linear(roles[1], w["deliv"], out=extra[1])
+            proj[:, 1:, 3 * E:].view(B, 2, P, 3 * E).copy_(extra.permute(1, 0, 2, 3))
+        return proj
+
+    def forward(self, q, h=None, mask=None):
+        if h is not None or mask is not None:
+            raise NotImplementedError("HeterogenousMHA: self-attention without a mask only (what the HAM encoder calls)")
+        att = ops.hetero_mha(self.project(q.contiguous()), self.num_heads)
+        return ops.linear(att, self.packed()["out"])
+
+
+class HeterogeneuousMHALayer(nn.Sequential):
+    """[SkipConnection(HeterogenousMHA), Normalization, SkipConnection(FFN), Normalization] (zoo/ham/encoder.py:8-29, its
+    spelling).  The FFN is an nn.Sequential(Linear, ReLU, Linear) holder so that the keys are `.2.module.0.*` / `.2.module.2.*`."""
+
+    def __init__(self, num_heads, embed_dim, feedforward_hidden=512, normalization="batch"):
+        super().__init__(
+            _Holder(HeterogenousMHA(num_heads, embed_dim, embed_dim)),
+            Normalization(embed_dim, normalization),
+            _Holder(nn.Sequential(nn.Linear(embed_dim, feedforward_hidden), nn.ReLU(), nn.Linear(feedforward_hidden, embed_dim))
+                    if feedforward_hidden > 0 else nn.Linear(embed_dim, embed_dim)),
+            Normalization(embed_dim, normalization),
+        )
+
+    def forward(self, h):
+        mha, ffn = self[0].module, self[2].module
+        att = ops.hetero_mha(mha.project(h), mha.num_heads)
+        bn1, bn2 = self[1].fused_bn(), self[3].fused_bn()
+        h = ops.linear(att, mha.packed()["out"], None, residual=h, bn=bn1)                 # norm(h + MHA(h))
+        if bn1 is None:
+            h = self[1].apply_(h)
+        if isinstance(ffn, nn.Linear):
+            return self._finish(ops.linear(h, ffn.weight, ffn.bias, residual=h, bn=bn2), bn2)
+        x = ops.linear(h, ffn[0].weight, ffn[0].bias, relu=True)
+        return self._finish(ops.linear(x, ffn[2].weight, ffn[2].bias, residual=h, bn=bn2), bn2)     # norm(h + FFN(h))
+
+    def _finish(self, h, bn2):
+        return h if bn2 is not None else self[3].apply_(h)
+
+
+class GraphHeterogeneousAttentionEncoder(nn.Module):
+    """zoo/ham/encoder.py:32-73: init embedding + HeterogeneuousMHALayer x num_encoder_layers -> (embeddings, init embeddings)."""
+
+    def __init__(self, init_embedding=None, num_heads=8, embed_dim=128, num_encoder_layers=3, env_name=None,
+                 normalization="batch", feedforward_hidden=512, sdpa_fn=None):
+        super().__init__()
+        if sdpa_fn is not None:
+            raise NotImplementedError("sdpa_fn injection is outside the MI355X rollout path")
+        env_name = "pdp" if env_name is None else _kind(env_name)
+        if init_embedding is None:
+            if env_name != "pdp":
+                raise NotImplementedError(f"GraphHeterogeneousAttentionEncoder: env_name={env_name!r}; the heterogeneous attention "
+                                          "is defined for pickup and delivery ('pdp')")
+            init_embedding = PDPInitEmbedding(embed_dim)
+        self.env_name = env_name
+        self.init_embedding = init_embedding
+        self.layers = nn.Sequential(*(HeterogeneuousMHALayer(num_heads, embed_dim, feedforward_hidden, normalization)
+                                      for _ in range(num_encoder_layers)))
+
+    def forward(self, x, mask=None):
+        assert mask is None, "Mask not yet supported!"
+        init_embeds = self.init_embedding(x)
+        h = init_embeds
+        for layer in self.layers:
+            h = layer(h)
+        return h, init_embeds
+
+    def refresh_packs(self):
+        """Repack weights that changed into the buffers a captured graph reads (GraphedRollout)."""
+        for layer in self.layers:
+            layer[0].module.packed()
+
+
 class _ContextParams(nn.Module):
     def __init__(self, embed_dim, step_context_dim, placeholder):
         super().__init__()
@@ -1220,6 +1368,23 @@ class AttentionModelPolicy(nn.Module):
         return acts, lps, alls, t, int(status.item())
 
 
+class HeterogeneousAttentionModelPolicy(AttentionModelPolicy):
+    """Heterogeneous Attention Model (Li et al. 2021) for pickup and delivery: Kool's model with the encoder whose attention
+    also scores a node's partner, the nodes of its own role and those of the other role (zoo/ham/policy.py:9-62, same
+    constructor arguments).  Decoder, context, cache, env and reward are AttentionModelPolicy's for PDP."""
+
+    def __init__(self, encoder: nn.Module = None, env_name: str = "pdp", init_embedding: nn.Module = None, embed_dim: int = 128,
+                 num_encoder_layers: int = 3, num_heads: int = 8, normalization: str = "batch", feedforward_hidden: int = 512,
+                 sdpa_fn=None, **kwargs):
+        if encoder is None:
+            encoder = GraphHeterogeneousAttentionEncoder(init_embedding=init_embedding, num_heads=num_heads, embed_dim=embed_dim,
+                                                         num_encoder_layers=num_encoder_layers, env_name=env_name,
+                                                         normalization=normalization, feedforward_hidden=feedforward_hidden,
+                                                         sdpa_fn=sdpa_fn)
+        super().__init__(env_name=env_name, encoder=encoder, embed_dim=embed_dim, num_encoder_layers=num_encoder_layers,
+                         num_heads=num_heads, normalization=normalization, **kwargs)
+
+
 def load_reference_checkpoint(policy: AttentionModelPolicy, ckpt, strict: bool = True):
     """Load the policy weights of a reference Lightning checkpoint.
 
@@ -1374,6 +1539,9 @@ class GraphedRollout:
             net = getattr(self.policy.encoder, "net", None)
             if hasattr(net, "_fused_layers"):
                 net._fused_layers(self._embed_probe)          # re-packs changed encoder weights into the buffers the graph reads
+            refresh = getattr(self.policy.encoder, "refresh_packs", None)
+            if refresh is not None:
+                refresh()
         pairs = []
         for k in self._keys:
             src = td[k]

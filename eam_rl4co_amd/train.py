@@ -246,8 +246,98 @@ def init_embedding_autograd(policy, td):
     return h
 
 
+class _HeteroAttentionFn(torch.autograd.Function):
+    """The HAM encoder's heterogeneous attention on the packed projection proj [B, M, 6E] (q | k | v | qpair | qsame | qother):
+    forward eamrl_hetero_mha (the rollout's kernel), backward eamrl_hetero_mha_backward, which recomputes the softmax from proj
+    -- nothing but proj is kept."""
+
+    @staticmethod
+    def forward(ctx, proj, num_heads):
+        from . import ops
+
+        p = proj.contiguous()
+        ctx.save_for_backward(p)
+        ctx.H = num_heads
+        return ops.hetero_mha(p, num_heads)
+
+    @staticmethod
+    def backward(ctx, dout):
+        from . import ops
+
+        (p,) = ctx.saved_tensors
+        return ops.hetero_mha_backward(p, dout.contiguous(), ctx.H), None
+
+
+def hetero_attention_torch(proj, H):
+    """The same as a torch expression (zoo/ham/attention.py:227-479 restated on the shared k and v): depot 0, pickups 1..P,
+    deliveries P+1..2P; a non-depot row's general, pair, same-role and other-role scores under one softmax.  The cross-check of
+    the kernels (EAMRL_TORCH_ATTENTION=1) and the path of graphs above the native backward's bound."""
+    B, M, E6 = proj.shape
+    E = E6 // 6
+    D, P = E // H, (M - 1) // 2
+    c = 1.0 / math.sqrt(D)
+    q, k, v, qp, qs, qo = (proj[..., i * E:(i + 1) * E].reshape(B, M, H, D).permute(0, 2, 1, 3) for i in range(6))
+    idx = torch.arange(M, device=proj.device)
+    role = (idx > 0).long() + (idx > P).long()
+    partner = torch.where(role == 1, idx + P, torch.where(role == 2, idx - P, idx))
+    nd = role != 0
+    ninf = torch.full((), float("-inf"), dtype=proj.dtype, device=proj.device)
+    zero = torch.zeros((), dtype=proj.dtype, device=proj.device)
+    kt = k.transpose(-1, -2)
+    s_gen = c * (q @ kt)
+    s_pair = torch.where(nd, c * (torch.where(nd[:, None], qp, zero) * k[:, :, partner]).sum(-1), ninf)
+    s_x = torch.where(role[:, None] == role[None, :], c * (torch.where(nd[:, None], qs, zero) @ kt),
+                      c * (torch.where(nd[:, None], qo, zero) @ kt))
+    s_x = torch.where(nd[:, None] & nd[None, :], s_x, ninf)
+    a = torch.softmax(torch.cat((s_gen, s_x, s_pair[..., None]), -1), -1)
+    heads = (a[..., :M] + a[..., M:2 * M]) @ v + a[..., 2 * M:] * v[:, :, partner]
+    return heads.permute(0, 2, 1, 3).reshape(B, M, E)
+
+
+def _hetero_attention(proj, H):
+    """proj [B, M, 6E] -> [B, M, E]"""
+    from . import ops
+
+    B, M, E6 = proj.shape
+    if (proj.is_cuda and proj.dtype == torch.float32 and os.environ.get("EAMRL_TORCH_ATTENTION", "0") != "1"
+            and ops.hetero_mha_backward_supported(M, E6 // 6, H)):
+        return _HeteroAttentionFn.apply(proj, H)
+    return hetero_attention_torch(proj, H)
+
+
+def _encode_autograd_ham(policy, td):
+    """The HAM encoder (policy.GraphHeterogeneousAttentionEncoder) of the training graph: the [H, E, D] weights are packed into
+    Linear weights inside the graph (their gradients come back through the reshapes), the GEMMs, the attention and the norms
+    run on this library's kernels where they apply."""
+    enc = policy.encoder
+    h = init_embedding_autograd(policy, td)
+    training = policy.training
+    for layer in enc.layers:
+        mha, ffn = layer[0].module, layer[2].module
+        B, M, E = h.shape
+        assert M % 2 == 1, "Graph size should have odd number of nodes"
+        P = (M - 1) // 2
+        pack = lambda names: torch.cat([getattr(mha, n).permute(0, 2, 1).reshape(-1, E) for n in names], 0)
+        qkv = _linear(h, pack(("W_query", "W_key", "W_val")))
+        pick = _linear(h[:, 1:P + 1].contiguous(), pack(("W1_query", "W2_query", "W3_query")))
+        deliv = _linear(h[:, P + 1:].contiguous(), pack(("W4_query", "W5_query", "W6_query")))
+        proj = torch.cat((qkv, torch.cat((qkv.new_zeros(B, 1, 3 * E), pick, deliv), 1)), -1)
+        att = _hetero_attention(proj, mha.num_heads)
+        h = _normalize(layer[1], _linear(att, mha.W_out.reshape(-1, mha.embed_dim).t().contiguous(), residual=h), training)
+        if isinstance(ffn, nn.Linear):
+            x = _linear(h, ffn.weight, ffn.bias, residual=h)
+        else:
+            x = _linear(_linear(h, ffn[0].weight, ffn[0].bias, relu=True), ffn[2].weight, ffn[2].bias, residual=h)
+        h = _normalize(layer[3], x, training)
+    return h
+
+
 def encode_autograd(policy, td):
     enc = policy.encoder
+    from .policy import GraphHeterogeneousAttentionEncoder
+
+    if isinstance(enc, GraphHeterogeneousAttentionEncoder):
+        return _encode_autograd_ham(policy, td)
     h = init_embedding_autograd(policy, td)
     training = policy.training
     for layer in enc.net.layers:

@@ -218,6 +218,27 @@ int eamrl_mha_encoder(const float* qkv, float* out, int64_t B, int N, int E, int
 int eamrl_mha_encoder_backward_supported(int N, int E, int H);
 int eamrl_mha_encoder_backward(const float* qkv, const float* dout, float* dqkv, int64_t B, int N, int E, int H, void* stream);
 
+/* Heterogeneous multi-head attention of the HAM encoder for pickup and delivery, between the projections and W_out
+ * [zoo/ham/attention.py:53-488 HeterogenousMHA.forward: lines 99-201 are the projections the caller makes, 227-414 the score
+ * groups, 421-479 the one softmax and the value products this call replaces; 481-486 (W_out) is the caller's again].
+ * proj [B][M][6E] = q | k | v | qpair | qsame | qother, each "(h d)": all nodes take q, k, v from W_query, W_key, W_val; a pickup
+ * takes the three extra queries from W1, W2, W3, a delivery from W4, W5, W6; the depot's last 3E are never read.  M = 2P + 1
+ * nodes: depot 0, pickups 1..P, deliveries P+1..2P.  out [B][M][E]: the heads "(h d)" before W_out.
+ * E = 128, H = 8, odd 3 <= M <= EAMRL_HETERO_MHA_MAX_NODES (eamrl_hetero_mha_supported).  fp32 MFMA; no atomics: two runs give
+ * the same bits, and an instance's result does not depend on the batch.  proj and out 16-byte aligned. */
+#define EAMRL_HETERO_MHA_MAX_NODES 513
+int eamrl_hetero_mha_supported(int M, int E, int H);
+int eamrl_hetero_mha(const float* proj, float* out, int64_t B, int M, int E, int H, void* stream);
+
+/* Gradient of eamrl_hetero_mha for the training graph [HeterogenousMHA.forward under loss.backward()]: proj as given to the
+ * forward, dout [B][M][E] -> dproj [B][M][6E] (every element written; the depot's dqpair | dqsame | dqother are zeros).  The
+ * softmax is recomputed from proj, nothing else is kept.  dk and dv are summed over the rows in ascending order: no
+ * floating-point atomics.  E = 128, H = 8, odd 3 <= M <= EAMRL_HETERO_MHA_BWD_MAX_NODES
+ * (eamrl_hetero_mha_backward_supported). */
+#define EAMRL_HETERO_MHA_BWD_MAX_NODES 129
+int eamrl_hetero_mha_backward_supported(int M, int E, int H);
+int eamrl_hetero_mha_backward(const float* proj, const float* dout, float* dproj, int64_t B, int M, int E, int H, void* stream);
+
 /* Normalization.forward in place on x [B][N][E]  [nn/ops.py:32-56].
  * BATCH_EVAL uses running stats (mean, var); INSTANCE ignores them (may be NULL). */
 int eamrl_normalize(float* x, int64_t B, int N, int E, int kind, const float* gamma, const float* beta,
