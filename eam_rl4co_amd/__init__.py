@@ -3,9 +3,10 @@
 from .envs import (CVRPEnv, CVRPGenerator, CVRPTWEnv, CVRPTWGenerator, OPEnv, OPGenerator, PCTSPEnv, PCTSPGenerator, PDPEnv, PDPGenerator, RL4COEnvBase, SDVRPEnv, SPCTSPEnv,  # noqa: F401
                    TSPEnv, TSPGenerator, get_env)  # noqa: F401
 from .policy import (AttentionModelDecoder, AttentionModelEncoder, AttentionModelPolicy, GraphedRollout,  # noqa: F401
-                     GraphHeterogeneousAttentionEncoder, HeterogeneousAttentionModelPolicy, SymNCOPolicy,
+                     GraphHeterogeneousAttentionEncoder, HeterogeneousAttentionModelPolicy, PolyNetDecoder, PolyNetPolicy,
+                     SymNCOPolicy,
                      load_reference_checkpoint, random_policy, rollout)
-from .attention import PointerAttention, scaled_dot_product_attention  # noqa: F401
+from .attention import PointerAttention, PolyNetAttention, scaled_dot_product_attention  # noqa: F401
 from .evolution import EA, EACvrpDraws, EAPrizeDraws, EADraws, evolution_worker, generate_batch_population  # noqa: F401
 from .search import EAS, EASEmb, EASLay, eas_loss_coefficients  # noqa: F401
 from .tensordict_lite import TensorDict  # noqa: F401

@@ -56,6 +56,12 @@ class Reeval(C.Structure):
                 ("mc_part_o", _vp), ("mc_part_s", _vp), ("mc_gstat", _vp), ("mc_lpart", _vp), ("mc_rsq", _vp), ("mc_dq", _vp)]
 
 
+class PolyNet(C.Structure):
+    """struct eamrl_polynet"""
+    _fields_ = [("Wout", _vp), ("W1", _vp), ("ctab", _vp), ("W2", _vp), ("b2", _vp), ("L", _vp),
+                ("k", C.c_int32), ("P", C.c_int32), ("s_offset", C.c_int32)]
+
+
 class State(C.Structure):
     """struct eamrl_state"""
     _fields_ = [("first", _vp), ("cur", _vp), ("istep", _vp), ("used", _vp), ("vcap", _vp), ("demand", _vp),
@@ -128,6 +134,11 @@ PROTOTYPES = {
     "eamrl_rollout_kernel": [_i32, C.POINTER(Cache), _i64, _i32, _i32, C.c_double],
     "eamrl_am_rollout_seeded": [_i32, C.POINTER(Cache), C.POINTER(State), _i64, C.c_uint64, _vp, _vp, _f32, _f32, _i32,
                                 _vp, _vp, _vp, _vp, _vp],
+    "eamrl_rollout_polynet_supported": [_i32, C.POINTER(Cache), _i64],
+    "eamrl_am_rollout_polynet": [_i32, C.POINTER(Cache), C.POINTER(State), C.POINTER(PolyNet), _i64, _i32, _vp, _vp, _i32, _f32,
+                                 _f32, _i32, _vp, _vp, _vp, _vp, _vp],
+    "eamrl_am_rollout_polynet_seeded": [_i32, C.POINTER(Cache), C.POINTER(State), C.POINTER(PolyNet), _i64, C.c_uint64, _vp, _f32,
+                                        _f32, _i32, _vp, _vp, _vp, _vp, _vp],
     "eamrl_tour_length": [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp],
     "eamrl_sum_logp": [_vp, _i64, _vp, _i64, _i32, _vp],
     "eamrl_tsp_two_opt": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp],

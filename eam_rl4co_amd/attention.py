@@ -13,6 +13,9 @@ call into the HIP path through the seams the reference offers.
 """
 from __future__ import annotations
 
+import itertools
+import math
+
 import torch
 import torch.nn as nn
 
@@ -39,6 +42,30 @@ class PointerAttention(nn.Module):
         if self.check_nan:
             assert not torch.isnan(logits).any(), "Logits contain NaNs"
         return logits
+
+
+class PolyNetAttention(PointerAttention):
+    """The pointer of PolyNet (Hottung et al. 2024; rl4co/models/nn/attention.py:476-555): between project_out and the logits the
+    glimpse goes through a two-layer MLP conditioned on one of k binary vectors, y = g + W2 relu(W1 [g ; z_j] + b1) -- one
+    strategy per solution of an instance (solution s uses j = s % k).  Same constructor, parameter names and state-dict keys as
+    the reference (`binary_vectors` is a non-trainable Parameter there too).  The layers run inside the rollout kernel
+    (PolyNetPolicy); as a stand-alone per-step module it is not built."""
+
+    def __init__(self, k: int, embed_dim: int, poly_layer_dim: int, num_heads: int, **kwargs):
+        super().__init__(embed_dim, num_heads, **kwargs)
+        if k < 1:
+            raise ValueError("PolyNetAttention: k must be at least 1")
+        self.k = k
+        self.binary_vector_dim = math.ceil(math.log2(k))
+        self.binary_vectors = nn.Parameter(
+            torch.tensor(list(itertools.product([0, 1], repeat=self.binary_vector_dim))[:k], dtype=torch.float32).reshape(
+                k, self.binary_vector_dim), requires_grad=False)
+        self.poly_layer_1 = nn.Linear(embed_dim + self.binary_vector_dim, poly_layer_dim)
+        self.poly_layer_2 = nn.Linear(poly_layer_dim, embed_dim)
+
+    def forward(self, query, key, value, logit_key, attn_mask=None):
+        raise NotImplementedError("PolyNetAttention computes its logits inside PolyNetPolicy's one-launch rollout; a stand-alone "
+                                  "per-step call is not built for MI355X")
 
 
 @torch.no_grad()

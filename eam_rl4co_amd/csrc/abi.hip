@@ -793,6 +793,98 @@ __attribute__((visibility("default"))) int eamrl_am_rollout_seeded(int env, cons
                             0.0, t_max, actions, logps, steps_out, status, stream);
 }
 
+// PolyNet rollouts (PolyNetAttention.forward, nn/attention.py:519-556, inside the decode loop of constructive/base.py:236-250).
+static bool polynet_shape_ok(int env, const eamrl_cache* c, int64_t R)
+{
+    if (env != EAMRL_ENV_TSP && env != EAMRL_ENV_CVRP) return false;
+    if (c->B <= 0 || R <= 0 || R % c->B != 0 || R > 0x7fffffffLL || R / c->B < 2) return false;
+    DecArgs a{};
+    a.B = c->B; a.M = c->M; a.E = c->E; a.H = c->H; a.ld = c->ld;
+    a.R = (R / c->B > 128 ? 128 : R / c->B) * c->B;         // the first launch (later ones differ in their number of solutions only)
+    return rollout_ms_poly_supports(env, a, true);
+}
+
+static int polynet_rollout(const char* what, int env, const eamrl_cache* cache_host, const eamrl_state* state_host,
+                           const eamrl_polynet* poly, int64_t R, int mode, const float* noise, const int64_t* given, int t_given,
+                           float tanh_clip, float temperature, int t_max, int64_t* actions, float* logps, int32_t* steps_out,
+                           uint32_t* status, bool seeded, uint64_t seed, const uint64_t* seed_dev, void* stream)
+{
+    DecArgs a;
+    int rc = fill_args(what, env, cache_host, state_host, R, mode, noise, given, tanh_clip, temperature, 0, 0.0, status, a, seeded);
+    if (rc) return rc;
+    REQUIRE(poly != nullptr, what);
+    REQUIRE(poly->Wout && poly->W1 && poly->ctab && poly->W2 && poly->b2 && poly->L, what);
+    REQUIRE(((uintptr_t)poly->Wout % 16 == 0) && ((uintptr_t)poly->W1 % 16 == 0) && ((uintptr_t)poly->ctab % 16 == 0) &&
+            ((uintptr_t)poly->W2 % 16 == 0) && ((uintptr_t)poly->b2 % 16 == 0) && ((uintptr_t)poly->L % 16 == 0), what);
+    REQUIRE(poly->P == 256 && poly->k >= 1 && poly->k <= (1 << 20) && poly->s_offset >= 0, what);
+    REQUIRE(polynet_shape_ok(env, cache_host, R), what);
+    const int64_t B = a.B, S = R / B;
+    REQUIRE(((int64_t)poly->s_offset + S) * B <= 0x7fffffffLL, what);
+    REQUIRE(actions && logps && steps_out && a.done && t_max > 0 && a.heads_out == nullptr, what);
+    if (env == EAMRL_ENV_CVRP) REQUIRE(a.visited && a.demand, what);
+    if (mode == EAMRL_EVALUATE) REQUIRE(t_given > 0, what);
+    a.fuse_env = 1; a.t_max = t_max; a.t_given = t_given;
+    a.steps_out = steps_out;
+    a.Lp = poly->L;
+    if (seeded) { a.seed = seed; a.seed_dev = seed_dev; a.use_rng = 1; }
+    {
+        DecArgs f = a;
+        f.R = (S > 128 ? 128 : S) * B;
+        REQUIRE(rollout_ms_poly_supports(env, f, false), what);
+    }
+    const int M = a.M;
+    for (int64_t s0 = 0; s0 < S; s0 += 128) {
+        const int64_t Sc = S - s0 < 128 ? S - s0 : 128, r0 = s0 * B;
+        DecArgs c = a;
+        c.R = Sc * B;
+        if (a.first) c.first = a.first + r0;
+        c.cur = a.cur + r0;
+        if (a.istep) c.istep = a.istep + r0;
+        if (a.used) c.used = a.used + r0;
+        if (a.vcap) c.vcap = a.vcap + r0;
+        c.mask = a.mask + r0 * M;
+        if (a.visited) c.visited = a.visited + r0 * M;
+        c.done = a.done + r0;
+        if (noise) c.noise = noise + r0 * t_max * M;
+        if (given) c.given = given + r0 * t_given;
+        c.action = actions + r0 * t_max;
+        c.logp = logps + r0 * t_max;
+        const PolyArgs pn{poly->Wout, poly->W1, poly->ctab, poly->W2, poly->b2, poly->k, (int)(poly->s_offset + s0)};
+        rc = launch_rollout_ms_poly(env, c, pn, (hipStream_t)stream);
+        if (rc) return launched(rc, what);
+    }
+    return 0;
+}
+
+__attribute__((visibility("default"))) int eamrl_rollout_polynet_supported(int env, const eamrl_cache* cache_host, int64_t R)
+{
+    if (!cache_host || g_debug[11]) return 0;
+    return polynet_shape_ok(env, cache_host, R) ? 1 : 0;
+}
+
+__attribute__((visibility("default"))) int eamrl_am_rollout_polynet(int env, const eamrl_cache* cache_host,
+                                                                   const eamrl_state* state_host, const eamrl_polynet* poly,
+                                                                   int64_t R, int mode, const float* noise,
+                                                                   const int64_t* given, int t_given, float tanh_clip,
+                                                                   float temperature, int t_max, int64_t* actions, float* logps,
+                                                                   int32_t* steps_out, uint32_t* status, void* stream)
+{
+    return polynet_rollout("eamrl_am_rollout_polynet", env, cache_host, state_host, poly, R, mode, noise, given, t_given, tanh_clip,
+                           temperature, t_max, actions, logps, steps_out, status, false, 0, nullptr, stream);
+}
+
+__attribute__((visibility("default"))) int eamrl_am_rollout_polynet_seeded(int env, const eamrl_cache* cache_host,
+                                                                          const eamrl_state* state_host,
+                                                                          const eamrl_polynet* poly, int64_t R, uint64_t seed,
+                                                                          const uint64_t* seed_dev, float tanh_clip,
+                                                                          float temperature, int t_max, int64_t* actions,
+                                                                          float* logps, int32_t* steps_out, uint32_t* status,
+                                                                          void* stream)
+{
+    return polynet_rollout("eamrl_am_rollout_polynet_seeded", env, cache_host, state_host, poly, R, EAMRL_SAMPLE, nullptr, nullptr,
+                           0, tanh_clip, temperature, t_max, actions, logps, steps_out, status, true, seed, seed_dev, stream);
+}
+
 __attribute__((visibility("default"))) int eamrl_tour_length(const float* locs, const int64_t* actions, float* reward,
                                                             int64_t R, int64_t B, int M, int T, int with_depot,
                                                             void* stream)

@@ -136,6 +136,10 @@ int launch_rollout_resident(int env, const DecArgs& a, hipStream_t st);
 bool rollout_resident_supports(int env, const DecArgs& a);
 bool rollout_ms_mfma_supports(int env, const DecArgs& a, bool shape_only = false);
 int launch_rollout_ms_mfma(int env, const DecArgs& a, hipStream_t st);
+// PolyNet case of the start-sharing kernel (rollout_multistart.hip): the operands of eamrl_polynet, by value
+struct PolyArgs { const float* Wout; const float* W1; const float* ctab; const float* W2; const float* b2; int k; int s_off; };
+bool rollout_ms_poly_supports(int env, const DecArgs& a, bool shape_only = false);
+int launch_rollout_ms_poly(int env, const DecArgs& a, const PolyArgs& pn, hipStream_t st);
 int launch_exp1_noise(uint64_t seed, const uint64_t* seed_dev, float* noise, int64_t R, int T, int M, hipStream_t st);
 // elites of EA.run's elitism_selection: int(selection_rate * pop.shape[0]), and idx[-0:] is everything; pairs = elites / 2
 inline int ea_num_elites(double selection_rate, int S)

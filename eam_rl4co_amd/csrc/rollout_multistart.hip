@@ -45,6 +45,8 @@ namespace {
 constexpr int ME = 128, MH = 8;
 constexpr int TS = 140, TG = 34;      // A-layout tile buffers [16][TS]: element (j, c) at j * TS + (c & 3) * TG + (c >> 2)
 constexpr int SMAX = 128;             // starts per instance
+constexpr int PD = 256;               // PolyNet: poly_layer_dim
+constexpr int TS2 = 268, TG2 = 66;    // ... its hidden tile [16][TS2]: element (j, c) at j * TS2 + (c & 3) * TG2 + (c >> 2)
 
 __device__ __forceinline__ f32x4 mf(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ f32x4 z4() { return (f32x4){0.f, 0.f, 0.f, 0.f}; }
@@ -118,14 +120,43 @@ __device__ __forceinline__ int half_min(int v)
     return min((int)r[0], (int)r[1]);
 }
 
+// PolyNet weight stream: a piece = PQ consecutive 16-byte A-fragment loads of one row tile (fragment order, eamrl_polynet)
+constexpr int PQ = 4;
+__device__ __forceinline__ void w_load(f32x4 (&dst)[PQ], const float* W, int piece, int lane)
+{
+    const f32x4* wp = reinterpret_cast<const f32x4*>(W) + piece * (PQ * 64) + lane;
+#pragma unroll
+    for (int i = 0; i < PQ; ++i) dst[i] = wp[64 * i];
+}
+// acc0 / acc1 += the piece's A fragments x 16 k-steps of a tile (hp: this lane's row of an A-layout tile, at the piece's first k-step)
+__device__ __forceinline__ void w_gemm(const f32x4 (&w)[PQ], const float* hp, f32x4& acc0, f32x4& acc1)
+{
+#pragma unroll
+    for (int i = 0; i < PQ; ++i) {
+        const float2 lo = *reinterpret_cast<const float2*>(hp + 4 * i), hi = *reinterpret_cast<const float2*>(hp + 4 * i + 2);
+        f32x4& acc = (i & 1) ? acc1 : acc0;
+        acc = mf(w[i][0], lo.x, acc); acc = mf(w[i][1], lo.y, acc);
+        acc = mf(w[i][2], hi.x, acc); acc = mf(w[i][3], hi.y, acc);
+    }
+}
+
+__device__ __forceinline__ PolyArgs poly_args() { return PolyArgs{}; }
+__device__ __forceinline__ PolyArgs poly_args(const PolyArgs& p) { return p; }
+
 // CC: the node-chunk length ceil(M / 4) as a compile-time value (0: run time).  With it every "does k-step t touch chunk g"
 // decision folds away; left to run time the ~100 uniform conditions are hoisted out of the loops into SGPRs that spill
 // (measured: 256 VGPRs + scratch vs 167 VGPRs), so the common sizes get their own instantiation.
 // ENV: EAMRL_ENV_TSP, _CVRP, and (round 3) _CVRPTW, _PCTSP, _OP (state machine of the starts: bit-set masks either way; the depot envs add the visited set, the
 // load of the vehicle and the per-step mask recomputation, cvrp/env.py:68-144).
-template <int RTT, int CC, int ENV>
-__global__ __launch_bounds__(512, 2) void k_rollout_ms_mfma(DecArgs a, int S, int nsplit)
+// POLY (PolyNet, nn/attention.py:476-555): between the glimpse and the logits every 16-query tile goes through
+//   g = heads Wout^T;  h = relu(W1[:, :E] g + ctab[strategy]);  y = g + (W2 h + b2)
+// and the logits are y . L -- the caller hands the UNFOLDED logit key in a.Lp.  See the block behind the glimpse barrier.
+// It is a trailing parameter pack so that the plain kernels keep their argument list: PA is empty, or one PolyArgs.
+template <int RTT, int CC, int ENV, typename... PA>
+__global__ __launch_bounds__(512, 2) void k_rollout_ms_mfma(DecArgs a, int S, int nsplit, PA... pa)
 {
+    constexpr bool POLY = sizeof...(PA) == 1;
+    const PolyArgs pn = poly_args(pa...);
     constexpr bool TW = ENV == EAMRL_ENV_CVRPTW;        // CVRP + clock and time windows
     constexpr bool CV = ENV == EAMRL_ENV_CVRP || TW;    // vehicle load against the demands
     constexpr bool PC = ENV == EAMRL_ENV_PCTSP;         // prize collecting: used = collected prize, cap = required prize
@@ -149,6 +180,7 @@ __global__ __launch_bounds__(512, 2) void k_rollout_ms_mfma(DecArgs a, int S, in
     __shared__ float s_xy[XY ? 256 : 2], s_tw0[TW ? 128 : 1], s_tw1[TW ? 128 : 1], s_dur[TW ? 128 : 1];   // coordinates, windows, service
     __shared__ uint32_t s_flags;
     __shared__ __attribute__((aligned(16))) float s_dyn[SD ? 3 * ME : 4];           // SDVRP: wk | wv | lw
+    __shared__ __attribute__((aligned(16))) float H1T[POLY ? 16 * TS2 : 4];         // PolyNet: relu(poly_layer_1) of the tile, [16][256]
     extern __shared__ __attribute__((aligned(16))) float LPF[];    // [RTT waves][32 k-steps][64 lanes]: the logit-key (Lp) A fragments
                                                                     // (kept in LDS, lane-linear: 32 VGPRs fewer per wave)
     // SDVRP: remaining demands of every start, [SMAX][16 RTT] in accumulator order -- node n at (n >> 4) * 16 + (n & 3) * 4 + ((n & 15) >> 2),
@@ -316,7 +348,7 @@ __global__ __launch_bounds__(512, 2) void k_rollout_ms_mfma(DecArgs a, int S, in
     const bool pre = nqt > 1;
     bool have_q = false;                // QT already holds the tile about to be processed
 #ifdef EAMRL_STAMPS
-    unsigned long long st_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_t = __builtin_readcyclecounter();
+    unsigned long long st_acc[24] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_t = __builtin_readcyclecounter();
 #endif
     for (;;) {
         __syncthreads();                 // the last tile's transition (its done flags) before anyone looks at them
@@ -514,8 +546,83 @@ __global__ __launch_bounds__(512, 2) void k_rollout_ms_mfma(DecArgs a, int S, in
                 }
             }
             MSTAMP(4);
+            // PolyNet: the three weight matrices (320 kB) do not fit into LDS next to the tiles, so every wavefront streams its own
+            // rows from L2 as ready-made MFMA A fragments (one 16-byte load per four k-steps), in pieces of four loads through two
+            // register buffers: a piece is requested while the MFMAs of the piece before it run, the first one here, across the
+            // barrier.  (Pieces of eight: 9 VGPRs to scratch at 112 nodes.)
+            f32x4 wa[PQ], wb[PQ];
+            if constexpr (POLY) w_load(wa, pn.Wout, 2 * wv, lane);                   // project_out rows 16 wv .. 16 wv + 15, columns 0 .. 63
             __syncthreads();
             MSTAMP(5);
+            if constexpr (POLY) {
+                // ---- PolyNet layers of the tile (queries = the MFMA's N dimension, as in the logit phase below) --------------------
+                // g = heads Wout^T, columns 16 wv + 4 G + r of query j
+                f32x4 g0 = z4(), g1 = z4();
+                {
+                    const float* hp = HT + j * TS + G * TG;
+                    w_load(wb, pn.Wout, 2 * wv + 1, lane);
+                    w_gemm(wa, hp, g0, g1);
+                    w_load(wa, pn.W1, 4 * wv, lane);                        // poly_layer_1 rows 32 wv .. + 15
+                    w_gemm(wb, hp + 16, g0, g1);
+                    w_load(wb, pn.W1, 4 * wv + 1, lane);
+                }
+                const f32x4 gl = g0 + g1;
+                MSTAMP(17);
+                {       // g goes into QT: the tile's queries were last read in the glimpse phase, the next tile's are stored in the finish phase
+                    float* gp = QT + j * TS + 4 * wv + G;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) gp[r * TG] = gl[r];
+                }
+                // strategy of this lane's query: start s_off + sq of the whole rollout, modulo k (the reference tiles the table)
+                const int js = (pn.s_off + 16 * qt + j) % pn.k;
+                const float4 cb0 = *reinterpret_cast<const float4*>(pn.ctab + js * PD + 32 * wv + 4 * G);
+                const float4 cb1 = *reinterpret_cast<const float4*>(pn.ctab + js * PD + 32 * wv + 16 + 4 * G);
+                const float4 bb = *reinterpret_cast<const float4*>(pn.b2 + 16 * wv + 4 * G);
+                __syncthreads();                 // g is published, and every wavefront has read the heads: HT is free for y
+                MSTAMP(18);
+                // h = relu(W1[:, :E] g + ctab[js]): hidden columns 32 wv + 4 G + r and + 16, the bias as the chain's first term
+                {
+                    const float* hp = QT + j * TS + G * TG;
+                    f32x4 h0 = (f32x4){cb0.x, cb0.y, cb0.z, cb0.w}, h0b = z4(), h1 = (f32x4){cb1.x, cb1.y, cb1.z, cb1.w}, h1b = z4();
+                    w_gemm(wa, hp, h0, h0b);
+                    w_load(wa, pn.W1, 4 * wv + 2, lane);                    // ... rows 32 wv + 16 .. + 31
+                    w_gemm(wb, hp + 16, h0, h0b);
+                    w_load(wb, pn.W1, 4 * wv + 3, lane);
+                    w_gemm(wa, hp, h1, h1b);
+                    w_load(wa, pn.W2, 4 * wv, lane);                        // poly_layer_2 rows 16 wv .. + 15, hidden columns 0 .. 63
+                    w_gemm(wb, hp + 16, h1, h1b);
+                    w_load(wb, pn.W2, 4 * wv + 1, lane);
+                    h0 = h0 + h0b;
+                    h1 = h1 + h1b;
+                    float* op = H1T + j * TS2 + 8 * wv + G;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        op[r * TG2] = h0[r] > 0.0f ? h0[r] : 0.0f;
+                        op[r * TG2 + 4] = h1[r] > 0.0f ? h1[r] : 0.0f;
+                    }
+                }
+                MSTAMP(19);
+                __syncthreads();                 // h is published
+                MSTAMP(20);
+                // y = g + (W2 h + b2): columns 16 wv + 4 G + r -- the ones whose g this lane still holds
+                {
+                    f32x4 p0 = (f32x4){bb.x, bb.y, bb.z, bb.w}, p1 = z4();
+                    const float* hp = H1T + j * TS2 + G * TG2;
+                    w_gemm(wa, hp, p0, p1);
+                    w_load(wa, pn.W2, 4 * wv + 2, lane);
+                    w_gemm(wb, hp + 16, p0, p1);
+                    w_load(wb, pn.W2, 4 * wv + 3, lane);
+                    w_gemm(wa, hp + 32, p0, p1);
+                    w_gemm(wb, hp + 48, p0, p1);
+                    const f32x4 y = gl + (p0 + p1);
+                    float* yp = HT + j * TS + 4 * wv + G;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) yp[r * TG] = y[r];
+                }
+                MSTAMP(21);
+                __syncthreads();                 // y is published: the logit phase reads it where it read the heads
+                MSTAMP(22);
+            }
             QRaw q_raw;
             if (pre) q_raw = q_fetch(qt + 1 == qt1 ? qt0 : qt + 1);       // loads in flight across the logit phase
             // ---- logits of key tile wv: u[query][key] = ((c0 + c1) + c2) + c3, transposed into UT ---------------------------------
@@ -598,6 +705,9 @@ __global__ __launch_bounds__(512, 2) void k_rollout_ms_mfma(DecArgs a, int S, in
                         // once, kept in 20 SGPRs across the whole kernel and spilled (a v_readlane per key, per tile)
                         uint64_t sd = seed;
                         asm volatile("" : "+s"(sd));
+                        // (PolyNet: the row of the whole rollout, so that a rollout split into launches draws what one launch would)
+                        if constexpr (POLY) exp1_noise4(sd, r2 + (int64_t)pn.s_off * a.B, t, l32, nz);
+                        else
                         exp1_noise4(sd, r2, t, l32, nz);
                     } else {
                         const float* np_ = a.noise + (mul32w(r2, a.t_max) + t) * (int64_t)M;
@@ -800,6 +910,7 @@ __global__ __launch_bounds__(512, 2) void k_rollout_ms_mfma(DecArgs a, int S, in
 #ifdef EAMRL_STAMPS
     if (lane == 0) {
         for (int i = 0; i < 16; ++i) atomicAdd(&g_ms_stamps[i], st_acc[i]);
+        for (int i = 17; i < 23; ++i) atomicAdd(&g_ms_stamps[i], st_acc[i]);        // PolyNet phases
         atomicAdd(&g_ms_stamps[16], 1ull);
     }
 #endif
@@ -870,6 +981,32 @@ int launch_env_t(const DecArgs& a, int S, int C, hipStream_t st)
     return C == 26 ? launch_t<7, 26, ENV>(a, S, st) : launch_t<7, 0, ENV>(a, S, st);
 }
 
+// PolyNet: TSP and CVRP.  One instantiation per key-tile count: the glimpse's node chunks are the fixed [4 RTT g, 4 RTT (g + 1))
+// -- whole k-steps, nothing straddles -- for every M the tile count covers (slots beyond M carry zero weights and values).  The
+// run-time chunk length ceil(M / 4) of the plain kernel, which exists to reproduce the oracle's summation order bit for bit,
+// costs ~50 VGPRs that the weight stream needs (scratch otherwise); PolyNet is pinned to a float64 restatement instead.
+template <int RTT, int ENV>
+int launch_poly_t(const DecArgs& a, const PolyArgs& pn, int S, hipStream_t st)
+{
+    const size_t lds = (size_t)RTT * 32 * 64 * sizeof(float);
+    auto k = k_rollout_ms_mfma<RTT, 4 * RTT, ENV, PolyArgs>;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return EAMRL_E_LAUNCH;
+    const int nqt = (S + 15) / 16;
+    int nsplit = a.B > 0 ? (int)(256 / a.B) : 1;
+    nsplit = nsplit < 1 ? 1 : (nsplit > nqt ? nqt : nsplit);
+    hipLaunchKernelGGL(k, dim3((unsigned)(a.B * nsplit)), dim3(512), lds, st, a, S, nsplit, pn);
+    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
+}
+
+template <int ENV>
+int launch_poly_env_t(const DecArgs& a, const PolyArgs& pn, int S, hipStream_t st)
+{
+    if (a.M <= 32) return launch_poly_t<2, ENV>(a, pn, S, st);
+    if (a.M <= 64) return launch_poly_t<4, ENV>(a, pn, S, st);
+    return launch_poly_t<7, ENV>(a, pn, S, st);
+}
+
 }  // namespace
 
 #ifdef EAMRL_STAMPS
@@ -917,6 +1054,24 @@ int launch_rollout_ms_mfma(int env, const DecArgs& a, hipStream_t st)
                  : env == EAMRL_ENV_SDVRP ? launch_env_t<EAMRL_ENV_SDVRP>(a, S, C, st) : launch_env_t<EAMRL_ENV_OP>(a, S, C, st);
     if (rc) return rc;
     launch_rollout_pad(env, a, st);              // rows that finished early end at the depot (and PCTSP / OP get their step counters)
+    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
+}
+
+// PolyNet rollouts: what the start-sharing kernel takes at all, TSP and CVRP only, no filters, no glimpse capture
+bool rollout_ms_poly_supports(int env, const DecArgs& a, bool shape_only)
+{
+    if (env != EAMRL_ENV_TSP && env != EAMRL_ENV_CVRP) return false;
+    return rollout_ms_mfma_supports(env, a, shape_only);
+}
+
+// one launch for the S <= 128 starts of `a` (a.Lp = the unfolded logit key); pn.s_off = the first start's index in the whole rollout
+int launch_rollout_ms_poly(int env, const DecArgs& a, const PolyArgs& pn, hipStream_t st)
+{
+    const int S = (int)(a.R / a.B);
+    if (env == EAMRL_ENV_TSP) return launch_poly_env_t<EAMRL_ENV_TSP>(a, pn, S, st);
+    const int rc = launch_poly_env_t<EAMRL_ENV_CVRP>(a, pn, S, st);
+    if (rc) return rc;
+    launch_rollout_pad(env, a, st);
     return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
 }
 

@@ -1576,8 +1576,10 @@ def _capture_heads(st, cache, cs, R, t_max, want_heads):
 
 
 def rollout(st: RolloutState, cache: DecodeCache, mode="greedy", noise=None, given=None, clip=10.0, temp=1.0,
-            t_max=None, top_k=0, top_p=0.0, seed=None, seed_dev=None, return_flags=False, want_heads=False):
+            t_max=None, top_k=0, top_p=0.0, seed=None, seed_dev=None, return_flags=False, want_heads=False, poly=None):
     """Whole decode loop in one launch.  -> (actions [R,t_max], logps [R,t_max], info int32[2] = (steps, status)).
+    poly: the operands of a PolyNet pointer (`polynet_operands`, on the device): the rollout runs the PolyNet case of the
+    start-sharing kernel (one launch per 128 rows of an instance), or raises where that is not built.
     Sampling takes its Exp(1) noise from `noise` [R, T, M] or, with `seed` (XOR the device word `seed_dev`), from the counter-based
     generator -- in place where the kernel supports it (TSP multistart), else through a scratch tensor of the same draws.
     return_flags: info is int32[4] = (steps, status, 0, 0), the last two free for the caller's validity counters."""
@@ -1586,9 +1588,13 @@ def rollout(st: RolloutState, cache: DecodeCache, mode="greedy", noise=None, giv
     R, M, dev = st.R, st.M, st.mask.device
     if t_max is None:
         t_max = env_spec.max_steps(st.env_name, M)
+    if mode == "sampling" and noise is None and seed is None:
+        raise ValueError("rollout: sampling needs `noise` or `seed`")
+    if poly is not None:
+        if top_k or (0.0 < top_p < 1.0):
+            raise NotImplementedError("PolyNet rollout: top-k / top-p filtering is not built")
+        return _rollout_polynet(st, cache, poly, mode, noise, given, clip, temp, int(t_max), seed, seed_dev, return_flags)
     if mode == "sampling" and noise is None:
-        if seed is None:
-            raise ValueError("rollout: sampling needs `noise` or `seed`")
         if top_k or (0.0 < top_p < 1.0):
             # the kernels that filter (register-resident FILT variant, streaming) read their noise from a tensor
             noise = exp1_noise(seed, R, int(t_max), M, dev, seed_dev)
@@ -1634,6 +1640,95 @@ def rollout(st: RolloutState, cache: DecodeCache, mode="greedy", noise=None, giv
                                     _ptr(given), t_given, float(clip), float(temp), int(top_k), float(top_p), int(t_max),
                                     _ptr(actions),
                                     _ptr(logps), steps_ptr, status_ptr, _stream(st.mask)), "eamrl_am_rollout")
+    return actions, logps, (info if return_flags else info[:2])
+
+
+# ------------------------------------------------------------------------------------------------------
+# PolyNet (eamrl_polynet): weight constants of the pointer, and the rollout on them
+# ------------------------------------------------------------------------------------------------------
+POLY_LAYER_DIM = 256        # the P the kernel is built for
+
+
+def pack_mfma_a(W):
+    """Row-major [N, K] -> the "fragment order" of include/eamrl.h (eamrl_polynet): float 4 * ((T * (K / 16) + q) * 64 + l) + i
+    holds W[16 T + l % 16, 16 q + 4 i + l // 16] -- what lane l of a wavefront feeds into four consecutive
+    v_mfma_f32_16x16x4_f32 as the A operand of row tile T, read with one 16-byte load.  Plain indexing (any device)."""
+    N, K = W.shape
+    assert N % 16 == 0 and K % 16 == 0
+    dev = W.device
+    T, q = torch.arange(N // 16, device=dev)[:, None, None, None], torch.arange(K // 16, device=dev)[None, :, None, None]
+    l, i = torch.arange(64, device=dev)[None, None, :, None], torch.arange(4, device=dev)[None, None, None, :]
+    return W[16 * T + l % 16, 16 * q + 4 * i + l // 16].contiguous().reshape(-1)
+
+
+def polynet_operands(Wout, W1, b1, W2, b2, binary_vectors):
+    """The weight-only operands of eamrl_polynet from the pointer's parameters (PolyNetAttention, nn/attention.py:502-517):
+    project_out / poly_layer_1[:, :E] / poly_layer_2 in fragment order and ctab[j] = W1[:, E:] z_j + b1 ([k, P], computed
+    in float64 and rounded once).  Any device; no kernel is launched."""
+    E = Wout.shape[0]
+    P = W1.shape[0]
+    Z = binary_vectors.detach().double()
+    ctab = (Z @ W1.detach()[:, E:].double().t() + b1.detach().double()).float().contiguous()
+    return {"Wout": pack_mfma_a(Wout.detach().float()), "W1": pack_mfma_a(W1.detach()[:, :E].float()), "ctab": ctab,
+            "W2": pack_mfma_a(W2.detach().float()), "b2": b2.detach().float().contiguous().clone(), "k": int(Z.shape[0]), "P": int(P)}
+
+
+def rollout_polynet_supported(env_name, cache, R) -> bool:
+    """Whether `rollout(..., poly=)` serves this env / cache shape / row count (eamrl_rollout_polynet_supported; host only)."""
+    if env_name not in ("tsp", "cvrp"):
+        return False
+    cs = cache if isinstance(cache, _lib.Cache) else cache.struct()
+    return bool(_lib.load().eamrl_rollout_polynet_supported(ENVS[env_name], C.byref(cs), int(R)))
+
+
+def _rollout_polynet(st, cache, poly, mode, noise, given, clip, temp, t_max, seed, seed_dev, return_flags):
+    lib = _lib.load()
+    R, M, dev = st.R, st.M, st.mask.device
+    if cache.planes:
+        raise NotImplementedError("PolyNet rollout: graphs above 112 nodes are not built (plane-major cache)")
+    for name in ("Wout", "W1", "ctab", "W2", "b2"):
+        _chk(poly[name], f"poly[{name!r}]", torch.float32)
+    E, k, P = cache.E, int(poly["k"]), int(poly["P"])
+    if P != POLY_LAYER_DIM:
+        raise NotImplementedError(f"PolyNet rollout: poly_layer_dim = {P}; the kernel is built for {POLY_LAYER_DIM}")
+    if (poly["Wout"].numel(), poly["W1"].numel(), poly["W2"].numel(), poly["b2"].numel()) != (E * E, P * E, E * P, E) \
+            or tuple(poly["ctab"].shape) != (k, P):
+        raise ValueError("PolyNet rollout: operand shapes do not match the cache (ops.polynet_operands)")
+    cs = cache.struct()
+    if not lib.eamrl_rollout_polynet_supported(ENVS.get(st.env_name, -1), C.byref(cs), R):
+        raise NotImplementedError(f"PolyNet rollout: env {st.env_name!r} with {M} nodes and {R // cache.B} rows per instance is not "
+                                  "built: TSP / CVRP, at most 112 nodes, at least two rows per instance, embed_dim 128, 8 heads")
+    t_given = 0
+    if noise is not None:
+        _chk(noise, "noise", torch.float32)
+        if noise.dim() != 3 or noise.shape[0] != R or noise.shape[2] != M:
+            raise ValueError("noise must be [R, T, M]")
+        t_max = noise.shape[1]
+    if given is not None:
+        _chk(given, "given actions", torch.int64)
+        if given.dim() != 2 or given.shape[0] != R:
+            raise ValueError("given actions must be [R, T]")
+        t_given = given.shape[1]
+        if noise is None and st.env_name != "tsp":
+            t_max = min(t_max, t_given)
+    actions, logps, info = _rollout_outputs(R, int(t_max), dev)
+    st.heads = st.heads_out = None
+    ss = st.struct()
+    ps = _lib.PolyNet()
+    ps.Wout, ps.W1, ps.ctab, ps.W2, ps.b2 = (poly[n].data_ptr() for n in ("Wout", "W1", "ctab", "W2", "b2"))
+    ps.L = cache.buf.data_ptr() + cache.slots["L"] * cache.E * 4
+    ps.k, ps.P, ps.s_offset = k, P, 0
+    steps_ptr, status_ptr = C.c_void_p(info.data_ptr()), C.c_void_p(info.data_ptr() + 4)
+    if mode == "sampling" and noise is None:
+        _lib.check(lib.eamrl_am_rollout_polynet_seeded(ENVS[st.env_name], C.byref(cs), C.byref(ss), C.byref(ps), R,
+                                                       C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _ptr(seed_dev), float(clip),
+                                                       float(temp), int(t_max), _ptr(actions), _ptr(logps), steps_ptr, status_ptr,
+                                                       _stream(st.mask)), "eamrl_am_rollout_polynet_seeded")
+    else:
+        _lib.check(lib.eamrl_am_rollout_polynet(ENVS[st.env_name], C.byref(cs), C.byref(ss), C.byref(ps), R, MODES[mode],
+                                                _ptr(noise), _ptr(given), t_given, float(clip), float(temp), int(t_max),
+                                                _ptr(actions), _ptr(logps), steps_ptr, status_ptr, _stream(st.mask)),
+                   "eamrl_am_rollout_polynet")
     return actions, logps, (info if return_flags else info[:2])
 
 

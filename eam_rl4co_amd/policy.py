@@ -917,6 +917,10 @@ class AttentionModelPolicy(nn.Module):
             if own_shared:
                 self._shared_dt = None
 
+    def _pointer_operands(self):
+        """Extra weight operands of the decode kernels' pointer (ops.rollout's `poly`): none for the plain pointer."""
+        return None
+
     def _parameter_list(self):
         """The Parameter objects, kept: walking the module tree costs 0.3 ms and every forward asks (see train._graph_key)."""
         lists = self.__dict__.get("_key_tensors")
@@ -1124,6 +1128,7 @@ class AttentionModelPolicy(nn.Module):
             acts, lps, info = ops.rollout(st, cache, mode, noise=noise, given=given, clip=tanh_clipping,
                                           temp=temperature, t_max=t_max, top_k=top_k, top_p=top_p, seed=seed, seed_dev=seed_dev,
                                           return_flags=True,          # int32[4]: steps, status, 2 free validity counters
+                                          poly=self._pointer_operands(),
                                           want_heads=bool(getattr(self, "_want_heads", False)) and bool(pre_actions))
         # Everything below is enqueued on the PADDED [R, t_max] arrays before the rollout's single host sync:
         # padding is depot visits with log-prob 0, which change neither the tour length (zero-length legs, and
@@ -1385,6 +1390,121 @@ class HeterogeneousAttentionModelPolicy(AttentionModelPolicy):
                          num_heads=num_heads, normalization=normalization, **kwargs)
 
 
+class PolyNetDecoder(AttentionModelDecoder):
+    """AttentionModelDecoder with the PolyNet pointer (zoo/polynet/decoder.py:27-112, same arguments and state-dict keys).
+    Cache, context and dynamic embedding are the Attention Model's; the pointer's extra operands go to the rollout kernel
+    through `poly_operands`."""
+
+    is_polynet = True
+
+    def __init__(self, k: int, encoder_type: str = "AM", embed_dim: int = 128, poly_layer_dim: int = 256, num_heads: int = 8,
+                 env_name="tsp", context_embedding=None, dynamic_embedding=None, mask_inner: bool = True,
+                 out_bias_pointer_attn: bool = False, linear_bias: bool = False, use_graph_context: bool = True,
+                 check_nan: bool = True, sdpa_fn=None, **unused_kwargs):
+        from .attention import PolyNetAttention
+
+        if encoder_type != "AM":
+            raise NotImplementedError(f"PolyNetDecoder: encoder_type={encoder_type!r} is not built for MI355X (the MatNet encoder "
+                                      "and its row / column cache are not part of this library); use encoder_type='AM'")
+        if poly_layer_dim != ops.POLY_LAYER_DIM:
+            raise NotImplementedError(f"PolyNetDecoder: poly_layer_dim={poly_layer_dim}; the rollout kernel is built for "
+                                      f"{ops.POLY_LAYER_DIM} (the reference's default)")
+        if isinstance(env_name, RL4COEnvBase):
+            env_name = env_name.name
+        if _kind(env_name) not in ("tsp", "cvrp"):
+            raise NotImplementedError(f"PolyNetDecoder: env_name={env_name!r}; the PolyNet rollout kernel is built for 'tsp' and "
+                                      "'cvrp' (SDVRP's dynamic embedding, PDP and the other envs are not)")
+        if embed_dim != 128 or num_heads != 8:
+            raise NotImplementedError("PolyNetDecoder: the rollout kernel is built for embed_dim=128, num_heads=8")
+        pointer = PolyNetAttention(k, embed_dim, poly_layer_dim, num_heads, mask_inner=mask_inner, out_bias=out_bias_pointer_attn,
+                                   check_nan=check_nan, sdpa_fn="default" if sdpa_fn is None else sdpa_fn)
+        super().__init__(embed_dim=embed_dim, num_heads=num_heads, env_name=env_name, context_embedding=context_embedding,
+                         dynamic_embedding=dynamic_embedding, mask_inner=mask_inner, out_bias_pointer_attn=out_bias_pointer_attn,
+                         linear_bias=linear_bias, use_graph_context=use_graph_context, check_nan=check_nan, pointer=pointer)
+        self.encoder_type, self.k = encoder_type, k
+
+    def poly_operands(self):
+        """ops.polynet_operands of the pointer's parameters, recomputed when one of them changes (optimizer step, load) and
+        refreshed in place where the shapes allow, like `_weight_constants`."""
+        ptr = self.pointer
+        srcs = (ptr.project_out.weight, ptr.poly_layer_1.weight, ptr.poly_layer_1.bias, ptr.poly_layer_2.weight,
+                ptr.poly_layer_2.bias, ptr.binary_vectors)
+        key = tuple((t.data_ptr(), t._version) for t in srcs)
+        if getattr(self, "_poly_key", None) != key:
+            new = ops.polynet_operands(*srcs)
+            old = self.__dict__.get("_poly")
+            if old is not None and all(isinstance(v, int) or (v.shape == old[n].shape and v.device == old[n].device)
+                                       for n, v in new.items()):
+                for n, v in new.items():
+                    if isinstance(v, int):
+                        old[n] = v
+                    else:
+                        old[n].copy_(v)
+            else:
+                self.__dict__["_poly"] = new
+            self._poly_key = key
+        return self.__dict__["_poly"]
+
+    def forward(self, td, cached, num_starts: int = 0):
+        raise NotImplementedError("PolyNetDecoder: a single decode step is not built for MI355X; PolyNetPolicy rolls out in one "
+                                  "launch per 128 solutions of an instance")
+
+
+class PolyNetPolicy(AttentionModelPolicy):
+    """PolyNet (Hottung et al. 2024; zoo/polynet/policy.py:10-99, same arguments and defaults): the Attention Model encoder
+    (POMO's settings) with the PolyNet decoder, k strategies per instance.  Rollouts are multi-row per instance --
+    `policy(td, env, num_starts=S, multisample=True)` as PolyNet.shared_step calls it (zoo/polynet/model.py:141-148) -- and run
+    in the PolyNet case of the start-sharing kernel; everything else raises NotImplementedError (there is no PyTorch rollout)."""
+
+    def __init__(self, k: int, encoder: nn.Module = None, encoder_type: str = "AM", embed_dim: int = 128,
+                 num_encoder_layers: int = 6, num_heads: int = 8, normalization: str = "instance",
+                 feedforward_hidden: int = 512, env_name="tsp", temperature: float = 1.0, tanh_clipping: float = 10.0,
+                 mask_logits: bool = True, train_decode_type: str = "sampling", val_decode_type: str = "sampling",
+                 test_decode_type: str = "sampling", **kwargs):
+        if encoder_type != "AM":
+            raise NotImplementedError(f"PolyNetPolicy: encoder_type={encoder_type!r} is not built for MI355X (no MatNet encoder in "
+                                      "this library); use encoder_type='AM'")
+        dec_kw = {n: kwargs.pop(n) for n in ("poly_layer_dim", "use_graph_context", "check_nan", "mask_inner",
+                                             "out_bias_pointer_attn") if n in kwargs}
+        if isinstance(env_name, RL4COEnvBase):
+            env_name = env_name.name
+        decoder = PolyNetDecoder(k=k, encoder_type=encoder_type, embed_dim=embed_dim, num_heads=num_heads, env_name=env_name,
+                                 **dec_kw)
+        super().__init__(encoder=encoder, decoder=decoder, embed_dim=embed_dim, num_encoder_layers=num_encoder_layers,
+                         num_heads=num_heads, normalization=normalization, feedforward_hidden=feedforward_hidden,
+                         env_name=env_name, temperature=temperature, tanh_clipping=tanh_clipping, mask_logits=mask_logits,
+                         train_decode_type=train_decode_type, val_decode_type=val_decode_type,
+                         test_decode_type=test_decode_type, **kwargs)
+        self.k = k
+
+    def _pointer_operands(self):
+        return self.decoder.poly_operands()
+
+    def _enqueue(self, td, env, phase, calc_reward, return_actions, return_entropy, return_hidden, return_init_embeds,
+                 return_sum_log_likelihood, actions, max_steps, **decoding_kwargs):
+        kw = decoding_kwargs
+        decode_type = kw.get("decode_type") or getattr(self, f"{phase}_decode_type")
+        if decode_type == "beam_search":
+            raise NotImplementedError("PolyNetPolicy: beam search is not built (its step loop runs the per-step decoder)")
+        if return_entropy or kw.get("store_all_logp"):
+            raise NotImplementedError("PolyNetPolicy: return_entropy / store_all_logp are not built (they need the per-step "
+                                      "decoder or the re-evaluation kernel, neither has the PolyNet layers)")
+        if kw.get("top_k") or 0.0 < float(kw.get("top_p") or 0.0) < 1.0:
+            raise NotImplementedError("PolyNetPolicy: top-k / top-p filtering is not built into the PolyNet rollout kernel")
+        if kw.get("select_best"):
+            raise NotImplementedError("PolyNetPolicy: select_best is not built; take the best of out['reward'] per instance")
+        S = kw.get("num_starts") if kw.get("num_starts") is not None else kw.get("num_samples")
+        many = (S is not None and S > 1) or (S is None and (kw.get("multistart") or kw.get("multisample")
+                                                            or "multistart" in decode_type))
+        if not many:
+            raise NotImplementedError("PolyNetPolicy: rollouts with one row per instance are not built; PolyNet decodes several "
+                                      "solutions per instance: policy(td, env, num_starts=S, multisample=True) with S >= 2")
+        if td["action_mask"].shape[-1] > 112:
+            raise NotImplementedError(f"PolyNetPolicy: graphs above 112 nodes are not built (got {td['action_mask'].shape[-1]})")
+        return super()._enqueue(td, env, phase, calc_reward, return_actions, return_entropy, return_hidden, return_init_embeds,
+                                return_sum_log_likelihood, actions, max_steps, **decoding_kwargs)
+
+
 def load_reference_checkpoint(policy: AttentionModelPolicy, ckpt, strict: bool = True):
     """Load the policy weights of a reference Lightning checkpoint.
 
@@ -1486,6 +1606,8 @@ class GraphedRollout:
         if (forward_kwargs.get("return_entropy") or forward_kwargs.get("store_all_logp") or forward_kwargs.get("select_best")
                 or forward_kwargs.get("decode_type") == "beam_search"):
             raise NotImplementedError("GraphedRollout: step-wise / select_best / beam-search rollouts are not capturable")
+        if isinstance(policy, PolyNetPolicy):
+            raise NotImplementedError("GraphedRollout: capture of a PolyNet rollout has not been built or tested")
         self.policy, self.env = policy, env
         self.kw = dict(phase=phase, calc_reward=True, return_actions=True, return_entropy=False, return_hidden=False,
                        return_init_embeds=False, return_sum_log_likelihood=True, actions=None, max_steps=1_000_000)

@@ -621,6 +621,10 @@ def decoder_tensors(policy, td):
         t["placeholder"] = dec.context_embedding.W_placeholder
     if policy.env_name == "sdvrp":
         t["dyn"] = dec.dynamic_embedding.projection.weight
+    if getattr(dec, "is_polynet", False):      # PolyNetAttention's layers (nn/attention.py:516-517) and its strategy table
+        ptr = dec.pointer
+        t.update(polyW1=ptr.poly_layer_1.weight, polyb1=ptr.poly_layer_1.bias, polyW2=ptr.poly_layer_2.weight,
+                 polyb2=ptr.poly_layer_2.bias, polyZ=ptr.binary_vectors)
     if shared is not None:
         shared["graph"] = (key, t)
     return t
@@ -647,9 +651,10 @@ def _filter_logits_(logits, act, top_k: int, top_p: float):
     return logits.masked_fill(drop, float("-inf"))
 
 
-def _logp_rows(env_name, t, static, act, nrep, multistart, H, temperature, clip, top_k=0, top_p=0.0):
+def _logp_rows(env_name, t, static, act, nrep, multistart, H, temperature, clip, top_k=0, top_p=0.0, s_first=0):
     """Per-step log-probabilities [Rc, T] of the rows `act` (nrep whole start groups of the B instances, (s b) order).
-    `t`: decoder_tensors; `static`: the instance tensors the masks are rebuilt from."""
+    `t`: decoder_tensors; `static`: the instance tensors the masks are rebuilt from.  s_first: index of the rows' first start
+    group in the whole rollout (PolyNet: the strategy of a row is its start index modulo k)."""
     emb, K, V, L = t["emb"], t["K"], t["V"], t["L"]
     B, M, E = emb.shape
     D = E // H
@@ -705,6 +710,11 @@ def _logp_rows(env_name, t, static, act, nrep, multistart, H, temperature, clip,
     else:
         heads = F.scaled_dot_product_attention(qh, kh, vh, attn_mask=mask[:, None])     # [Rc, H, T, D]
     glimpse = F.linear(heads.permute(0, 2, 1, 3).reshape(Rc, T, E), t["Wout"])
+    if "polyW1" in t:       # PolyNetAttention.forward (nn/attention.py:534-545): row r = s * B + b uses strategy (s_first + s) % k
+        Z = t["polyZ"]
+        z = Z[(s_first + torch.arange(Rc, device=act.device) // B) % Z.shape[0]]
+        hid = F.relu(F.linear(torch.cat((glimpse, z[:, None, :].expand(Rc, T, z.shape[-1])), -1), t["polyW1"], t["polyb1"]))
+        glimpse = glimpse + F.linear(hid, t["polyW2"], t["polyb2"])
     logits = torch.bmm(glimpse, Lr.transpose(1, 2))
     if env_name == "sdvrp":
         logits = logits + dem_t * (glimpse @ wl)[..., None]
@@ -763,6 +773,8 @@ def native_reeval_supported(policy, M: int) -> bool:
     from . import ops
 
     dec = policy.decoder
+    if getattr(dec, "is_polynet", False):       # the re-evaluation kernels have no PolyNet layers: the PyTorch expression
+        return False
     return (os.environ.get("EAMRL_NATIVE_REEVAL", "1") != "0" and policy.env_name in _NATIVE_ENVS
             and ops.reeval_supported(M, dec.embed_dim, dec.num_heads))
 
@@ -918,7 +930,7 @@ def evaluate_log_likelihood(policy, td, env, actions, num_starts: int = 0, tempe
     def chunk(c, *tensors):
         s0, s1 = bounds[c]
         return _logp_rows(env_name, dict(zip(names, tensors)), static, actions[s0 * B:s1 * B], s1 - s0, multistart, H,
-                          temperature, clip, top_k, top_p)
+                          temperature, clip, top_k, top_p, s_first=s0)
 
     if checkpoint is None:      # ~6 live [rows, H, T, M] fp32 tensors per chunk if the graph is kept
         checkpoint = len(bounds) > 1 and 24.0 * R * H * T * M > 8e9
@@ -1077,6 +1089,29 @@ def symeam_loss(policy, env, td, ea, num_augment: int = 4, num_starts: int = 0, 
     return res
 
 
+def polynet_loss(reward, log_likelihood):
+    """PolyNet's Poppy loss (zoo/polynet/model.py:195-239 with the shared baseline, rl/reinforce/baselines.py:57-61):
+    reward, log_likelihood [B, S]; the baseline is the mean reward of an instance's S rollouts, and only each instance's
+    best rollout (the first one among equals in a stable descending order, as the reference's double argsort picks)
+    carries gradient.  -> scalar loss = -mean(advantage * log_likelihood * mask) over all B * S entries."""
+    bl = reward.mean(dim=1, keepdim=True)
+    best = (-reward).argsort(1).argsort(1) < 1
+    return -((reward - bl) * log_likelihood * best).mean()
+
+
+def polynet_step_loss(policy, env, td, num_starts: int, **rollout_kwargs):
+    """PolyNet.shared_step in the train phase (zoo/polynet/model.py:124-158): a multisample rollout with `num_starts`
+    solutions per instance and `polynet_loss` on it.  Returns the dict `reinforce_loss` returns."""
+    with torch.enable_grad():
+        out = policy(td, env, phase="train", num_starts=num_starts, multisample=True, return_sum_log_likelihood=False,
+                     **rollout_kwargs)
+    logp = out["log_likelihood"]
+    ll = logp.sum(1)
+    loss = polynet_loss(unbatchify(out["reward"], num_starts), unbatchify(ll, num_starts))
+    return {"loss": loss, "reward": out["reward"], "log_likelihood": ll, "actions": out["actions"], "logp_steps": logp,
+            "native_log_likelihood": ll.detach()}
+
+
 class PolicyGradientStep:
     """One optimizer step of the reference's REINFORCE / POMO training, data-parallel (BASELINE.json configs[3]):
 
@@ -1107,7 +1142,10 @@ class PolicyGradientStep:
 
     def __call__(self, td, **rollout_kwargs) -> dict:
         self.grads.zero_()
-        out = reinforce_loss(self.policy, self.env, td, baseline=self.baseline, num_starts=self.S, **rollout_kwargs)
+        if getattr(self.policy.decoder, "is_polynet", False):       # PolyNet trains on its Poppy loss (num_starts = k in the reference)
+            out = polynet_step_loss(self.policy, self.env, td, self.S, **rollout_kwargs)
+        else:
+            out = reinforce_loss(self.policy, self.env, td, baseline=self.baseline, num_starts=self.S, **rollout_kwargs)
         out["loss"].backward()
         if not self.grads.attached():
             raise RuntimeError("PolicyGradientStep: p.grad is no longer a view of the flat buffer (zero_grad(set_to_none)?)")

@@ -556,6 +556,46 @@ int eamrl_am_rollout_seeded(int env, const eamrl_cache* cache_host, const eamrl_
                             const uint64_t* seed_dev, float* noise_scratch, float tanh_clip, float temperature, int t_max, int64_t* actions,
                             float* logps, int32_t* steps_out, uint32_t* status, void* stream);
 
+/* ---- PolyNet: K strategies per instance in one rollout launch ---------------------------------------- */
+
+/* The pointer of PolyNetAttention.forward  [nn/attention.py:519-556; zoo/polynet/decoder.py:96-105]:
+ *   heads = inner masked MHA;  g = heads Wout^T;  h = relu(W1 [g ; z_j] + b1);  y = g + (W2 h + b2);  logits = y . L[n] / sqrt(E)
+ * with z_j row j = s % k of binary_vectors for solution s of an instance (rows in "(s b)" order: row r = s * B + b).  The
+ * weights are shared by all rows, so the z part of poly_layer_1 is a table: ctab[j] = W1[:, E:] z_j + b1, [k][P].
+ * Wout [E][E], W1 = poly_layer_1.weight[:, :E] [P][E] and W2 = poly_layer_2.weight [E][P] are read as ready-made MFMA A
+ * fragments ("fragment order" of a row-major [N][K] matrix: float 4 * ((T * (K / 16) + q) * 64 + l) + i holds
+ * W[16 T + l % 16][16 q + 4 i + l / 16], l = 0..63, i = 0..3); L is the cache's UNFOLDED logit key, row stride cache->ld
+ * (the Lp fold does not cover y).  All six pointers 16-byte aligned.  P must be 256, E 128. */
+typedef struct eamrl_polynet {
+    const float* Wout; /* pointer.project_out.weight, fragment order */
+    const float* W1;   /* pointer.poly_layer_1.weight[:, :E], fragment order */
+    const float* ctab; /* [k][P] */
+    const float* W2;   /* pointer.poly_layer_2.weight, fragment order */
+    const float* b2;   /* [E] pointer.poly_layer_2.bias */
+    const float* L;    /* [B][M][E] logit key, row stride cache->ld */
+    int32_t k, P;
+    int32_t s_offset;  /* index of the call's first solution in the whole rollout: strategy (s_offset + s) % k, and the
+                        * in-place noise of eamrl_am_rollout_polynet_seeded is drawn for row (s_offset + s) * B + b */
+} eamrl_polynet;
+
+/* eamrl_am_rollout / eamrl_am_rollout_seeded for a PolyNet decoder  [constructive/base.py:236-250 with the pointer above]:
+ * the start-sharing MFMA kernel with the three PolyNet GEMMs of every 16-query tile on v_mfma_f32_16x16x4_f32 between its
+ * glimpse and logit phases.  EAMRL_ENV_TSP and EAMRL_ENV_CVRP, E = 128, H = 8, 2 <= M <= 112, R = S * B rows with S >= 2
+ * (multisample / multistart batches); no top-k / top-p, state->heads_out must be NULL.  S > 128: the call splits the
+ * solutions into launches of at most 128 and advances s_offset itself; the seeded twin computes its noise in place as a
+ * function of the row of the whole rollout, so it equals eamrl_am_rollout_polynet(EAMRL_SAMPLE) fed with the tensor
+ * eamrl_exp1_noise(seed, ..., R, t_max, M) writes, bit for bit, however the solutions were split.  Everything is checked
+ * before the first launch.  eamrl_rollout_polynet_supported: 1 if (env, cache shape, R) is served (host only). */
+int eamrl_rollout_polynet_supported(int env, const eamrl_cache* cache_host, int64_t R);
+int eamrl_am_rollout_polynet(int env, const eamrl_cache* cache_host, const eamrl_state* state_host, const eamrl_polynet* poly,
+                             int64_t R, int mode, const float* noise, const int64_t* given, int t_given, float tanh_clip,
+                             float temperature, int t_max, int64_t* actions, float* logps, int32_t* steps_out,
+                             uint32_t* status, void* stream);
+int eamrl_am_rollout_polynet_seeded(int env, const eamrl_cache* cache_host, const eamrl_state* state_host,
+                                    const eamrl_polynet* poly, int64_t R, uint64_t seed, const uint64_t* seed_dev,
+                                    float tanh_clip, float temperature, int t_max, int64_t* actions, float* logps,
+                                    int32_t* steps_out, uint32_t* status, void* stream);
+
 /* ---- reward ----------------------------------------------------------------------------------------- */
 
 /* reward[r] = -(closed tour length)  [utils/ops.py:59-95; tsp/env.py:152-159; cvrp/env.py:146-155].
