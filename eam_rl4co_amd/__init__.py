@@ -9,6 +9,8 @@ from .policy import (AttentionModelDecoder, AttentionModelEncoder, AttentionMode
 from .attention import PointerAttention, PolyNetAttention, scaled_dot_product_attention  # noqa: F401
 from .evolution import EA, EACvrpDraws, EAPrizeDraws, EADraws, evolution_worker, generate_batch_population  # noqa: F401
 from .search import EAS, EASEmb, EASLay, eas_loss_coefficients  # noqa: F401
+from .critic import CriticNetwork, create_critic_from_actor  # noqa: F401
+from .train import PPOStep, ppo_loss_terms  # noqa: F401
 from .tensordict_lite import TensorDict  # noqa: F401
 from .utils import batchify, gather_by_index, unbatchify  # noqa: F401
 

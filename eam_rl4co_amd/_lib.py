@@ -53,7 +53,8 @@ class Reeval(C.Structure):
                 ("dK", _vp), ("dV", _vp), ("dLp", _vp), ("dPa", _vp), ("dPb", _vp), ("ldg", _i64),
                 ("dgctx", _vp), ("dCvec", _vp), ("rem", _vp), ("dyn", _vp), ("ddyn", _vp),
                 ("nkc", C.c_int32), ("scratch", _vp), ("mc_koff", C.c_int32), ("mc_mstride", C.c_int32),
-                ("mc_part_o", _vp), ("mc_part_s", _vp), ("mc_gstat", _vp), ("mc_lpart", _vp), ("mc_rsq", _vp), ("mc_dq", _vp)]
+                ("mc_part_o", _vp), ("mc_part_s", _vp), ("mc_gstat", _vp), ("mc_lpart", _vp), ("mc_rsq", _vp), ("mc_dq", _vp),
+                ("gent", _vp)]
 
 
 class PolyNet(C.Structure):

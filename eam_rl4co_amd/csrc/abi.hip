@@ -508,7 +508,10 @@ static int check_reeval(const eamrl_reeval* p, const char* what, bool bwd)
         REQUIRE((p->Pb == nullptr) == (p->dPb == nullptr) && (p->gctx == nullptr) == (p->dgctx == nullptr) &&
                     (p->NC == 0 || p->dCvec) && ((uintptr_t)p->dheads % 16 == 0), what);
         REQUIRE(p->NC <= 2 && p->R * (int64_t)p->T < (int64_t)1 << 31, what);     // the backward kernels' query indices
-
+        if (p->gent) {      // the entropy gradient reads what the forward pass wrote, and only the single-chunk kernels carry it
+            REQUIRE(p->entropy && p->lse, what);
+            REQUIRE(p->M <= 112 && p->nkc <= 1, what);
+        }
     }
     return 0;
 }

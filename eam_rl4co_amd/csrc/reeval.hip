@@ -809,7 +809,14 @@ __device__ __forceinline__ uint4 load_mask_words(const ReevalArgs& a, int qi)
     return qi >= 0 ? m : make_uint4(0, 0, 0, 0);
 }
 
-template <int RTT, bool HEADS, bool DYN = false>
+// ENT (eamrl_reeval.gent, PPO's entropy bonus: rl4co/models/rl/ppo/ppo.py:205-209): the logit gradient gains
+//   gent[q] * dH/dz[n] = gent[q] * (-p[n] (log p[n] + H[q])),   H = -sum_n p[n] log p[n]   (calculate_entropy, rl4co/utils/ops.py:108-116)
+// next to glogp[q] * (1[a = n] - p[n]), before the common chain dz/du.  H is a sum over all key tiles: it is not reduced here but
+// read back from the forward pass (a.entropy, like a.lse), so the tile loop keeps its two barriers.  Zero cases are exact: an
+// infeasible node never enters (no 0 * -inf), a step before tstart or past the chunk has gent forced to 0, and a step whose
+// forward entropy is exactly 0 -- what the forward writes for a single feasible node -- takes no entropy gradient at all.
+// ENT = false is the kernel as it was: no extra load, register or branch.
+template <int RTT, bool HEADS, bool DYN = false, bool ENT = false>
 __global__ __launch_bounds__(512, 2) void k_reeval_bwd_logits(ReevalArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -934,6 +941,8 @@ __global__ __launch_bounds__(512, 2) void k_reeval_bwd_logits(ReevalArgs a)
             const bool live = qj >= 0 && tj >= a.tstart;
             const int act_l = (int)a.actions[qjc] - a.mc_koff;
             const float g_l = a.glogp[qjc], lse_l = derive_lse ? a.logp[qjc] : a.lse[qjc];
+            float ge_l = 0.0f, H_l = 0.0f;
+            if (ENT) { ge_l = a.gent[qjc]; H_l = a.entropy[qjc]; }
             wj.next(T);
             qjn = qi_of(wj);
             tjn = wj.t;
@@ -955,6 +964,7 @@ __global__ __launch_bounds__(512, 2) void k_reeval_bwd_logits(ReevalArgs a)
             const int act = qj >= 0 ? act_l : -1;
             const float g = live ? g_l : 0.0f;
             float lse = live ? lse_l : 0.0f;
+            const float H = H_l, ge = (ENT && live && H_l != 0.0f) ? ge_l : 0.0f;     // (H == 0: a forced step, no entropy gradient)
             float zr[4] = {0.f, 0.f, 0.f, 0.f}, dz[4] = {0.f, 0.f, 0.f, 0.f};
             if (wv < RTT) {
 #pragma unroll
@@ -977,7 +987,12 @@ __global__ __launch_bounds__(512, 2) void k_reeval_bwd_logits(ReevalArgs a)
                     const uint32_t w = (n0 >> 5) == 0 ? mb.x : (n0 >> 5) == 1 ? mb.y : (n0 >> 5) == 2 ? mb.z : mb.w;
                     const bool ok = (w >> ((n0 & 31) + G)) & 1u;
                     float du = 0.0f;
-                    if (ok && g != 0.0f) {
+                    if (ENT) {
+                        if (ok && (g != 0.0f || ge != 0.0f)) {
+                            const float lp = zr[r] - lse, p = fexp(lp);       // (a feasible node: lp is finite, p may underflow to 0)
+                            du = (g * ((n0 + G == act ? 1.0f : 0.0f) - p) - ge * (p * (lp + H))) * dz[r];
+                        }
+                    } else if (ok && g != 0.0f) {
                         const float p = fexp(zr[r] - lse);
                         du = g * ((n0 + G == act ? 1.0f : 0.0f) - p) * dz[r];
                     }
@@ -1618,6 +1633,9 @@ static int launch_bwd_t(const ReevalArgs& a, hipStream_t st)
     const bool dyn = a.dyn != nullptr;
     const size_t ldl = (4 * 16 * (size_t)TS + 8 * RTT * 256 + 2 * RE + 16 * RTT * DS + 16 + 32 + (dyn ? 2 * 16 * 16 * RTT + 128 + 2 * RE : 0)) * sizeof(float);
     auto kl = dyn ? k_reeval_bwd_logits<RTT, false, true> : a.heads ? k_reeval_bwd_logits<RTT, true> : k_reeval_bwd_logits<RTT, false>;
+    if (a.gent)         // the entropy term lives in its own instantiations: a NULL gent runs the kernels above, untouched
+        kl = dyn ? k_reeval_bwd_logits<RTT, false, true, true>
+                 : a.heads ? k_reeval_bwd_logits<RTT, true, false, true> : k_reeval_bwd_logits<RTT, false, false, true>;
     if (ldl > 64 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void*>(kl), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldl) != hipSuccess)
         return EAMRL_E_LAUNCH;
@@ -1676,7 +1694,7 @@ static int launch_bwd_mc(const ReevalArgs& a0, hipStream_t st)
 int launch_reeval_bwd(const ReevalArgs& a0, hipStream_t st)
 {
     if (a0.B <= 0 || a0.S <= 0 || a0.T <= 0) return 0;
-    if (a0.M > KCH) return launch_bwd_mc(a0, st);
+    if (a0.M > KCH) return a0.gent ? EAMRL_E_LAUNCH : launch_bwd_mc(a0, st);       // (gent with key chunks: refused by the caller)
     ReevalArgs a = a0;
     a.nkc = 1; a.mc_koff = 0; a.mc_mstride = 4;
     if (a.M <= 32) return launch_bwd_t<2>(a, st);

@@ -638,7 +638,7 @@ class ReevalPlan:
         self.slots = slots or {n: i for i, n in enumerate(["K", "V", "Lp", "Pa"] + (["Pb"] if has_pb else []))}
         self.E = E if E is not None else width // (5 if has_pb else 4)
         self.buf, self.has_pb, self.gctx, self.cvec = buf, has_pb, gctx, cvec
-        self.entropy = None
+        self.entropy = self.lse_ent = None
         self.want_entropy = bool(want_entropy)
         R, T = actions.shape
         if R != S * self.B:
@@ -725,17 +725,28 @@ class ReevalPlan:
             self.entropy = torch.empty(self.R, self.T, dtype=torch.float32, device=self.buf.device)
             if self.lse is None:        # (the rollout's log-probs stay untouched: the kernel writes into a scratch)
                 self.logp = torch.empty(self.R, self.T, dtype=torch.float32, device=self.buf.device)
+                # the normaliser of this pass, for a backward that is handed an entropy gradient (it reads lse and entropy as
+                # written here); a backward without one keeps recovering it from logp, as before
+                self.lse_ent = torch.empty(self.R, self.T, dtype=torch.float32, device=self.buf.device)
         s = self._struct()
+        if self.lse is None and self.want_entropy:
+            s.lse = _ptr(self.lse_ent)
         _lib.check(lib.eamrl_reeval_forward(C.byref(s), _stream(self.buf)), "eamrl_reeval_forward")
         return self.logp.view_as(self.logp)         # (a new tensor object, see above)
 
-    def backward(self, glogp):
-        """-> (dbuf [B, M, P*E], dgctx or None, dcvec or None)"""
+    def backward(self, glogp, gent=None):
+        """-> (dbuf [B, M, P*E], dgctx or None, dcvec or None).  gent [R, T] (optional): dL/d(entropy) per step, on a plan built
+        with want_entropy=True whose forward() has run (eamrl_reeval.gent: single-chunk graphs; the library refuses the rest)."""
         if self.planes:
             raise ValueError("reeval backward: operands side by side [B, M, P * E] (a plane-layout decoder cache serves the forward only)")
         lib = _lib.load()
         glogp = glogp.contiguous()
         _chk(glogp, "grad of logp", torch.float32, (self.R, self.T))
+        if gent is not None:
+            if not self.want_entropy or self.entropy is None:
+                raise ValueError("reeval backward: an entropy gradient needs a plan built with want_entropy=True whose forward() has run")
+            gent = gent.contiguous()
+            _chk(gent, "grad of entropy", torch.float32, (self.R, self.T))
         dev = self.buf.device
         dbuf = torch.zeros_like(self.buf)
         # (key chunks: per-chunk partials of dheads, then the per-chunk query gradients)
@@ -752,6 +763,10 @@ class ReevalPlan:
         s.dgctx, s.dCvec = _ptr(dg), _ptr(dc)
         self.ddyn = torch.zeros_like(self.dyn) if self.dyn is not None else None      # read by the caller (SDVRP)
         s.ddyn = _ptr(self.ddyn)
+        if gent is not None:
+            s.gent = _ptr(gent)
+            if self.lse is None:
+                s.lse = _ptr(self.lse_ent)
         _lib.check(lib.eamrl_reeval_backward(C.byref(s), _stream(self.buf)), "eamrl_reeval_backward")
         return dbuf, dg, dc
 

@@ -911,6 +911,7 @@ class AttentionModelPolicy(nn.Module):
                     self._want_heads = False        # (GraphedRollout calls _enqueue directly)
                 if "out" in p:          # beam search is host-driven and arrives finished (inference only)
                     return p["out"]
+                p["given_actions"] = actions is not None
                 out = self._finish(p)
             return self._attach_grad(out, p) if want_grad else out
         finally:
@@ -967,10 +968,18 @@ class AttentionModelPolicy(nn.Module):
                                or filtering or best):
             fl = None
         fh = p.get("final_heads") if fl is not None else None       # (heads are only used together with the rollout's log-probs)
+        # Given tours (actions=) with return_entropy: the entropy carries a graph too (PPO's entropy bonus, rl/ppo/ppo.py:168-209):
+        # its value stays the one computed above, its gradient is the re-evaluation's.  A sampled rollout keeps the detached
+        # entropy (the trainers only log it), and so does a filtered (top-k / top-p) or best-row re-evaluation.
+        want_ent = bool(p.get("given_actions")) and p["return_entropy"] and "entropy" in out and not filtering and not best
         re = evaluate_log_likelihood(self, p["td"], p["env"], p["final_actions"], num_starts=0 if best else p["S"],
                                      multistart=bool(p["pre"]), temperature=p["temperature"],
                                      tanh_clipping=p["tanh_clipping"], rollout_logp=fl, rollout_heads=fh,
-                                     top_k=int(p["top_k"] or 0), top_p=float(p["top_p"] or 0.0))
+                                     top_k=int(p["top_k"] or 0), top_p=float(p["top_p"] or 0.0), return_entropy=want_ent)
+        ent = None
+        if want_ent:
+            re, ent = re
+            ent = ent.sum(1)
         td_mask = p["td"].get("mask", None) if hasattr(p["td"], "get") else None
         if td_mask is not None:
             re = re.masked_fill(~td_mask, 0)
@@ -978,6 +987,8 @@ class AttentionModelPolicy(nn.Module):
             re = re.sum(1)
         out = dict(out)
         out["log_likelihood"] = out["log_likelihood"].detach() + (re - re.detach())     # native value, re-eval gradient
+        if ent is not None:
+            out["entropy"] = out["entropy"].detach() + (ent - ent.detach())
         return out
 
     def _enqueue(self, td, env, phase, calc_reward, return_actions, return_entropy, return_hidden, return_init_embeds,

@@ -651,10 +651,13 @@ def _filter_logits_(logits, act, top_k: int, top_p: float):
     return logits.masked_fill(drop, float("-inf"))
 
 
-def _logp_rows(env_name, t, static, act, nrep, multistart, H, temperature, clip, top_k=0, top_p=0.0, s_first=0):
+def _logp_rows(env_name, t, static, act, nrep, multistart, H, temperature, clip, top_k=0, top_p=0.0, s_first=0,
+               return_entropy=False):
     """Per-step log-probabilities [Rc, T] of the rows `act` (nrep whole start groups of the B instances, (s b) order).
     `t`: decoder_tensors; `static`: the instance tensors the masks are rebuilt from.  s_first: index of the rows' first start
-    group in the whole rollout (PolyNet: the strategy of a row is its start index modulo k)."""
+    group in the whole rollout (PolyNet: the strategy of a row is its start index modulo k).
+    return_entropy: -> (logp, entropy [Rc, T]), the entropy of every step's distribution from the same log-softmax
+    (calculate_entropy, rl4co/utils/ops.py:108-116, before its sum over the steps; 0 for the multistart column)."""
     emb, K, V, L = t["emb"], t["K"], t["V"], t["L"]
     B, M, E = emb.shape
     D = E // H
@@ -724,10 +727,17 @@ def _logp_rows(env_name, t, static, act, nrep, multistart, H, temperature, clip,
     logits = logits.masked_fill(~mask, float("-inf")) / temperature
     if top_k > 0 or 0.0 < top_p < 1.0:
         logits = _filter_logits_(logits, act, top_k, top_p)
-    logp = F.log_softmax(logits, dim=-1).gather(-1, act[..., None]).squeeze(-1)
+    lsm = F.log_softmax(logits, dim=-1)
+    logp = lsm.gather(-1, act[..., None]).squeeze(-1)
     if multistart:   # the start node is not a decision (decoding.py:318-324)
         logp = torch.cat((torch.zeros_like(logp[:, :1]), logp[:, 1:]), 1)
         # steps t >= 1 were evaluated with the state after the start action: column t uses prefix a_{<t} as built
+    if return_entropy:      # infeasible nodes: log p = -inf, p = 0 -> their term is 0 (nan_to_num in the reference), no 0 * inf
+        lp = lsm.masked_fill(~mask, 0.0)
+        ent = -(lp.exp().masked_fill(~mask, 0.0) * lp).sum(-1)
+        if multistart:
+            ent = torch.cat((torch.zeros_like(ent[:, :1]), ent[:, 1:]), 1)
+        return logp, ent
     return logp
 
 
@@ -837,27 +847,37 @@ def replay_states(policy, td, actions, S: int, multistart: bool):
 
 
 class _NativeReeval(torch.autograd.Function):
-    """logp [R, T] = eamrl_reeval_forward(K, V, Lp, Pa, Pb, gctx, cvec | replayed states); backward = eamrl_reeval_backward."""
+    """logp [R, T] = eamrl_reeval_forward(K, V, Lp, Pa, Pb, gctx, cvec | replayed states); backward = eamrl_reeval_backward.
+    meta["want_entropy"]: -> (logp [R, T], entropy [R, T]), and both upstream gradients go into ONE backward call
+    (eamrl_reeval.glogp / .gent)."""
 
     @staticmethod
     def forward(ctx, K, V, Lp, Pa, Pb, gctx, cvec, meta, dyn=None):
         from . import ops
 
+        want_entropy = bool(meta.get("want_entropy"))
         parts = [K, V, Lp, Pa] + ([Pb] if Pb is not None else [])
         buf = torch.cat([x.detach() for x in parts], -1).contiguous()
         plan = ops.ReevalPlan(buf, Pb is not None, None if gctx is None else gctx.detach().contiguous(),
                               None if cvec is None else cvec.detach().contiguous(), meta["idxA"], meta["idxB"], meta["sc"],
                               meta["maskbits"], meta["actions"], meta["S"], meta["tstart"], meta["clip"], meta["temp"],
                               rollout_logp=meta.get("rollout_logp"), rollout_heads=meta.get("rollout_heads"),
-                              rem=meta.get("rem"), dyn=None if dyn is None else dyn.detach().contiguous())
+                              rem=meta.get("rem"), dyn=None if dyn is None else dyn.detach().contiguous(),
+                              want_entropy=want_entropy)
         ctx.plan = plan
         ctx.has = (Pb is not None, gctx is not None, cvec is not None, dyn is not None)
-        return plan.forward()
+        logp = plan.forward()
+        if want_entropy:
+            ctx.set_materialize_grads(False)        # an unused output hands None to the backward, not a tensor of zeros
+            return logp, plan.entropy.view_as(plan.entropy)
+        return logp
 
     @staticmethod
-    def backward(ctx, g):
+    def backward(ctx, g, gent=None):
         plan = ctx.plan
-        dbuf, dg, dc = plan.backward(g)
+        if g is None:
+            g = torch.zeros(plan.R, plan.T, dtype=torch.float32, device=plan.buf.device)
+        dbuf, dg, dc = plan.backward(g, gent)
         plan.heads = None           # 5 .. 10 GB at the POMO sizes: not kept for as long as the graph object lives
         E = plan.E
         sl = [dbuf[..., i * E:(i + 1) * E] for i in range(5 if ctx.has[0] else 4)]
@@ -865,9 +885,11 @@ class _NativeReeval(torch.autograd.Function):
                 dc if ctx.has[2] else None, None, plan.ddyn if ctx.has[3] else None)
 
 
-def _evaluate_native(policy, t, td, actions, S, multistart, temperature, clip, rollout_logp=None, rollout_heads=None):
+def _evaluate_native(policy, t, td, actions, S, multistart, temperature, clip, rollout_logp=None, rollout_heads=None,
+                     return_entropy=False):
     """Differentiable log-probs [R, T]: the weight folds (Lp = L Wout, Pa / Pb = emb x halves of project_context, state
-    columns) as small autograd GEMMs on the decoder tensors `t`, everything per (row, step) in the HIP kernels."""
+    columns) as small autograd GEMMs on the decoder tensors `t`, everything per (row, step) in the HIP kernels.
+    return_entropy: -> (logp, entropy [R, T]), both with a graph (single-chunk graphs: the backward kernel's limit)."""
     E = t["emb"].shape[-1]
     Wctx = t["Wctx"]
     Lp = _linear(t["L"], t["Wout"].t().contiguous())
@@ -878,7 +900,9 @@ def _evaluate_native(policy, t, td, actions, S, multistart, temperature, clip, r
         cvec = F.linear(t["placeholder"][None], Wctx) if meta["placeholder"] else None            # [1, E]
     else:
         cvec = Wctx[:, E:].t()                                                                      # [NC, E] state columns
-    meta.update(actions=actions.contiguous(), S=S, clip=float(clip), temp=float(temperature))
+    meta.update(actions=actions.contiguous(), S=S, clip=float(clip), temp=float(temperature), want_entropy=bool(return_entropy))
+    if return_entropy:          # the forward kernel always runs: the backward reads its lse and entropy
+        rollout_logp = None
     if rollout_logp is not None:
         meta["rollout_logp"] = rollout_logp.detach().to(torch.float32).contiguous()
         if rollout_heads is not None:           # the rollout kernel's glimpse outputs of these very steps: not recomputed
@@ -892,7 +916,7 @@ def _evaluate_native(policy, t, td, actions, S, multistart, temperature, clip, r
 
 def evaluate_log_likelihood(policy, td, env, actions, num_starts: int = 0, temperature=None, tanh_clipping=None,
                             chunk_rows: int = 4096, multistart=None, checkpoint=None, native=None, rollout_logp=None,
-                            rollout_heads=None, top_k: int = 0, top_p: float = 0.0):
+                            rollout_heads=None, top_k: int = 0, top_p: float = 0.0, return_entropy: bool = False):
     """Differentiable per-step log-probabilities of `actions` [R, T] (R = B or S*B rows in (s b) order).  native
     (default: where supported -- TSP / CVRP / PCTSP / OP / CVRPTW, graphs up to 112 nodes): forward and backward of the
     decode steps run in the HIP re-evaluation kernels; otherwise (and as the cross-check) PyTorch autograd ops.  multistart
@@ -902,7 +926,13 @@ def evaluate_log_likelihood(policy, td, env, actions, num_starts: int = 0, tempe
     the rollout kernel produced for exactly these actions with this policy -- the HIP forward pass is then skipped (the
     returned values are these; the backward recovers each step's normaliser from them).  top_k / top_p: the rollout filtered
     its logits (process_logits, decoding.py:170-176): the same entries are dropped here, as a fixed mask, before the
-    log-softmax (PyTorch path).  Returns logp [R, T]."""
+    log-softmax (PyTorch path).  Returns logp [R, T]; with return_entropy=True (logp, entropy [R, T]) -- each step's
+    calculate_entropy term (rl4co/utils/ops.py:108-116, before the sum over the steps), with a graph like logp: from the HIP
+    kernels where they serve the shape (up to 112 nodes: the entropy gradient is not built for key chunks), from the PyTorch
+    path's log-softmax otherwise.  Not under top_k / top_p (NotImplementedError)."""
+    if return_entropy and (top_k > 0 or 0.0 < top_p < 1.0):
+        raise NotImplementedError("evaluate_log_likelihood: a differentiable entropy under top_k / top_p is not built "
+                                  "(the entropy of a filtered distribution stays the rollout's step loop)")
     temperature = policy.temperature if temperature is None else temperature
     clip = policy.tanh_clipping if tanh_clipping is None else tanh_clipping
     H = policy.decoder.num_heads
@@ -916,11 +946,12 @@ def evaluate_log_likelihood(policy, td, env, actions, num_starts: int = 0, tempe
     env_name = policy.env_name
     filtering = top_k > 0 or 0.0 < top_p < 1.0
     if native is None:
-        native = native_reeval_supported(policy, M) and not filtering
+        native = native_reeval_supported(policy, M) and not filtering and not (return_entropy and M > 112)
     if native:
         if filtering:
             raise ValueError("evaluate_log_likelihood: the native re-evaluation kernels do not filter (top_k / top_p)")
-        return _evaluate_native(policy, t, td, actions, S, multistart, temperature, clip, rollout_logp, rollout_heads)
+        return _evaluate_native(policy, t, td, actions, S, multistart, temperature, clip, rollout_logp, rollout_heads,
+                                return_entropy)
     static = {k: td[k] for k in _STATE_KEYS[env_name]}
     # rows are processed in chunks of whole start-groups so that memory stays bounded ([rows, H, T, M] scores)
     starts_per_chunk = max(1, chunk_rows // B)
@@ -929,14 +960,17 @@ def evaluate_log_likelihood(policy, td, env, actions, num_starts: int = 0, tempe
 
     def chunk(c, *tensors):
         s0, s1 = bounds[c]
-        return _logp_rows(env_name, dict(zip(names, tensors)), static, actions[s0 * B:s1 * B], s1 - s0, multistart, H,
-                          temperature, clip, top_k, top_p, s_first=s0)
+        out = _logp_rows(env_name, dict(zip(names, tensors)), static, actions[s0 * B:s1 * B], s1 - s0, multistart, H,
+                         temperature, clip, top_k, top_p, s_first=s0, return_entropy=return_entropy)
+        return torch.cat(out, 1) if return_entropy else out       # (one tensor per chunk: logp | entropy side by side)
 
     if checkpoint is None:      # ~6 live [rows, H, T, M] fp32 tensors per chunk if the graph is kept
         checkpoint = len(bounds) > 1 and 24.0 * R * H * T * M > 8e9
     if checkpoint and torch.is_grad_enabled():
-        return _ChunkedReeval.apply(chunk, len(bounds), *[t[k] for k in names])
-    return torch.cat([chunk(c, *[t[k] for k in names]) for c in range(len(bounds))], 0)
+        res = _ChunkedReeval.apply(chunk, len(bounds), *[t[k] for k in names])
+    else:
+        res = torch.cat([chunk(c, *[t[k] for k in names]) for c in range(len(bounds))], 0)
+    return (res[:, :T], res[:, T:]) if return_entropy else res
 
 
 def attach_log_likelihood_grad(policy, td, env, actions, native_logp, num_starts: int = 0, multistart=None,
@@ -949,14 +983,21 @@ def attach_log_likelihood_grad(policy, td, env, actions, native_logp, num_starts
     return native_logp.detach() + (re - re.detach())
 
 
-def reinforce_loss(policy, env, td, baseline: str = "shared", num_starts: int = 0, decode_type: str = None,
+def reinforce_loss(policy, env, td, baseline: str = "shared", num_starts: int = 0, decode_type: str = None, critic=None,
                    **rollout_kwargs):
     """One REINFORCE forward as the reference's trainers run it (REINFORCE.shared_step + calculate_loss,
     reinforce.py:59-106; POMO.shared_step, pomo/model.py:89-112): `policy(td, env, phase="train")` under autograd ->
     loss = -((reward - bl) * log_likelihood).mean().
 
-    baseline: "shared" (POMO: mean over the starts of an instance, needs num_starts > 1), "mean" (batch mean) or
-    "no".  Returns dict(loss, reward, log_likelihood, actions, ...)."""
+    baseline: "shared" (POMO: mean over the starts of an instance, needs num_starts > 1), "mean" (batch mean), "no", or
+    "critic" (CriticBaseline.eval, baselines.py:140-159: v = critic(td).squeeze(-1); the baseline is v.detach() and
+    F.mse_loss(v, reward) is added to the loss; `critic`: a critic.CriticNetwork, single rows per instance).
+    Returns dict(loss, reward, log_likelihood, actions, ...)."""
+    if baseline == "critic":
+        if critic is None:
+            raise ValueError("reinforce_loss(baseline='critic') needs critic= (critic.create_critic_from_actor(policy))")
+        if num_starts > 1:
+            raise NotImplementedError("reinforce_loss(baseline='critic') with num_starts > 1 is not built")
     if decode_type is None:
         decode_type = "multistart_sampling" if num_starts > 1 else "sampling"
     kw = dict(rollout_kwargs)
@@ -974,6 +1015,13 @@ def reinforce_loss(policy, env, td, baseline: str = "shared", num_starts: int = 
         loss = -(adv * unbatchify(ll, num_starts)).mean()
     elif baseline == "mean":
         loss = -((reward - reward.mean()) * ll).mean()
+    elif baseline == "critic":
+        with torch.enable_grad():
+            v = critic(td).squeeze(-1)
+        bl_loss = F.mse_loss(v, reward)
+        loss = -((reward - v.detach()) * ll).mean() + bl_loss           # reinforce.py:103-106: reinforce_loss + bl_loss
+        return {"loss": loss, "reward": reward, "log_likelihood": ll, "actions": actions, "logp_steps": logp,
+                "native_log_likelihood": ll.detach(), "bl_val": v.detach(), "bl_loss": bl_loss}
     else:
         loss = -(reward * ll).mean()
     return {"loss": loss, "reward": reward, "log_likelihood": ll, "actions": actions, "logp_steps": logp,
@@ -1157,3 +1205,128 @@ class PolicyGradientStep:
 
             allreduce_buffers(self.policy)
         return out
+
+
+# ------------------------------------------------------------------------------------------------------------
+# PPO (rl4co/models/rl/ppo/ppo.py:61-235, rl4co/models/zoo/amppo/model.py)
+# ------------------------------------------------------------------------------------------------------------
+def ppo_loss_terms(ll_new, ll_old, reward, value, entropy, clip_range: float = 0.2, vf_lambda: float = 0.5,
+                   entropy_lambda: float = 0.0, normalize_adv: bool = False) -> dict:
+    """The loss of one PPO mini-batch, ppo.py:177-209 line by line.  ll_new [b] (summed log-likelihood under the current
+    policy, with a graph), ll_old [b] (the rollout's), reward [b] or [b, 1], value [b, 1] (the critic's, with a graph),
+    entropy [b].  -> dict(loss, surrogate_loss, value_loss, entropy = entropy.mean())."""
+    previous_reward = reward.view(-1, 1)
+    ratio = torch.exp(ll_new - ll_old).view(-1, 1)                      # [batch, 1]
+    adv = previous_reward - value.detach()
+    if normalize_adv:
+        adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+    surrogate_loss = -torch.min(ratio * adv, torch.clamp(ratio, 1 - clip_range, 1 + clip_range) * adv).mean()
+    value_loss = F.huber_loss(value, previous_reward)
+    ent = entropy.mean()
+    loss = surrogate_loss + vf_lambda * value_loss - entropy_lambda * ent
+    return {"loss": loss, "surrogate_loss": surrogate_loss, "value_loss": value_loss, "entropy": ent}
+
+
+def _ppo_mini_batch_size(mini_batch_size):
+    """The constructor's rules and warnings of ppo.py:87-101."""
+    import logging
+
+    log = logging.getLogger(__name__)
+    if isinstance(mini_batch_size, bool) or not isinstance(mini_batch_size, (int, float)):
+        raise ValueError("mini_batch_size must be an integer or a float.")
+    if isinstance(mini_batch_size, float) and (mini_batch_size <= 0 or mini_batch_size > 1):
+        log.warning("mini_batch_size must be an integer or a float in the range (0, 1], got %s. Setting mini_batch_size to %s.",
+                    mini_batch_size, 0.25)
+        mini_batch_size = 0.25
+    if isinstance(mini_batch_size, int) and mini_batch_size <= 0:
+        log.warning("mini_batch_size must be an integer or a float in the range (0, 1], got %s. Setting mini_batch_size to %s.",
+                    mini_batch_size, 128)
+        mini_batch_size = 128
+    return mini_batch_size
+
+
+def _ppo_resolve_mini_batch(mini_batch_size, batch_size: int) -> int:
+    """ppo.py:139-148: a float is a fraction of the batch, the size is capped at the batch."""
+    mb = int(batch_size * mini_batch_size) if isinstance(mini_batch_size, float) else int(mini_batch_size)
+    if mb <= 0:
+        raise ValueError(f"mini_batch_size={mini_batch_size!r} of a batch of {batch_size} is an empty mini-batch")
+    return min(mb, batch_size)
+
+
+class PPOStep:
+    """One training step of the reference's PPO (ppo.py:128-232; AMPPO, zoo/amppo/model.py, is this with the attention model):
+
+        no_grad: out = policy(td.clone(), env, phase="train")           -> actions, reward, old log-likelihood
+        ppo_epochs x shuffled mini-batches (the last partial one kept, as a DataLoader without drop_last):
+            out = policy(sub.clone(), env, phase="train", actions=A[idx], return_entropy=True, return_sum_log_likelihood=False)
+            value = critic(sub);  ppo_loss_terms;  zero grads, backward, ONE flat all-reduce over policy + critic gradients
+            (mean over the ranks), clip the global norm to max_grad_norm, optimizer.step()
+
+    The tours are fixed after the rollout, so every mini-batch pass is the teacher-forced re-evaluation: log-likelihood AND
+    entropy come with a graph from the native kernels where they serve the env and size (eamrl_reeval_forward / _backward with
+    eamrl_reeval.gent), from the PyTorch expression otherwise (PDP, graphs above 112 nodes).  Depot-padded columns of the
+    action rows are steps with one feasible node: log-prob 0, entropy 0, no gradient.
+    Defaults are the reference's (ppo.py:61-111).  A PolyNet policy has no re-evaluation with given actions on this path."""
+
+    def __init__(self, policy, env, critic=None, clip_range: float = 0.2, ppo_epochs: int = 2, mini_batch_size=0.25,
+                 vf_lambda: float = 0.5, entropy_lambda: float = 0.0, normalize_adv: bool = False, max_grad_norm: float = 0.5,
+                 lr: float = 1e-4, optimizer=None, generator=None):
+        from .critic import create_critic_from_actor
+        from .dist import FlatGradBuffer, broadcast_module_state
+
+        if getattr(policy.decoder, "is_polynet", False):
+            raise NotImplementedError("PPOStep: a PolyNet policy has no re-evaluation with given actions (actions=) on this path")
+        if critic is None:
+            critic = create_critic_from_actor(policy)
+        self.policy, self.env, self.critic = policy, env, critic
+        self.clip_range, self.ppo_epochs = float(clip_range), int(ppo_epochs)
+        self.mini_batch_size = _ppo_mini_batch_size(mini_batch_size)
+        self.vf_lambda, self.entropy_lambda, self.normalize_adv = float(vf_lambda), float(entropy_lambda), bool(normalize_adv)
+        self.max_grad_norm = max_grad_norm
+        self.generator = generator
+        self.modules = nn.ModuleList([policy, critic])
+        broadcast_module_state(self.modules, src=0)          # before the optimizer reads the parameters
+        self.grads = FlatGradBuffer(self.modules)
+        self.optimizer = optimizer or torch.optim.Adam(self.modules.parameters(), lr=lr)
+
+    def partition(self, batch_size: int):
+        """One epoch's mini-batches: a permutation of the batch cut into consecutive pieces -> list of index tensors (CPU)."""
+        mb = _ppo_resolve_mini_batch(self.mini_batch_size, batch_size)
+        perm = torch.randperm(batch_size, generator=self.generator)
+        return [perm[i:i + mb] for i in range(0, batch_size, mb)]
+
+    def mini_batch_terms(self, sub, actions, ll_old, reward) -> dict:
+        """ppo.py:168-209 on one mini-batch: -> ppo_loss_terms(...) plus ll [b, T], entropy [b] and value [b, 1] (graphs attached)."""
+        with torch.enable_grad():
+            out = self.policy(sub.clone(), self.env, phase="train", actions=actions, return_entropy=True,
+                              return_sum_log_likelihood=False)
+            ll, entropy = out["log_likelihood"], out["entropy"]
+            value = self.critic(sub)
+            terms = ppo_loss_terms(ll.sum(dim=-1), ll_old, reward, value, entropy, self.clip_range, self.vf_lambda,
+                                   self.entropy_lambda, self.normalize_adv)
+        terms.update(ll=ll, entropy_rows=entropy, value=value)
+        return terms
+
+    def __call__(self, td) -> dict:
+        with torch.no_grad():
+            out = self.policy(td.clone(), self.env, phase="train")
+        actions, reward, ll_old = out["actions"], out["reward"], out["log_likelihood"]
+        B = actions.shape[0]
+        steps, terms = 0, None
+        for _ in range(self.ppo_epochs):
+            for idx in self.partition(B):
+                sub = td[idx]                       # (sub_td of the reference's DataLoader: the rows of the instance tensors)
+                idx = idx.to(actions.device)
+                terms = self.mini_batch_terms(sub, actions[idx].contiguous(), ll_old[idx], reward[idx])
+                self.grads.zero_()
+                terms["loss"].backward()
+                if not self.grads.attached():
+                    raise RuntimeError("PPOStep: p.grad is no longer a view of the flat buffer (zero_grad(set_to_none)?)")
+                self.grads.allreduce(average=True)
+                if self.max_grad_norm is not None:
+                    self.grads.clip_(self.max_grad_norm)
+                self.optimizer.step()
+                steps += 1
+        return {"loss": terms["loss"].detach(), "surrogate_loss": terms["surrogate_loss"].detach(),
+                "value_loss": terms["value_loss"].detach(), "entropy": terms["entropy"].detach(), "reward": reward,
+                "actions": actions, "optimizer_steps": steps}

@@ -431,12 +431,27 @@ typedef struct eamrl_reeval {
      * per-chunk query gradients).  The mc_* fields are set by the library. */
     int nkc; float* scratch;
     int mc_koff, mc_mstride; float *mc_part_o, *mc_part_s, *mc_gstat, *mc_lpart, *mc_rsq, *mc_dq;
+    /* backward, optional (NULL: the backward exactly as without this field): gent [R][T] = dL/d(entropy) of step t of row r --
+     * the entropy bonus of PPO's loss, `- entropy_lambda * entropy.mean()`  [models/rl/ppo/ppo.py:205-209].  With
+     * z_n = clip tanh(u_n) / temp over the feasible nodes, p = softmax(z), H = -sum_n p_n log p_n  [calculate_entropy,
+     * utils/ops.py:108-116, before its sum over the steps], the logit gradient gains
+     *     gent * dH/dz_n = gent * (-p_n (log p_n + H))
+     * next to glogp * (1[a = n] - p_n); both pass through the same chain clip (1 - tanh^2) / (sqrt(E) temp) (the plain scale
+     * when clip == 0) and everything downstream (dheads -> dK dV dLp dPa dPb dgctx dCvec ddyn) follows unchanged.
+     * Exact zeros, never NaN: an infeasible node (p_n = 0) never enters the sum, steps t < tstart take no gradient, and a step
+     * with a single feasible node (the forward wrote H = 0 for it; p = 1) takes none either.
+     * H and the normaliser are NOT reduced again: the backward reads `entropy` and `lse` as eamrl_reeval_forward wrote them
+     * on this same struct.  eamrl_reeval_backward returns -1 before launching anything when gent is set and
+     *   - entropy or lse is NULL (no forward pass ran), or
+     *   - the graph needs key chunks (M > 112 / nkc > 1).
+     * eamrl_reeval_backward_lp ignores the field. */
+    const float* gent;
 } eamrl_reeval;
 
 int eamrl_reeval_supported(int M, int E, int H);                  /* 1 for M <= 112 (1024 with key chunks), E = 128, H = 8 */
 int64_t eamrl_reeval_scratch_floats(int64_t R, int T, int M);     /* 0 for M <= 112 */
 int eamrl_reeval_forward(const eamrl_reeval* p, void* stream);    /* -> logp, lse (lse may be NULL) [, entropy] */
-int eamrl_reeval_backward(const eamrl_reeval* p, void* stream);   /* glogp, lse (or rollout logp) -> dK dV dLp dPa dPb dgctx dCvec */
+int eamrl_reeval_backward(const eamrl_reeval* p, void* stream);   /* glogp [, gent], lse (or rollout logp) -> dK dV dLp dPa dPb dgctx dCvec */
 /* d(sum glogp * logp)/dLp only: the gradient an adapted logit key needs (EAS-Emb).  Same struct as
  * eamrl_reeval_backward; reads K V Pa Pb gctx Cvec idx* sc only when p->heads == NULL (glimpse recomputed); writes
  * nothing but dLp (accumulated, +=, row stride ldg).  dK dV dPa dPb dgctx dCvec dheads may be NULL.
