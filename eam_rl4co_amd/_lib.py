@@ -70,6 +70,12 @@ class State(C.Structure):
                 ("time", _vp), ("tw", _vp), ("dur", _vp), ("heads_out", _vp), ("to_deliver", _vp)]
 
 
+class EasLayer(C.Structure):
+    """struct eamrl_eas_layer"""
+    _fields_ = [("W1", _vp), ("b1", _vp), ("W2", _vp), ("b2", _vp), ("forced", _vp), ("t_forced", C.c_int32),
+                ("dW1", _vp), ("db1", _vp), ("dW2", _vp), ("db2", _vp)]
+
+
 # name -> argtypes (all return int unless listed in _RESTYPES); mirrors include/eamrl.h one to one
 PROTOTYPES = {
     "eamrl_version": [],
@@ -140,6 +146,10 @@ PROTOTYPES = {
                                  _f32, _i32, _vp, _vp, _vp, _vp, _vp],
     "eamrl_am_rollout_polynet_seeded": [_i32, C.POINTER(Cache), C.POINTER(State), C.POINTER(PolyNet), _i64, C.c_uint64, _vp, _f32,
                                         _f32, _i32, _vp, _vp, _vp, _vp, _vp],
+    "eamrl_rollout_eas_layer_supported": [_i32, C.POINTER(Cache), _i64],
+    "eamrl_am_rollout_eas_layer": [_i32, C.POINTER(Cache), C.POINTER(State), C.POINTER(EasLayer), _i64, _i32, _vp, _vp, _i32, _i32,
+                                   C.c_uint64, _vp, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp],
+    "eamrl_eas_layer_backward": [C.POINTER(Reeval), C.POINTER(EasLayer), _vp],
     "eamrl_tour_length": [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp],
     "eamrl_sum_logp": [_vp, _i64, _vp, _i64, _i32, _vp],
     "eamrl_tsp_two_opt": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp],

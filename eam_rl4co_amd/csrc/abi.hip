@@ -888,6 +888,74 @@ __attribute__((visibility("default"))) int eamrl_am_rollout_polynet_seeded(int e
                            0, tanh_clip, temperature, t_max, actions, logps, steps_out, status, true, seed, seed_dev, stream);
 }
 
+// EAS-Lay (zoo/eas/decoder.py:35-126): the rollout with a per-instance residual layer, and the layer's backward
+static bool eas_layer_shape_ok(int env, const eamrl_cache* c, int64_t R)
+{
+    if (env != EAMRL_ENV_TSP && env != EAMRL_ENV_CVRP) return false;
+    if (c->B <= 0 || R <= 0 || R % c->B != 0 || R > 0x7fffffffLL) return false;
+    DecArgs a{};
+    a.B = c->B; a.M = c->M; a.E = c->E; a.H = c->H; a.ld = c->ld; a.R = R;
+    return rollout_ms_lay_supports(env, a, true);
+}
+
+__attribute__((visibility("default"))) int eamrl_rollout_eas_layer_supported(int env, const eamrl_cache* cache_host, int64_t R)
+{
+    if (!cache_host || g_debug[11]) return 0;
+    return eas_layer_shape_ok(env, cache_host, R) ? 1 : 0;
+}
+
+__attribute__((visibility("default"))) int eamrl_am_rollout_eas_layer(int env, const eamrl_cache* cache_host,
+                                                                     const eamrl_state* state_host, const eamrl_eas_layer* layer,
+                                                                     int64_t R, int mode, const float* noise,
+                                                                     const int64_t* given, int t_given, int seeded, uint64_t seed,
+                                                                     const uint64_t* seed_dev, float tanh_clip, float temperature,
+                                                                     int t_max, int64_t* actions, float* logps,
+                                                                     int32_t* steps_out, uint32_t* status, void* stream)
+{
+    const char* what = "eamrl_am_rollout_eas_layer";
+    REQUIRE(cache_host && state_host && layer, what);
+    REQUIRE(!seeded || mode == EAMRL_SAMPLE, "eamrl_am_rollout_eas_layer (seeded: mode must be EAMRL_SAMPLE)");
+    DecArgs a;
+    int rc = fill_args(what, env, cache_host, state_host, R, mode, noise, given, tanh_clip, temperature, 0, 0.0, status, a, seeded != 0);
+    if (rc) return rc;
+    REQUIRE(layer->W1 && layer->b1 && layer->W2 && layer->b2, what);
+    REQUIRE(((uintptr_t)layer->W1 % 16 == 0) && ((uintptr_t)layer->b1 % 16 == 0) && ((uintptr_t)layer->W2 % 16 == 0) &&
+            ((uintptr_t)layer->b2 % 16 == 0), what);
+    REQUIRE(!layer->forced || layer->t_forced > 0, what);
+    REQUIRE(env == EAMRL_ENV_TSP || env == EAMRL_ENV_CVRP, "eamrl_am_rollout_eas_layer (env: TSP or CVRP)");
+    REQUIRE(a.M <= 112, "eamrl_am_rollout_eas_layer (M <= 112)");
+    REQUIRE(R / a.B >= 2 && R / a.B <= 128, "eamrl_am_rollout_eas_layer (2 <= rows per instance <= 128)");
+    REQUIRE(eas_layer_shape_ok(env, cache_host, R), "eamrl_am_rollout_eas_layer (E = 128, H = 8, 2 <= M <= 112)");
+    REQUIRE(actions && logps && steps_out && a.done && t_max > 0, what);
+    if (env == EAMRL_ENV_CVRP) REQUIRE(a.visited && a.demand, what);
+    if (mode == EAMRL_EVALUATE) REQUIRE(t_given > 0, what);
+    REQUIRE(!a.heads_out || (uintptr_t)a.heads_out % 16 == 0, what);
+    a.fuse_env = 1; a.t_max = t_max; a.t_given = t_given;
+    a.action = actions; a.logp = logps; a.steps_out = steps_out;
+    if (seeded) { a.seed = seed; a.seed_dev = seed_dev; a.use_rng = 1; }
+    REQUIRE(rollout_ms_lay_supports(env, a, false), what);
+    const LayArgs ly{layer->W1, layer->b1, layer->W2, layer->b2, layer->forced, layer->t_forced};
+    return launched(launch_rollout_ms_lay(env, a, ly, (hipStream_t)stream), what);
+}
+
+__attribute__((visibility("default"))) int eamrl_eas_layer_backward(const eamrl_reeval* p, const eamrl_eas_layer* layer, void* stream)
+{
+    const char* what = "eamrl_eas_layer_backward";
+    REQUIRE(p && layer, what);
+    REQUIRE(p->M >= 1 && p->M <= 112 && p->nkc <= 1, "eamrl_eas_layer_backward (M <= 112, single key chunk)");
+    REQUIRE(p->dyn == nullptr && p->rem == nullptr, "eamrl_eas_layer_backward (dyn == NULL: no dynamic embedding)");
+    REQUIRE(p->heads != nullptr, "eamrl_eas_layer_backward (heads != NULL: the rollout's glimpse outputs are required)");
+    REQUIRE(p->heads_T > 0 && (uintptr_t)p->heads % 16 == 0, what);
+    REQUIRE(p->Lp && p->maskbits && p->actions && p->logp && p->glogp, what);
+    REQUIRE(p->B > 0 && p->S > 0 && p->T > 0 && p->R == p->B * p->S && p->nchunk >= 1 && p->nchunk <= p->S, what);
+    REQUIRE(p->ld >= 128 && p->ld % 4 == 0 && p->temp > 0.0f && p->tstart >= 0, what);
+    REQUIRE((uintptr_t)p->maskbits % 16 == 0 && p->R * (int64_t)p->T < (int64_t)1 << 31 && p->B * (int64_t)p->nchunk < (int64_t)1 << 31, what);
+    REQUIRE(layer->W1 && layer->b1 && layer->W2 && layer->b2 && layer->dW1 && layer->db1 && layer->dW2 && layer->db2, what);
+    REQUIRE(((uintptr_t)layer->W1 % 16 == 0) && ((uintptr_t)layer->b1 % 16 == 0) && ((uintptr_t)layer->W2 % 16 == 0) &&
+            ((uintptr_t)layer->b2 % 16 == 0), what);
+    return launched(launch_eas_layer_bwd(*p, *layer, (hipStream_t)stream), what);
+}
+
 __attribute__((visibility("default"))) int eamrl_tour_length(const float* locs, const int64_t* actions, float* reward,
                                                             int64_t R, int64_t B, int M, int T, int with_depot,
                                                             void* stream)

@@ -142,6 +142,14 @@ __device__ __forceinline__ void w_gemm(const f32x4 (&w)[PQ], const float* hp, f3
 
 __device__ __forceinline__ PolyArgs poly_args() { return PolyArgs{}; }
 __device__ __forceinline__ PolyArgs poly_args(const PolyArgs& p) { return p; }
+__device__ __forceinline__ PolyArgs poly_args(const LayArgs&) { return PolyArgs{}; }
+__device__ __forceinline__ LayArgs lay_args() { return LayArgs{}; }
+__device__ __forceinline__ LayArgs lay_args(const PolyArgs&) { return LayArgs{}; }
+__device__ __forceinline__ LayArgs lay_args(const LayArgs& p) { return p; }
+// which case the trailing argument pack selects: 0 = plain, 1 = PolyNet, 2 = EAS-Lay
+template <typename... PA> struct pack_kind { static constexpr int v = 0; };
+template <> struct pack_kind<PolyArgs> { static constexpr int v = 1; };
+template <> struct pack_kind<LayArgs> { static constexpr int v = 2; };
 
 // CC: the node-chunk length ceil(M / 4) as a compile-time value (0: run time).  With it every "does k-step t touch chunk g"
 // decision folds away; left to run time the ~100 uniform conditions are hoisted out of the loops into SGPRs that spill
@@ -151,12 +159,17 @@ __device__ __forceinline__ PolyArgs poly_args(const PolyArgs& p) { return p; }
 // POLY (PolyNet, nn/attention.py:476-555): between the glimpse and the logits every 16-query tile goes through
 //   g = heads Wout^T;  h = relu(W1[:, :E] g + ctab[strategy]);  y = g + (W2 h + b2)
 // and the logits are y . L -- the caller hands the UNFOLDED logit key in a.Lp.  See the block behind the glimpse barrier.
-// It is a trailing parameter pack so that the plain kernels keep their argument list: PA is empty, or one PolyArgs.
+// LAY (EAS-Lay, zoo/eas/nn.py:5-30 at zoo/eas/decoder.py:12-32): the heads tile goes through the residual layer of the workgroup's
+//   own instance,  y = h + relu(h W1[b] + b1[b]) W2[b] + b2[b],  and the logits are y . Lp (the fold stays valid: the layer sits
+//   before project_out).  heads_out keeps the pre-layer h.  See the second block behind the glimpse barrier.
+// It is a trailing parameter pack so that the plain kernels keep their argument list: PA is empty, one PolyArgs or one LayArgs.
 template <int RTT, int CC, int ENV, typename... PA>
 __global__ __launch_bounds__(512, 2) void k_rollout_ms_mfma(DecArgs a, int S, int nsplit, PA... pa)
 {
-    constexpr bool POLY = sizeof...(PA) == 1;
+    constexpr bool POLY = pack_kind<PA...>::v == 1;
+    constexpr bool LAY = pack_kind<PA...>::v == 2;
     const PolyArgs pn = poly_args(pa...);
+    const LayArgs ly = lay_args(pa...);
     constexpr bool TW = ENV == EAMRL_ENV_CVRPTW;        // CVRP + clock and time windows
     constexpr bool CV = ENV == EAMRL_ENV_CVRP || TW;    // vehicle load against the demands
     constexpr bool PC = ENV == EAMRL_ENV_PCTSP;         // prize collecting: used = collected prize, cap = required prize
@@ -552,8 +565,48 @@ __global__ __launch_bounds__(512, 2) void k_rollout_ms_mfma(DecArgs a, int S, in
             // barrier.  (Pieces of eight: 9 VGPRs to scratch at 112 nodes.)
             f32x4 wa[PQ], wb[PQ];
             if constexpr (POLY) w_load(wa, pn.Wout, 2 * wv, lane);                   // project_out rows 16 wv .. 16 wv + 15, columns 0 .. 63
+            if constexpr (LAY) w_load(wa, ly.W1 + b * (ME * ME), 2 * wv, lane);      // W1[b]^T rows (= pre columns) 16 wv .. + 15, k = 0 .. 63
             __syncthreads();
             MSTAMP(5);
+            if constexpr (LAY) {
+                // ---- EAS-Lay: the instance's residual layer on the tile, the weights streamed as in the PolyNet case (128 kB per
+                // instance: they do not fit into LDS next to the tiles and Lp).  Lane (query j, G), register r <-> column 16 wv + 4 G + r.
+                const float* W1b = ly.W1 + b * (ME * ME);
+                const float* W2b = ly.W2 + b * (ME * ME);
+                const float4 bb1 = *reinterpret_cast<const float4*>(ly.b1 + b * ME + 16 * wv + 4 * G);
+                const float4 bb2 = *reinterpret_cast<const float4*>(ly.b2 + b * ME + 16 * wv + 4 * G);
+                f32x4 p0 = (f32x4){bb1.x, bb1.y, bb1.z, bb1.w}, p1 = z4();
+                f32x4 hown;                                                 // this lane's own columns of h (the residual)
+                {
+                    const float* hp = HT + j * TS + G * TG;
+                    const float* ho = HT + j * TS + 4 * wv + G;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) hown[r] = ho[r * TG];
+                    w_load(wb, W1b, 2 * wv + 1, lane);
+                    w_gemm(wa, hp, p0, p1);
+                    w_load(wa, W2b, 2 * wv, lane);                          // W2[b]^T rows (= y columns) 16 wv .. + 15
+                    w_gemm(wb, hp + 16, p0, p1);
+                    w_load(wb, W2b, 2 * wv + 1, lane);
+                }
+                {       // a = relu(pre) goes into QT (free since the glimpse barrier, as PolyNet's g)
+                    const f32x4 pr = p0 + p1;
+                    float* gp = QT + j * TS + 4 * wv + G;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) gp[r * TG] = pr[r] > 0.0f ? pr[r] : 0.0f;
+                }
+                __syncthreads();                 // a is published, and every wavefront has read the heads: HT is free for y
+                {
+                    f32x4 q0 = (f32x4){bb2.x, bb2.y, bb2.z, bb2.w}, q1 = z4();
+                    const float* ap = QT + j * TS + G * TG;
+                    w_gemm(wa, ap, q0, q1);
+                    w_gemm(wb, ap + 16, q0, q1);
+                    const f32x4 y = hown + (q0 + q1);
+                    float* yp = HT + j * TS + 4 * wv + G;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) yp[r * TG] = y[r];
+                }
+                __syncthreads();                 // y is published: the logit phase reads it where it read the heads
+            }
             if constexpr (POLY) {
                 // ---- PolyNet layers of the tile (queries = the MFMA's N dimension, as in the logit phase below) --------------------
                 // g = heads Wout^T, columns 16 wv + 4 G + r of query j
@@ -768,6 +821,9 @@ __global__ __launch_bounds__(512, 2) void k_rollout_ms_mfma(DecArgs a, int S, in
                 }
                 int sel = half_min(cand);
                 if (a.mode == EAMRL_EVALUATE && live2) sel = (t < a.t_given) ? (int)a.given[mul32w(r2, a.t_given) + t] : 0;
+                if constexpr (LAY) {            // the incumbent row: the instance's last row takes the caller's tour, depot-padded
+                    if (ly.forced && live2 && s2 == S - 1) sel = (t < ly.t_forced) ? (int)ly.forced[b * ly.t_forced + t] : 0;
+                }
                 uint32_t fl = 0;
                 if (live2) {
                     if (nan_seen) fl |= EAMRL_ST_NAN_LOGITS;
@@ -1007,6 +1063,31 @@ int launch_poly_env_t(const DecArgs& a, const PolyArgs& pn, int S, hipStream_t s
     return launch_poly_t<7, ENV>(a, pn, S, st);
 }
 
+// EAS-Lay: TSP and CVRP, one instantiation per key-tile count with PolyNet's fixed node chunks (the same register argument: the
+// run-time chunk length costs ~50 VGPRs next to the weight stream), so the captured heads are the plain kernel's to rounding, not
+// bit for bit.
+template <int RTT, int ENV>
+int launch_lay_t(const DecArgs& a, const LayArgs& ly, int S, hipStream_t st)
+{
+    const size_t lds = (size_t)RTT * 32 * 64 * sizeof(float);
+    auto k = k_rollout_ms_mfma<RTT, 4 * RTT, ENV, LayArgs>;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return EAMRL_E_LAUNCH;
+    const int nqt = (S + 15) / 16;
+    int nsplit = a.B > 0 ? (int)(256 / a.B) : 1;
+    nsplit = nsplit < 1 ? 1 : (nsplit > nqt ? nqt : nsplit);
+    hipLaunchKernelGGL(k, dim3((unsigned)(a.B * nsplit)), dim3(512), lds, st, a, S, nsplit, ly);
+    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
+}
+
+template <int ENV>
+int launch_lay_env_t(const DecArgs& a, const LayArgs& ly, int S, hipStream_t st)
+{
+    if (a.M <= 32) return launch_lay_t<2, ENV>(a, ly, S, st);
+    if (a.M <= 64) return launch_lay_t<4, ENV>(a, ly, S, st);
+    return launch_lay_t<7, ENV>(a, ly, S, st);
+}
+
 }  // namespace
 
 #ifdef EAMRL_STAMPS
@@ -1070,6 +1151,23 @@ int launch_rollout_ms_poly(int env, const DecArgs& a, const PolyArgs& pn, hipStr
     const int S = (int)(a.R / a.B);
     if (env == EAMRL_ENV_TSP) return launch_poly_env_t<EAMRL_ENV_TSP>(a, pn, S, st);
     const int rc = launch_poly_env_t<EAMRL_ENV_CVRP>(a, pn, S, st);
+    if (rc) return rc;
+    launch_rollout_pad(env, a, st);
+    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
+}
+
+// EAS-Lay rollouts: what the start-sharing kernel takes at all, TSP and CVRP only, no filters
+bool rollout_ms_lay_supports(int env, const DecArgs& a, bool shape_only)
+{
+    if (env != EAMRL_ENV_TSP && env != EAMRL_ENV_CVRP) return false;
+    return rollout_ms_mfma_supports(env, a, shape_only);
+}
+
+int launch_rollout_ms_lay(int env, const DecArgs& a, const LayArgs& ly, hipStream_t st)
+{
+    const int S = (int)(a.R / a.B);
+    if (env == EAMRL_ENV_TSP) return launch_lay_env_t<EAMRL_ENV_TSP>(a, ly, S, st);
+    const int rc = launch_lay_env_t<EAMRL_ENV_CVRP>(a, ly, S, st);
     if (rc) return rc;
     launch_rollout_pad(env, a, st);
     return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;

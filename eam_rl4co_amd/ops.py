@@ -785,6 +785,27 @@ class ReevalPlan:
         _lib.check(lib.eamrl_reeval_backward_lp(C.byref(s), _stream(self.buf)), "eamrl_reeval_backward_lp")
         return out
 
+    def backward_layer(self, glogp, layer, out=None):
+        """-> {"W1", "b1", "W2", "b2"}: d(sum glogp * logp)/d(layer parameters) of an EAS-Lay layer (eamrl_eas_layer_backward), in
+        the parameters' own layout ([B, E * E] fragment order, [B, E]).  layer: the dict of `eas_layer_operands`; the plan's
+        log-probs (or lse) and rollout heads must come from a rollout WITH that layer.  `out` (the same dict shape) is
+        accumulated into (+=).  The library refuses plans above 112 nodes, with a dynamic embedding or without rollout heads
+        before it launches anything."""
+        lib = _lib.load()
+        glogp = glogp.contiguous()
+        _chk(glogp, "grad of logp", torch.float32, (self.R, self.T))
+        ls = _eas_layer_struct(layer, self.B, self.E)
+        if out is None:
+            out = {n: torch.zeros(self.B, self.E * (self.E if n[0] == "W" else 1), dtype=torch.float32, device=self.buf.device)
+                   for n in ("W1", "b1", "W2", "b2")}
+        for n in ("W1", "b1", "W2", "b2"):
+            _chk(out[n], f"d{n}", torch.float32, (self.B, self.E * (self.E if n[0] == "W" else 1)))
+        ls.dW1, ls.db1, ls.dW2, ls.db2 = (out[n].data_ptr() for n in ("W1", "b1", "W2", "b2"))
+        s = self._struct()
+        s.glogp = _ptr(glogp)
+        _lib.check(lib.eamrl_eas_layer_backward(C.byref(s), C.byref(ls), _stream(self.buf)), "eamrl_eas_layer_backward")
+        return out
+
 
 # ------------------------------------------------------------------------------------------------------
 # environment transitions
@@ -1591,10 +1612,14 @@ def _capture_heads(st, cache, cs, R, t_max, want_heads):
 
 
 def rollout(st: RolloutState, cache: DecodeCache, mode="greedy", noise=None, given=None, clip=10.0, temp=1.0,
-            t_max=None, top_k=0, top_p=0.0, seed=None, seed_dev=None, return_flags=False, want_heads=False, poly=None):
+            t_max=None, top_k=0, top_p=0.0, seed=None, seed_dev=None, return_flags=False, want_heads=False, poly=None,
+            eas_layer=None):
     """Whole decode loop in one launch.  -> (actions [R,t_max], logps [R,t_max], info int32[2] = (steps, status)).
     poly: the operands of a PolyNet pointer (`polynet_operands`, on the device): the rollout runs the PolyNet case of the
     start-sharing kernel (one launch per 128 rows of an instance), or raises where that is not built.
+    eas_layer: the parameters of an EAS-Lay layer (`eas_layer_operands`: one residual layer per instance, on the device): the
+    rollout runs the layer case of the start-sharing kernel, or raises NotImplementedError where that is not built.  With
+    want_heads the pre-layer glimpse outputs are kept in st.heads (and the call raises if that buffer cannot be had).
     Sampling takes its Exp(1) noise from `noise` [R, T, M] or, with `seed` (XOR the device word `seed_dev`), from the counter-based
     generator -- in place where the kernel supports it (TSP multistart), else through a scratch tensor of the same draws.
     return_flags: info is int32[4] = (steps, status, 0, 0), the last two free for the caller's validity counters."""
@@ -1609,6 +1634,11 @@ def rollout(st: RolloutState, cache: DecodeCache, mode="greedy", noise=None, giv
         if top_k or (0.0 < top_p < 1.0):
             raise NotImplementedError("PolyNet rollout: top-k / top-p filtering is not built")
         return _rollout_polynet(st, cache, poly, mode, noise, given, clip, temp, int(t_max), seed, seed_dev, return_flags)
+    if eas_layer is not None:
+        if top_k or (0.0 < top_p < 1.0):
+            raise NotImplementedError("EAS-Lay rollout: top-k / top-p filtering is not built")
+        return _rollout_eas_layer(st, cache, eas_layer, mode, noise, given, clip, temp, int(t_max), seed, seed_dev, return_flags,
+                                  want_heads)
     if mode == "sampling" and noise is None:
         if top_k or (0.0 < top_p < 1.0):
             # the kernels that filter (register-resident FILT variant, streaming) read their noise from a tensor
@@ -1744,6 +1774,112 @@ def _rollout_polynet(st, cache, poly, mode, noise, given, clip, temp, t_max, see
                                                 _ptr(noise), _ptr(given), t_given, float(clip), float(temp), int(t_max),
                                                 _ptr(actions), _ptr(logps), steps_ptr, status_ptr, _stream(st.mask)),
                    "eamrl_am_rollout_polynet")
+    return actions, logps, (info if return_flags else info[:2])
+
+
+# ------------------------------------------------------------------------------------------------------
+# EAS-Lay (eamrl_eas_layer): one residual layer per instance inside the decode step
+# ------------------------------------------------------------------------------------------------------
+def _eas_layer_index(E, dev):
+    """[E * E] int64: position in a row-major [E, E] matrix W (y = x W) of every float of its kernel layout -- the fragment
+    order (pack_mfma_a) of W^T: float 4 * ((T * (E / 16) + q) * 64 + l) + i holds W[16 q + 4 i + l // 16, 16 T + l % 16]."""
+    T, q = torch.arange(E // 16, device=dev)[:, None, None, None], torch.arange(E // 16, device=dev)[None, :, None, None]
+    l, i = torch.arange(64, device=dev)[None, None, :, None], torch.arange(4, device=dev)[None, None, None, :]
+    return ((16 * q + 4 * i + l // 16) * E + 16 * T + l % 16).reshape(-1)
+
+
+def pack_eas_layer(W):
+    """[N, E, E] (y = x W[b], the reference's EASLayerNet.W1 / W2) -> [N, E * E] in the layout of eamrl_eas_layer.  Plain
+    indexing (any device); `unpack_eas_layer` is its exact inverse."""
+    N, E, E2 = W.shape
+    assert E == E2 and E % 16 == 0
+    return W.reshape(N, E * E)[:, _eas_layer_index(E, W.device)].contiguous()
+
+
+def unpack_eas_layer(P, E=128):
+    """[N, E * E] in the layout of eamrl_eas_layer -> [N, E, E] row-major (parameters and gradients alike)."""
+    N = P.shape[0]
+    out = torch.empty_like(P)
+    out[:, _eas_layer_index(E, P.device)] = P
+    return out.view(N, E, E)
+
+
+def eas_layer_operands(W1, b1, W2, b2, forced=None):
+    """The dict `rollout(..., eas_layer=)` and `ReevalPlan.backward_layer` take, from the reference's shapes: W1, W2 [N, E, E],
+    b1, b2 [N, 1, E] or [N, E]; forced [N, t] int64 (optional: the tour of every instance's last row)."""
+    N, E, _ = W1.shape
+    d = {"W1": pack_eas_layer(W1.detach().float()), "b1": b1.detach().float().reshape(N, E).contiguous().clone(),
+         "W2": pack_eas_layer(W2.detach().float()), "b2": b2.detach().float().reshape(N, E).contiguous().clone()}
+    if forced is not None:
+        d["forced"] = forced
+    return d
+
+
+def rollout_eas_layer_supported(env_name, cache, R) -> bool:
+    """Whether `rollout(..., eas_layer=)` serves this env / cache shape / row count (eamrl_rollout_eas_layer_supported; host only)."""
+    if env_name not in ("tsp", "cvrp"):
+        return False
+    cs = cache if isinstance(cache, _lib.Cache) else cache.struct()
+    return bool(_lib.load().eamrl_rollout_eas_layer_supported(ENVS[env_name], C.byref(cs), int(R)))
+
+
+def _eas_layer_struct(layer, B, E):
+    for name, n in (("W1", E * E), ("b1", E), ("W2", E * E), ("b2", E)):
+        _chk(layer[name], f"eas_layer[{name!r}]", torch.float32)
+        if layer[name].numel() != B * n:
+            raise ValueError(f"EAS-Lay: eas_layer[{name!r}] must hold {B} x {n} floats (one layer per instance: ops.eas_layer_operands)")
+    ls = _lib.EasLayer()
+    ls.W1, ls.b1, ls.W2, ls.b2 = (layer[n].data_ptr() for n in ("W1", "b1", "W2", "b2"))
+    return ls
+
+
+def _rollout_eas_layer(st, cache, layer, mode, noise, given, clip, temp, t_max, seed, seed_dev, return_flags, want_heads):
+    lib = _lib.load()
+    R, M, dev = st.R, st.M, st.mask.device
+    if st.env_name not in ("tsp", "cvrp"):
+        raise NotImplementedError(f"EAS-Lay rollout: env {st.env_name!r} is not built (TSP and CVRP are)")
+    if cache.planes or M > KEY_CHUNK:
+        raise NotImplementedError(f"EAS-Lay rollout: graphs above {KEY_CHUNK} nodes are not built ({M} nodes)")
+    S = R // cache.B
+    if S < 2 or S > 128:
+        raise NotImplementedError(f"EAS-Lay rollout: 2 .. 128 rows per instance are built, not {S}")
+    cs = cache.struct()
+    if not lib.eamrl_rollout_eas_layer_supported(ENVS[st.env_name], C.byref(cs), R):
+        raise NotImplementedError("EAS-Lay rollout: this decoder shape is not built (embed_dim 128, 8 heads, 2 .. 112 nodes)")
+    ls = _eas_layer_struct(layer, cache.B, cache.E)
+    forced = layer.get("forced")
+    if forced is not None:
+        _chk(forced, "eas_layer['forced']", torch.int64)
+        if forced.dim() != 2 or forced.shape[0] != cache.B or forced.shape[1] < 1:
+            raise ValueError("EAS-Lay: forced must be [B, t >= 1] int64")
+        ls.forced, ls.t_forced = forced.data_ptr(), forced.shape[1]
+    t_given = 0
+    if noise is not None:
+        _chk(noise, "noise", torch.float32)
+        if noise.dim() != 3 or noise.shape[0] != R or noise.shape[2] != M:
+            raise ValueError("noise must be [R, T, M]")
+        t_max = noise.shape[1]
+    if given is not None:
+        _chk(given, "given actions", torch.int64)
+        if given.dim() != 2 or given.shape[0] != R:
+            raise ValueError("given actions must be [R, T]")
+        t_given = given.shape[1]
+        if noise is None and st.env_name != "tsp":
+            t_max = min(t_max, t_given)
+    actions, logps, info = _rollout_outputs(R, int(t_max), dev)
+    _capture_heads(st, cache, cs, R, t_max, want_heads)
+    if want_heads and st.heads is None:
+        raise RuntimeError("EAS-Lay rollout: the buffer for the steps' glimpse outputs could not be had (see the log); the layer's "
+                           "backward has no path without it")
+    ss = st.struct()
+    st.heads_out = None
+    seeded = mode == "sampling" and noise is None
+    _lib.check(lib.eamrl_am_rollout_eas_layer(ENVS[st.env_name], C.byref(cs), C.byref(ss), C.byref(ls), R, MODES[mode], _ptr(noise),
+                                              _ptr(given), t_given, int(seeded),
+                                              C.c_uint64((int(seed) if seeded else 0) & 0xFFFFFFFFFFFFFFFF),
+                                              _ptr(seed_dev if seeded else None), float(clip), float(temp), int(t_max), _ptr(actions),
+                                              _ptr(logps), C.c_void_p(info.data_ptr()), C.c_void_p(info.data_ptr() + 4),
+                                              _stream(st.mask)), "eamrl_am_rollout_eas_layer")
     return actions, logps, (info if return_flags else info[:2])
 
 

@@ -1,5 +1,5 @@
-"""Efficient Active Search with embedding adaptation (EAS-Emb; Hottung et al. 2022) on the native rollout and re-evaluation
-kernels.  Reference: rl4co/models/zoo/eas/search.py:50-69,137-281 (hyper-parameters, loss, incumbent) and decoder.py:35-126
+"""Efficient Active Search (Hottung et al. 2022) with embedding adaptation (EAS-Emb) or layer adaptation (EAS-Lay, last
+section) on the native rollout and re-evaluation kernels.  Reference: rl4co/models/zoo/eas/search.py:50-69,137-281 (hyper-parameters, loss, incumbent) and decoder.py:35-126
 (the rollout with an incumbent row per instance).
 
 The policy is frozen.  A batch of test instances is augmented and encoded ONCE; the decoder cache of that pass
@@ -20,6 +20,13 @@ parameters of a torch Adam.  Every iteration
 Two deviations from the reference, both deliberate: the start nodes are env.select_start_nodes(td, S) as in every
 other multistart rollout of this library (the reference's select_start_nodes(td, S + 1) % S maps a depot env's last customer to
 the depot), and iteration 0 has no incumbent group and no imitation term (the reference imitates one more sampled row there).
+
+EAS-Lay (use_eas_layer=True, use_eas_embedding=False; zoo/eas/nn.py:5-30, decoder.py:12-32): the cache stays as it is and the
+parameters are one residual layer per augmented instance, y = h + relu(h W1 + b1) W2 + b2 on the glimpse output h before
+project_out, kept for the whole search in the kernels' layout (ops.pack_eas_layer; Adam is element-wise).  Every iteration is ONE
+rollout of S + 1 rows per instance on the layer case of the start-sharing kernel -- from iteration 1 on the last row is forced
+to the incumbent, as the reference's row S + 1 (decoder.py:73-79,111-115) -- and ONE eamrl_eas_layer_backward launch over all
+rows, on the rollout's own log-probs and captured heads.  TSP and CVRP, at most 112 nodes, S + 1 <= 128.
 """
 from __future__ import annotations
 
@@ -32,6 +39,19 @@ from .utils import StateAugmentation
 
 CACHE_KEYS = {"logit_key": "L", "glimpse_key": "K", "glimpse_val": "V"}      # PrecomputedCache field -> cache slot
 BASELINES = ("multistart", "symmetric", "full")
+LAYER_ENVS = ("tsp", "cvrp")        # EAS-Lay: the envs of the rollout kernel's layer case
+LAYER_PARAMS = ("W1", "b1", "W2", "b2")
+
+
+def eas_layer_init(N: int, E: int, generator=None):
+    """The reference's initialisation of EASLayerNet on the reference's shapes (zoo/eas/nn.py:14-24): W1 [N, E, E] and b1 [N, 1, E]
+    by xavier_uniform_ (torch's fan rule for those shapes: fan_in = E * E and N * E for W1, E and N * E for b1), W2 = b2 = 0.
+    CPU tensors."""
+    W1, b1 = torch.empty(N, E, E), torch.empty(N, 1, E)
+    kw = {} if generator is None else {"generator": generator}
+    torch.nn.init.xavier_uniform_(W1, **kw)
+    torch.nn.init.xavier_uniform_(b1, **kw)
+    return W1, b1, torch.zeros(N, E, E), torch.zeros(N, 1, E)
 
 
 def eas_loss_coefficients(reward, baseline: str, eas_lambda: float, incumbent: bool):
@@ -54,6 +74,12 @@ def eas_loss_coefficients(reward, baseline: str, eas_lambda: float, incumbent: b
     return coef
 
 
+def eas_layer_row_coefficients(coef):
+    """[B, n_aug, G] coefficients (`eas_loss_coefficients`) -> [G * n_aug * B], one per row of the layer rollout: rows in "(s b)"
+    order over the augmented batch, row (g * n_aug + a) * B + b, so the forced (incumbent) group g = G - 1 comes last."""
+    return coef.permute(2, 1, 0).reshape(-1)
+
+
 def _pad_to(actions, width: int):
     """Depot visits up to `width` columns (a finished row stays at the depot with probability 1)."""
     if actions.shape[1] >= width:
@@ -70,9 +96,12 @@ class EAS:
     for `max_iters` iterations and returns {"max_reward": [B] float32, "best_solutions": [B, T] int64}.  The policy's parameters,
     their requires_grad flags and its buffers are never written.  No Lightning and no dataset plumbing: the caller batches.
 
-    Names and defaults are the reference's (zoo/eas/search.py:50-69).  use_eas_layer (EAS-Lay: a per-instance residual layer
-    inside the decode step, which the rollout kernels do not have) and num_parallel_runs != 1 (the reference's incumbent
-    indexing is not well defined for it) raise NotImplementedError, as does an env without native re-evaluation (PDP).
+    Names and defaults are the reference's (zoo/eas/search.py:50-69).  use_eas_layer=True with use_eas_embedding=False is EAS-Lay
+    (module docstring).  The layer has no CPU path: a layer search whose policy parameters are not on a GPU raises
+    NotImplementedError at construction, before anything else is looked at.  Also NotImplementedError, each naming its limit:
+    both adaptations at once, a layer search on an env other than TSP / CVRP (here), above 112 nodes or with S + 1 > 128 rows
+    per instance (in `begin`, where the batch is known), num_parallel_runs != 1 (the reference's incumbent indexing is not well
+    defined for it) and an env without native re-evaluation (PDP).
     seed: seeds the rollouts' counter-based noise (None: torch's global generator, as the policy's own sampling rollouts)."""
 
     def __init__(self, env, policy, use_eas_embedding: bool = True, use_eas_layer: bool = False,
@@ -83,8 +112,14 @@ class EAS:
 
         assert use_eas_embedding or use_eas_layer, "At least one of `use_eas_embedding` or `use_eas_layer` must be True."
         if use_eas_layer:
-            raise NotImplementedError("EAS-Lay: the per-instance residual layer sits inside the decode step, which the rollout "
-                                      "kernels do not have; use EASEmb")
+            if not all(p.is_cuda for p in policy.parameters()):
+                raise NotImplementedError("EAS-Lay: the per-instance layer runs inside the GPU rollout kernel and has no CPU path; "
+                                          "move the policy to the GPU")
+            if use_eas_embedding:
+                raise NotImplementedError("EAS: use_eas_embedding and use_eas_layer together are not built; choose one")
+            if policy.env_name not in LAYER_ENVS:
+                raise NotImplementedError(f"EAS-Lay: env {policy.env_name!r} is not built; the layer rollout serves {LAYER_ENVS}")
+        self.layer = bool(use_eas_layer)
         if num_parallel_runs != 1:
             raise NotImplementedError("num_parallel_runs != 1: the reference's incumbent indexing is not well defined for it")
         assert baseline in BASELINES, f"Baseline {baseline} not supported."
@@ -125,16 +160,18 @@ class EAS:
             s.cache = pol.decoder._precompute_cache(hidden)
         finally:
             pol.train(was_training)
-        s.Wout = pol.decoder.pointer.project_out.weight.detach().contiguous()
-        s.WoutT = s.Wout.t().contiguous()
-        s.params = {k: torch.nn.Parameter(s.cache.view(CACHE_KEYS[k]).clone().contiguous()) for k in self.keys}
-        s.opt = torch.optim.Adam(list(s.params.values()), **self.optimizer_kwargs)
-        s.fast = (self.keys == ["logit_key"] and s.M <= ops.KEY_CHUNK and s.cache.dyn is None and not s.cache.planes)
         seed = self.seed if seed is None else seed
         s.gen = None if seed is None else torch.Generator().manual_seed(int(seed))
         s.max_reward = torch.full((s.B,), -float("inf"), device=td["locs"].device)
         s.best = None           # [B, W] int64 once an iteration has run
         s.iter = 0
+        if self.layer:
+            return self._begin_layer(s)
+        s.Wout = pol.decoder.pointer.project_out.weight.detach().contiguous()
+        s.WoutT = s.Wout.t().contiguous()
+        s.params = {k: torch.nn.Parameter(s.cache.view(CACHE_KEYS[k]).clone().contiguous()) for k in self.keys}
+        s.opt = torch.optim.Adam(list(s.params.values()), **self.optimizer_kwargs)
+        s.fast = (self.keys == ["logit_key"] and s.M <= ops.KEY_CHUNK and s.cache.dyn is None and not s.cache.planes)
         return s
 
     def _plane(self, s: _State, slot: str):
@@ -210,11 +247,81 @@ class EAS:
             t["dyn"] = dec.dynamic_embedding.projection.weight.detach()
         return t
 
+    # ---- EAS-Lay -----------------------------------------------------------------------------------------------------
+    def _begin_layer(self, s: _State) -> _State:
+        """The layer's parameters (one set per augmented instance, kernel layout) and their Adam."""
+        pol, c = self.policy, s.cache
+        if s.M > ops.KEY_CHUNK or c.planes:
+            raise NotImplementedError(f"EAS-Lay: graphs above {ops.KEY_CHUNK} nodes are not built ({s.M} nodes)")
+        if s.S + 1 > 128:
+            raise NotImplementedError(f"EAS-Lay: S + 1 = {s.S + 1} rows per instance; the layer rollout takes at most 128")
+        if not ops.rollout_eas_layer_supported(pol.env_name, c, (s.S + 1) * s.Ba):
+            raise NotImplementedError("EAS-Lay: this decoder shape is not built (embed_dim 128, 8 heads, 2 .. 112 nodes)")
+        dev = s.td["locs"].device
+        W1, b1, W2, b2 = eas_layer_init(s.Ba, c.E, s.gen)
+        s.params = {"W1": torch.nn.Parameter(ops.pack_eas_layer(W1).to(dev)), "b1": torch.nn.Parameter(b1.reshape(s.Ba, c.E).to(dev)),
+                    "W2": torch.nn.Parameter(ops.pack_eas_layer(W2).to(dev)), "b2": torch.nn.Parameter(b2.reshape(s.Ba, c.E).to(dev))}
+        s.opt = torch.optim.Adam(list(s.params.values()), **self.optimizer_kwargs)
+        s.fast = False
+        return s
+
+    def _layer_operands(self, s: _State, forced=None):
+        d = {n: s.params[n].detach() for n in LAYER_PARAMS}
+        if forced is not None:
+            d["forced"] = forced
+        return d
+
+    @torch.no_grad()
+    def _rollout_layer(self, s: _State):
+        """One sampling rollout of S (+ 1 with an incumbent) rows per instance through the layer; the last row follows the incumbent.
+        -> actions [R, T] (start column included), logp [R, T], heads [R, >= T - 1, E] (pre-layer), reward [R], rows per instance"""
+        from .policy import _env_step_, _max_decode_steps, state_from_td
+
+        pol, env = self.policy, self.env
+        inc = s.best is not None
+        S1 = s.S + (1 if inc else 0)
+        st = state_from_td(pol.env_name, s.td, S1)
+        start = env.select_start_nodes(s.td, num_starts=s.S).to(torch.int64)
+        forced = None
+        if inc:
+            tour = s.best.repeat(s.n_aug, 1)                        # rows (a b) <- best[b]
+            start = torch.cat((start, tour[:, 0]))
+            forced = tour[:, 1:].contiguous()
+        start = start.contiguous()
+        _env_step_(st, start)
+        t_max = int(max(1, _max_decode_steps(pol.env_name, s.M, 1)))
+        seed = int(torch.randint(0, 2 ** 62, (1,), generator=s.gen).item())
+        acts, lps, info = ops.rollout(st, s.cache, "sampling", clip=pol.tanh_clipping, temp=pol.temperature, t_max=t_max, seed=seed,
+                                      want_heads=True, eas_layer=self._layer_operands(s, forced))
+        T, status = info.tolist()
+        ops.raise_on_status(status)
+        actions = torch.cat((start[:, None], acts[:, :T]), 1).contiguous()
+        logp = torch.cat((torch.zeros_like(lps[:, :1]), lps[:, :T]), 1).contiguous()
+        reward = env.get_reward(s.td, actions, check_solution=False)
+        return actions, logp, st.heads, reward, S1
+
+    def _iteration_layer(self, s: _State, rollout=None) -> dict:
+        actions, logp, heads, reward, S1 = rollout if rollout is not None else self._rollout_layer(s)
+        R, T = actions.shape
+        ns = s.S * s.Ba                                             # the sampled rows come first ((s b) order, incumbent group last)
+        inc = S1 > s.S
+        r3 = reward[:ns].view(s.S, s.n_aug, s.B).permute(2, 1, 0)   # [B, n_aug, S]
+        coef = eas_loss_coefficients(r3, self.baseline, self.eas_lambda, incumbent=inc)
+        g = eas_layer_row_coefficients(coef)[:, None].expand(R, T).contiguous()
+        with torch.no_grad():
+            grads = self._plan(s, actions, S1, rollout_logp=logp, rollout_heads=heads).backward_layer(g, self._layer_operands(s))
+        for n in LAYER_PARAMS:
+            s.params[n].grad = grads[n]
+        return dict(actions=actions[:ns], reward=reward[:ns], logp=logp[:ns], rollout=(actions, logp, heads, reward, S1),
+                    inc_actions=actions[ns:] if inc else None, inc_reward=reward[ns:] if inc else None, coef=coef, grads=grads)
+
     def iteration(self, s: _State, general=None, rollout=None) -> dict:
         """Refresh, rollout, incumbent rows and the gradient of the adapted tensors (left in their .grad); no optimizer step.
         general: force the general (True) or the fast (False) backward; rollout: the `rollout` entry of an earlier call on the same
         state, taken instead of a new rollout (the two paths on the same tours).
         -> dict(actions, reward, logp, rollout, inc_actions, inc_reward, coef, grads)"""
+        if self.layer:
+            return self._iteration_layer(s, rollout)
         pol, env = self.policy, self.env
         general = (not s.fast or self.force_general) if general is None else general
         if not general and not s.fast:
@@ -305,7 +412,8 @@ class EASEmb(EAS):
 
 
 class EASLay(EAS):
-    """EAS with layer adaptation (zoo/eas/search.py:330-346): not built -- the rollout kernels have no per-instance layer."""
+    """EAS with layer adaptation (zoo/eas/search.py:330-346): `search(td)` as EASEmb, on one residual layer per augmented
+    instance instead of the embeddings.  Needs the policy on a GPU (NotImplementedError otherwise)."""
 
     def __init__(self, *args, **kwargs):
         kwargs["use_eas_embedding"] = False

@@ -712,7 +712,10 @@ def _logp_rows(env_name, t, static, act, nrep, multistart, H, temperature, clip,
         heads = torch.matmul(att, vh) + (att * dem_t[:, None]).sum(-1, keepdim=True) * wv.view(1, H, 1, D)
     else:
         heads = F.scaled_dot_product_attention(qh, kh, vh, attn_mask=mask[:, None])     # [Rc, H, T, D]
-    glimpse = F.linear(heads.permute(0, 2, 1, 3).reshape(Rc, T, E), t["Wout"])
+    hcat = heads.permute(0, 2, 1, 3).reshape(Rc, T, E)
+    if "eas_layer" in t:    # EAS-Lay (zoo/eas/decoder.py:12-32): a callable on the concatenated heads [Rc, T, E], before project_out
+        hcat = t["eas_layer"](hcat)
+    glimpse = F.linear(hcat, t["Wout"])
     if "polyW1" in t:       # PolyNetAttention.forward (nn/attention.py:534-545): row r = s * B + b uses strategy (s_first + s) % k
         Z = t["polyZ"]
         z = Z[(s_first + torch.arange(Rc, device=act.device) // B) % Z.shape[0]]

@@ -611,6 +611,50 @@ int eamrl_am_rollout_polynet_seeded(int env, const eamrl_cache* cache_host, cons
                                     float tanh_clip, float temperature, int t_max, int64_t* actions, float* logps,
                                     int32_t* steps_out, uint32_t* status, void* stream);
 
+/* ---- EAS-Lay: a residual layer per instance inside the decode step ----------------------------------- */
+
+/* The layer of EASLayerNet.forward  [zoo/eas/nn.py:5-30] as forward_pointer_attn_eas_lay places it  [zoo/eas/decoder.py:12-32]:
+ * on the glimpse output h (the concatenated heads, BEFORE project_out) of every row of instance b at every decode step
+ *   pre = h W1[b] + b1[b];   a = relu(pre);   y = h + a W2[b] + b2[b];   u[n] = y . Lp[b][n]
+ * project_out has no bias, so the cache's folded logit key Lp = L Wout stays exact; everything from u on is the plain decode
+ * step.  One weight set per instance of the (augmented) batch, B = cache->B of them.
+ * Weight layout: W1 and W2 are [B][E * E], instance b's [E][E] matrix W (y = x W, W[k][n]) stored as the "fragment order"
+ * (eamrl_polynet) of its transpose: float 4 * ((T * 8 + q) * 64 + l) + i of the instance's block holds
+ * W[16 q + 4 i + l / 16][16 T + l % 16].  b1, b2 are [B][E].  The four gradients have the layouts of their parameters, so an
+ * element-wise optimizer never repacks.  All pointers 16-byte aligned.  E must be 128. */
+typedef struct eamrl_eas_layer {
+    const float *W1, *b1, *W2, *b2;
+    /* rollout, optional: forced [B][t_forced] -- the LAST row of every instance (s = S - 1; rows in "(s b)" order) takes
+     * forced[b][t] as its pick at step t and node 0 once t >= t_forced, whatever the call's mode; its log-prob is that of the
+     * forced node, an infeasible forced node sets EAMRL_ST_INFEASIBLE.  This is the incumbent row of the reference's rollout
+     * [zoo/eas/decoder.py:73-79,111-115].  NULL: every row follows the mode.  The backward ignores both fields. */
+    const int64_t* forced; int32_t t_forced;
+    /* backward: ACCUMULATED into (+=); the rollout ignores them */
+    float *dW1, *db1, *dW2, *db2;
+} eamrl_eas_layer;
+
+/* eamrl_am_rollout / eamrl_am_rollout_seeded with the layer  [zoo/eas/decoder.py:35-126 around constructive/base.py:236-250]:
+ * the start-sharing MFMA kernel with the layer's two GEMMs of every 16-query tile on v_mfma_f32_16x16x4_f32 between its
+ * glimpse and logit phases.  state->heads_out, if set, receives the PRE-layer h of every step (what the backward needs).
+ * EAMRL_ENV_TSP and EAMRL_ENV_CVRP, E = 128, H = 8, 2 <= M <= 112, R = S * B rows with 2 <= S <= 128; no top-k / top-p.
+ * seeded != 0: mode must be EAMRL_SAMPLE and the noise is computed in place from (seed ^ *seed_dev, row, step, node) as in
+ * eamrl_am_rollout_seeded; otherwise noise [R][t_max][M] (SAMPLE) / given [R][t_given] (EVALUATE) as in eamrl_am_rollout.
+ * Anything else returns -1 before a launch.  eamrl_rollout_eas_layer_supported: 1 if (env, cache shape, R) is served (host only). */
+int eamrl_rollout_eas_layer_supported(int env, const eamrl_cache* cache_host, int64_t R);
+int eamrl_am_rollout_eas_layer(int env, const eamrl_cache* cache_host, const eamrl_state* state_host, const eamrl_eas_layer* layer,
+                               int64_t R, int mode, const float* noise, const int64_t* given, int t_given, int seeded,
+                               uint64_t seed, const uint64_t* seed_dev, float tanh_clip, float temperature, int t_max,
+                               int64_t* actions, float* logps, int32_t* steps_out, uint32_t* status, void* stream);
+
+/* d(sum glogp * logp)/d(W1, b1, W2, b2) of the layer  [the autograd step of zoo/eas/search.py:202-259 with use_eas_layer]:
+ *   dY = du Lp[b];  dW2[b] += a^T dY;  db2[b] += sum dY;  dpre = (dY W2[b]^T) o [pre > 0];  dW1[b] += h^T dpre;  db1[b] += sum dpre
+ * with du as in eamrl_reeval_backward.  Nothing upstream of h is adapted, so this is the whole gradient.  Reads of `p`: Lp ld
+ * maskbits actions glogp heads heads_T B R S T M tstart nchunk clip temp and lse -- or, with lse == NULL, logp = the
+ * rollout's log-probs, from which the normaliser is recovered.  Steps before tstart, queries past a row chunk's end and steps
+ * with a single feasible node contribute exact zeros; with W2 = 0, dW1 and db1 are exact zeros.
+ * Returns -1 before launching anything when M > 112 (or key chunks), when p->dyn != NULL, and when p->heads == NULL. */
+int eamrl_eas_layer_backward(const eamrl_reeval* p, const eamrl_eas_layer* layer, void* stream);
+
 /* ---- reward ----------------------------------------------------------------------------------------- */
 
 /* reward[r] = -(closed tour length)  [utils/ops.py:59-95; tsp/env.py:152-159; cvrp/env.py:146-155].
