@@ -741,8 +741,8 @@ __global__ __launch_bounds__(256) void k_mha_encoder_tiled(const float* __restri
 int launch_mha_encoder(const float* qkv, float* out, int64_t B, int N, int E, int H, hipStream_t st)
 {
     const int D = E / H;
-    const size_t lds = (size_t)2 * N * D * sizeof(float);
-    if (D * H != E || lds > 160 * 1024 || B * H > 0x7fffffffLL) return EAMRL_E_ARG;
+    const size_t lds = (size_t)2 * N * D * sizeof(float);       // of k_mha_encoder<D> alone: the kernels before it tile the keys
+    if (D * H != E || B * H > 0x7fffffffLL) return EAMRL_E_ARG;
     dim3 grid((unsigned)(B * H)), block(128);
     // blocked kernel: 4 heads per block, 2 query rows per thread (needs 4 * ceil(N/2) <= 256 threads, aligned rows)
     if (D == 16 && H % 4 == 0 && 2 * (N + 1) <= 256 && !g_debug[3] && ((uintptr_t)qkv & 15) == 0 && ((uintptr_t)out & 15) == 0) {
@@ -759,6 +759,7 @@ int launch_mha_encoder(const float* qkv, float* out, int64_t B, int N, int E, in
         hipLaunchKernelGGL(k_mha_encoder_tiled, dim3(nb), dim3(256), 0, st, qkv, out, N, E, H);
         return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
     }
+    if (lds > 160 * 1024) return EAMRL_E_ARG;
     if (D == 16) {
         if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(k_mha_encoder<16>),
                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)

@@ -156,7 +156,9 @@ def test_encoder_attention_norms_mean(oracle, B, N):
     qkv = rng.standard_normal((B, N, 3 * E)).astype(np.float32)
     ref = oracle.mha_encoder(qkv, H)
     assert_bits_equal(ops.mha_encoder(t(qkv), H), ref, "mha_encoder default dispatch")
-    for key, variant in ((7, 1), (3, 1)):     # matrix-core kernel (N <= 128), then the plain VALU kernel
+    # key 7 (once a matrix-core variant) is read by no code any more: the default dispatch again; key 3: the plain VALU kernel;
+    # key 15: above 127 nodes k_mha_encoder_tiled in place of k_mha_encoder_mfma
+    for key, variant in ((7, 1), (3, 1), (15, 1)):
         _lib.load().eamrl_debug_set(key, variant)
         try:
             assert_bits_equal(ops.mha_encoder(t(qkv), H), ref, f"mha_encoder debug key {key}")

@@ -61,10 +61,12 @@ def batchnorm_backward(x, dy, gamma, eps, dtype=torch.float64, stats=None):
     return mean, var, dx, dgamma, dbeta
 
 
-def attention_backward(qkv, dout, H, dtype=torch.float64, keys=None):
+def attention_backward(qkv, dout, H, dtype=torch.float64, keys=None, skip_queries=None):
     """qkv [B, N, 3E] packed q | k | v with H heads each, dout [B, N, E] -> y [B, N, E], dqkv [B, N, 3E].
     p = softmax(q k^T / sqrt(D)) over the keys, y = p v;  dv = p^T dout,  dp = dout v^T,  ds = p (dp - sum p dp),
-    dq = ds k / sqrt(D),  dk = ds^T q / sqrt(D).  `keys`: only the first `keys` nodes are attended to (a deliberately wrong form)."""
+    dq = ds k / sqrt(D),  dk = ds^T q / sqrt(D).  Two deliberately wrong forms, for the planted errors of the tests: `keys`: only the
+    first `keys` nodes are attended to (a bool tensor [N]: only the nodes it marks);  `skip_queries` (indices): these query rows are
+    left out of the sums over the queries, dk and dv (y and dq are as without it)."""
     qkv, dout = qkv.to(dtype), dout.to(dtype)
     B, N, E3 = qkv.shape
     E = E3 // 3
@@ -72,14 +74,20 @@ def attention_backward(qkv, dout, H, dtype=torch.float64, keys=None):
     q, k, v = (qkv[..., i * E:(i + 1) * E].reshape(B, N, H, D).permute(0, 2, 1, 3) for i in range(3))      # [B, H, N, D]
     do = dout.reshape(B, N, H, D).permute(0, 2, 1, 3)
     s = q @ k.transpose(-1, -2) / math.sqrt(D)
-    if keys is not None:
+    if isinstance(keys, torch.Tensor):
+        s[..., ~keys] = -math.inf
+    elif keys is not None:
         s[..., keys:] = -math.inf
     p = torch.softmax(s, dim=-1)
     y = p @ v
-    dv = p.transpose(-1, -2) @ do
     dp = do @ v.transpose(-1, -2)
     ds = p * (dp - (p * dp).sum(-1, keepdim=True))
     dq = ds @ k / math.sqrt(D)
+    if skip_queries is not None:
+        p, ds = p.clone(), ds.clone()
+        p[..., skip_queries, :] = 0
+        ds[..., skip_queries, :] = 0
+    dv = p.transpose(-1, -2) @ do
     dk = ds.transpose(-1, -2) @ q / math.sqrt(D)
     flat = (lambda t: t.permute(0, 2, 1, 3).reshape(B, N, E))
     return flat(y), torch.cat([flat(dq), flat(dk), flat(dv)], dim=-1)
