@@ -1449,14 +1449,17 @@ __global__ __launch_bounds__(512, 2) void k_reeval_bwd_glimpse(ReevalArgs a)
     uint4 mb = load_mask_words(a, qj);
     // key chunks: the query's statistics over all chunks (maximum, 1 / sum, rs), fetched one tile ahead like the mask words
     const int64_t RT = a.R * (int64_t)a.T;
-    auto load_given = [&](int q, float (&g)[3]) {
+    // (a step before tstart has no statistics: the forward pass never wrote them, so whatever the scratch holds there -- a NaN as
+    //  well -- must not reach the weights; maximum = +inf makes every weight exp(-inf) = 0 exactly)
+    auto load_given = [&](int q, int t, float (&g)[3]) {
         const int qc = max(q, 0);
+        const bool live = q >= 0 && t >= a.tstart;
         const float2 st2 = *reinterpret_cast<const float2*>(a.mc_gstat + ((int64_t)qc * RH + h) * 2);
         const float rsv = a.mc_rsq[(int64_t)qc * RH + h];
-        g[0] = q >= 0 ? st2.x : 0.0f; g[1] = q >= 0 ? st2.y : 0.0f; g[2] = q >= 0 ? rsv : 0.0f;
+        g[0] = live ? st2.x : INFINITY; g[1] = live ? st2.y : 0.0f; g[2] = live ? rsv : 0.0f;
     };
     float gv[3] = {0.f, 0.f, 0.f};
-    if (MC) load_given(qj, gv);
+    if (MC) load_given(qj, wj.t, gv);
     __syncthreads();                    // CV, KTL
 
     for (int tile = 0; tile < ntiles; ++tile) {
@@ -1474,7 +1477,7 @@ __global__ __launch_bounds__(512, 2) void k_reeval_bwd_glimpse(ReevalArgs a)
         wj.next(T);
         qj = qi_of(wj);
         mb = load_mask_words(a, qj);
-        if (MC) load_given(qj, gv);
+        if (MC) load_given(qj, wj.t, gv);
         __syncthreads();
         const float* QT = QTB + cur * 16 * TS;
         const float* DHT = DHB + cur * 16 * TS;

@@ -80,6 +80,7 @@ CASES = _build()
 NAMES = list(CASES)
 EDGE_NODES = sorted({e + d for e in range(16, 1024, 16) for d in (-1, 0)})      # both sides of every 16-key tile / 32-bit word
 FORCED_EVERY, TIE_EVERY = (3, 2), (3, 1)        # steps t with t % 3 == 2 are forced, with t % 3 == 1 ties
+SCALES = {"normal": (1.0, 2.0, 1.0), "peaked": (5.0, 8.0, 1.6), "policy": (0.3, 0.25, 1.0)}      # of K, Lp and the query parts
 
 
 def dead_node(c, b):
@@ -106,7 +107,7 @@ def operands(name):
     def randn(*shape, s=1.0):
         return torch.randn(*shape, generator=g) * s
 
-    ks, ls, qs = {"normal": (1.0, 2.0, 1.0), "peaked": (5.0, 8.0, 1.6), "policy": (0.3, 0.25, 1.0)}[c["scale"]]
+    ks, ls, qs = SCALES[c["scale"]]
     op = dict(K=randn(B, M, E, s=ks), V=randn(B, M, E), Lp=randn(B, M, E, s=ls), Pa=randn(B, M, E, s=0.7 * qs),
               Pb=randn(B, M, E, s=0.5 * qs) if c["pb"] else None, gctx=randn(B, E, s=0.5 * qs) if c["gctx"] else None,
               Cvec=randn(c["NC"], E, s=0.5) if c["NC"] else None, sc=torch.rand(c["NC"], R, T, generator=g) if c["NC"] else None,

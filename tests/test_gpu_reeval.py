@@ -41,8 +41,9 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 
-def run_kernels(name):
-    """-> dict of the kernels' outputs for case `name` (CPU tensors)."""
+def run_kernels(name, poison=False):
+    """-> dict of the kernels' outputs for case `name` (CPU tensors).  poison: the scratch that a key-chunked plan keeps from the
+    forward to the backward pass starts out as NaNs instead of whatever the allocator hands over."""
     from eam_rl4co_amd import ops
 
     c = rc.CASES[name]
@@ -63,6 +64,10 @@ def run_kernels(name):
                           rollout_heads=dev(op["heads"][:, t0:]) if c["rollout_heads"] else None,
                           rem=dev(rr.rem_rows(op["rem"])) if c["dyn"] else None, dyn=dev(op["dyn"]))
     assert plan.nchunk == max(1, min(c["S"], -(-512 // c["B"])))
+    if poison:
+        assert plan.nkc > 1 and plan.scratch is None
+        n = int(ops._lib.load().eamrl_reeval_scratch_floats(plan.R, plan.T, plan.M))
+        plan.scratch = torch.full((n,), float("nan"), dtype=torch.float32, device=DEV)
     got = dict(logp=plan.forward().cpu())
     if c["rollout_logp"]:
         assert plan.lse is None and torch.equal(got["logp"], fed)
@@ -110,4 +115,18 @@ def test_reeval_kernels_match_the_float64_restatement(name):
             assert (got["dPa"][:, n] == 0).all() and (not c["pb"] or (got["dPb"][:, n] == 0).all())
         for k in rc.exact_zero(c):
             assert (got[k] == 0).all(), k
+    assert rc.misses(c, got, r64, r32) == []
+
+
+@pytest.mark.parametrize("name", ["edge_M113", "edge_M225", "ops_dyn_M130", "rows_B100_S13_M113_T5"])
+def test_chunked_backward_reads_no_statistics_of_inactive_steps(name):
+    """Graphs above 112 nodes: the forward pass writes the glimpse statistics (maximum, 1 / sum) of the steps t >= tstart only.
+    The backward pass must not let the scratch of the other steps reach a gradient: with that scratch full of NaNs every
+    output stays finite and within its bound (it used to form exp(s - NaN) * 0 there: dK and dV came out as NaN whenever the
+    allocator's memory happened to hold one)."""
+    c = rc.CASES[name]
+    assert c["M"] > rr.KEY_CHUNK and c["tstart"] >= 1 and c["backward"]
+    op, glogp, r64, r32 = rc.reference(name)
+    got = run_kernels(name, poison=True)
+    assert all(torch.isfinite(got[k]).all() for k in got)
     assert rc.misses(c, got, r64, r32) == []
