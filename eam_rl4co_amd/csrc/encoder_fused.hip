@@ -99,6 +99,69 @@ __device__ __forceinline__ void load_b0(float4 (&b0)[CT], const float* const (&w
     for (int ct = 0; ct < CT; ++ct) b0[ct] = global_load_b128(wp[ct]);
 }
 
+__device__ __forceinline__ float global_load_b32(const float* p)
+{
+    typedef const __attribute__((address_space(1))) float* global_ptr;
+    return *(global_ptr)(p);
+}
+
+// The per-layer constants (CST) are staged in two steps: cst_request issues all loads of a thread's (at most four) entries,
+// cst_store folds and writes them to LDS.  Between the two lies whatever hides the latency: the request for layer l + 1 is
+// issued ahead of layer l's norm2, the store stays behind the barrier that ends it.
+// Thread tid stages the entries tid + 512 t.  Every segment boundary of the CST layout is a multiple of 128, so the segment of
+// a trip is uniform over a wave and the pointer is chosen on the wave number wv (an SGPR) with scalar selects -- chosen per
+// lane, the compiler fetched the pointer itself with a vector load from the argument block.
+//   t = 0: waves 0-5 bqkv, 6-7 bo          t = 1: b1
+//   t = 2: waves 0-1 b2, 2-3 norm1 scale, 4-5 norm1 shift, 6-7 norm2 scale          t = 3: waves 0-1 norm2 shift
+// so a wave has one normalisation entry, of channel tid & 127, and loads its four operands whatever the kind of norm (instance
+// norm may come without running statistics: gamma stands in); b2 is loaded by every wave and stored by waves 0-1.  Nothing
+// here sits under a branch.
+static_assert(C_BO == 6 * 64 && C_B1 == 512 && C_B2 == 1024 && C_N1 == C_B2 + 2 * 64 && C_N2 == C_N1 + 4 * 64 && NCST == 1536 + 2 * 64,
+              "cst_request / cst_store spell out the CST layout");
+struct CstRaw { float e0, e1, b2, gamma, beta, mean, var; };
+
+__device__ __forceinline__ CstRaw cst_request(const float* bqkv, const float* bo, const float* b1, const float* b2,
+                                              const float* n1_gamma, const float* n1_beta, const float* n1_mean, const float* n1_var,
+                                              const float* n2_gamma, const float* n2_beta, const float* n2_mean, const float* n2_var,
+                                              int norm, int wv, int tid)
+{
+    const int c = tid & (FE - 1);
+    const bool n1 = wv >= 2 && wv < 6, stats = norm == EAMRL_NORM_BATCH_EVAL;
+    const float* gam = n1 ? n1_gamma : n2_gamma;
+    const float* mean = n1 ? n1_mean : n2_mean;
+    const float* var = n1 ? n1_var : n2_var;
+    CstRaw r;
+    r.e0 = global_load_b32((wv < 6 ? bqkv : bo) + (tid - (wv < 6 ? 0 : C_BO)));
+    r.e1 = global_load_b32(b1 + tid);
+    r.b2 = global_load_b32(b2 + c);
+    r.gamma = global_load_b32(gam + c);
+    r.beta = global_load_b32((n1 ? n1_beta : n2_beta) + c);
+    r.mean = global_load_b32((stats ? mean : gam) + c);
+    r.var = global_load_b32((stats ? var : gam) + c);
+    return r;
+}
+
+__device__ __forceinline__ void cst_store(float* CST, const CstRaw r, int norm, float eps, int wv, int tid)
+{
+    const bool shift = wv < 2 || (wv >= 4 && wv < 6);
+    float nv;
+    if (norm == EAMRL_NORM_BATCH_EVAL) {
+        const float sc = r.gamma / __builtin_sqrtf(r.var + eps);
+        const float ms = r.mean * sc;
+        nv = shift ? r.beta - ms : sc;
+    } else {
+        nv = shift ? r.beta : r.gamma;
+    }
+    CST[tid] = r.e0;
+    CST[512 + tid] = r.e1;
+    if (wv < 2) {
+        CST[1024 + tid] = r.b2;
+        CST[1536 + tid] = nv;
+    } else {
+        CST[1024 + tid] = nv;
+    }
+}
+
 // First group of A fragments of a pass ([rt][0]: k-steps 0, 1; [rt][1]: k-steps 2, 3).  Where the A buffer is not written by the
 // phase before the pass (HB in P1 and P4) they are read ahead of that phase's closing barrier, like the first weights; where
 // the barrier publishes the buffer (P3, P5, the Lp pass) right behind it.
@@ -240,9 +303,18 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
     const int64_t inst = blockIdx.x;
     const float* hrow = HB + (row0 + j) * SA + G * GA;          // this lane's A row of HB, tile 0
 #ifdef EAMRL_STAMPS
-    unsigned long long st_acc[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_t = __builtin_readcyclecounter();
+    unsigned long long st_acc[22] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_t = __builtin_readcyclecounter();
 #endif
 
+    // ---- what does not depend on h is requested first, so that one memory latency covers it and the loads of h: layer 0's
+    //      constants and the first weights of its P1 (head group 0) ---------------------------------------------------------
+    CstRaw cst = cst_request(a.L[0].bqkv, a.L[0].bo, a.L[0].b1, a.L[0].b2, a.L[0].n1_gamma, a.L[0].n1_beta, a.L[0].n1_mean,
+                             a.L[0].n1_var, a.L[0].n2_gamma, a.L[0].n2_beta, a.L[0].n2_mean, a.L[0].n2_var, a.norm, wv, tid);
+    const float* wp1[3];
+    float4 b1[3];
+#pragma unroll
+    for (int x = 0; x < 3; ++x) wp1[x] = a.L[0].Wqkv + ((int64_t)(8 * x + cw) * (FE / 16)) * 256 + lane * 4;
+    load_b0<3>(b1, wp1);
     // ---- h into the A layout; rows >= M are zero ---------------------------------------------------------------------
     if (a.h_in) load_h<ROWS>(a.h_in, M, L);
     else init_embedding<ROWS>(a.init, M, L);
@@ -251,42 +323,16 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
 
     for (int layer = 0; layer < a.nlayers; ++layer) {
         const eamrl_encoder_layer& Ly = a.L[layer];
-        // P1 of head group 0: its first weights and A fragments are requested ahead of the constants' barrier (h is stable
-        // since the barrier that ended the previous layer); those of group 1 ahead of P3 of group 0
-        const float* wp1[3];
-        float4 b1[3];
+        // P1 of head group 0: its first weights (wp1, b1) were requested at kernel entry / ahead of the previous layer's norm2,
+        // its first A fragments here (h is stable since the barrier that ended the previous layer); those of group 1 ahead of
+        // P3 of group 0
         float2 a1[RTW][2];
-#pragma unroll
-        for (int x = 0; x < 3; ++x) wp1[x] = Ly.Wqkv + ((int64_t)(8 * x + cw) * (FE / 16)) * 256 + lane * 4;
-        load_b0<3>(b1, wp1);
         load_a0<RTW, SA>(a1, hrow, nrt);
-        // ---- the layer's biases and normalisation constants -> LDS (one exposed L2 latency per layer instead of one per
-        //      pass: every accumulator is initialised with its bias before the first MFMA can issue) ------------------------
-        for (int i = tid; i < NCST; i += blockDim.x) {
-            float v;
-            if (i < C_BO) v = Ly.bqkv[i];
-            else if (i < C_B1) v = Ly.bo[i - C_BO];
-            else if (i < C_B2) v = Ly.b1[i - C_B1];
-            else if (i < C_N1) v = Ly.b2[i - C_B2];
-            else {
-                const bool second = i >= C_N2;
-                const int k = (i - (second ? C_N2 : C_N1));
-                const int c = k & (FE - 1);
-                const float* gam = second ? Ly.n2_gamma : Ly.n1_gamma;
-                const float* bet = second ? Ly.n2_beta : Ly.n1_beta;
-                if (a.norm == EAMRL_NORM_BATCH_EVAL) {
-                    const float* mean = second ? Ly.n2_mean : Ly.n1_mean;
-                    const float* var = second ? Ly.n2_var : Ly.n1_var;
-                    const float sc = gam[c] / __builtin_sqrtf(var[c] + a.eps);
-                    const float ms = mean[c] * sc;
-                    v = k < FE ? sc : bet[c] - ms;
-                } else {
-                    v = k < FE ? gam[c] : bet[c];
-                }
-            }
-            CST[i] = v;
-        }
+        // ---- the layer's biases and normalisation constants -> LDS (every accumulator is initialised with its bias before
+        //      the first MFMA can issue): requested a phase ago (cst_request), so this is a fold and a store, not a load ----
+        cst_store(CST, cst, a.norm, a.eps, wv, tid);
         __syncthreads();
+        ESTAMP(18);
         // out_proj accumulators: this wave's column tiles 2 cw, 2 cw + 1
         f32x4 acc_o[RTW][2];
 #pragma unroll
@@ -515,6 +561,15 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
             __syncthreads();
             ESTAMP(11);
         }
+        // ---- the next layer's constants and P1 weights fly during norm2 (after the last layer: the same layer again, unused) ----
+        {
+            const eamrl_encoder_layer& Ln = a.L[layer + 1 < a.nlayers ? layer + 1 : layer];
+            cst = cst_request(Ln.bqkv, Ln.bo, Ln.b1, Ln.b2, Ln.n1_gamma, Ln.n1_beta, Ln.n1_mean, Ln.n1_var, Ln.n2_gamma, Ln.n2_beta,
+                              Ln.n2_mean, Ln.n2_var, a.norm, wv, tid);
+#pragma unroll
+            for (int x = 0; x < 3; ++x) wp1[x] = Ln.Wqkv + ((int64_t)(8 * x + cw) * (FE / 16)) * 256 + lane * 4;
+            load_b0<3>(b1, wp1);
+        }
         // ---- h2 = norm2(h1 + ffn) -> HB ------------------------------------------------------------------------------------
         residual_norm_store<RTW>(acc_f, HB, row0, nrt, cw, j, G, a.norm, CST + C_N2);
         __syncthreads();
@@ -527,7 +582,19 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
     // ---- store h; skipped when the caller keeps only the decoder cache ----------------------------------------------------
     if (a.h_out) store_h(a.h_out, M, L);
     ESTAMP(13);
+    // the first weights of cache pass 0 fly during the graph context; those of pass sl + 1 during the global stores of pass sl
+    // (no branch around the request -- a load under a branch makes the graph context wait for it; without a cache it reads
+    // layer 0's weights, unused)
+    const float* wpc[2];
+    float4 bc[2];
+    {
+        const float* w0 = !a.cache.out ? a.L[0].Wqkv : a.cache.nproj == 0 ? a.cache.WoutT : a.cache.Wc;
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) wpc[ct] = w0 + ((int64_t)(2 * cw + ct) * (FE / 16)) * 256 + lane * 4;
+        load_b0<2>(bc, wpc);
+    }
     if (a.cache.gctx) graph_context(a.cache.Wg, a.cache.gctx, M, L, CST);          // the layer constants are dead
+    ESTAMP(19);
     // ---- decoder cache from the resident embeddings: nproj projections of h, then Lp = L Wout ------------------------------
     if (a.cache.out) {
         float* STG = QA;                           // L in the A layout (operand of the Lp pass); aliases the dead attention buffers
@@ -535,12 +602,6 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
         for (int sl = 0; sl <= a.cache.nproj; ++sl) {
             const bool lp = sl == a.cache.nproj;
             f32x4 acc[RTW][2];
-            const float* wp[2];
-            float4 b0[2];
-#pragma unroll
-            for (int ct = 0; ct < 2; ++ct)
-                wp[ct] = (lp ? a.cache.WoutT : a.cache.Wc + (int64_t)sl * FE * FE) + ((int64_t)(2 * cw + ct) * (FE / 16)) * 256 + lane * 4;
-            load_b0<2>(b0, wp);
 #pragma unroll
             for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
@@ -549,7 +610,15 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
             const float* arow = (lp ? STG : HB) + (row0 + j) * SA + G * GA;
             float2 a0[RTW][2];
             load_a0<RTW, SA>(a0, arow, nrt);
-            gemm_pass<RTW, 2, SA, FE / 16, true, RTT - RTA>(acc, arow, nrt, wp, b0, a0);
+            gemm_pass<RTW, 2, SA, FE / 16, true, RTT - RTA>(acc, arow, nrt, wpc, bc, a0);
+            {   // the next pass (after the last one: the same weights again, unused; no branch around a load)
+                const int sn = lp ? sl : sl + 1;
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct)
+                    wpc[ct] = (sn == a.cache.nproj ? a.cache.WoutT : a.cache.Wc + (int64_t)sn * FE * FE) +
+                              ((int64_t)(2 * cw + ct) * (FE / 16)) * 256 + lane * 4;
+                load_b0<2>(bc, wpc);
+            }
             // transposed tiles: lane = node row0 + 16 rt + j, registers = output columns 32 cw + 16 ct + 4 G + (0..3)
 #pragma unroll
             for (int rt = 0; rt < RTW; ++rt)
@@ -569,9 +638,11 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
                 }
         }
     }
+    ESTAMP(21);
 #ifdef EAMRL_STAMPS
-    if (lane == 0) {
-        for (int i = 0; i < 20; ++i) atomicAdd(&g_enc_stamps[i], st_acc[i]);
+    if (lane == 0) {       // [20] counts the wavefronts; [18] constants staging, [19] graph context, [21] cache passes
+        for (int i = 0; i < 22; ++i)
+            if (i != 20) atomicAdd(&g_enc_stamps[i], st_acc[i]);
         atomicAdd(&g_enc_stamps[20], 1ull);
     }
 #endif

@@ -32,7 +32,8 @@ constexpr int C_BQKV = 0, C_BO = 3 * FE, C_B1 = 4 * FE, C_B2 = 4 * FE + FF, C_N1
 // a reference to it: a pointer into the argument handed to a helper keeps the argument in scratch until the helper is
 // inlined, and the kernel then loses its scalar (uniform) loads -- other registers, other code (a reference to the kernel's
 // layout object delays its promotion to registers the same way).  For the same reason each
-// kernel stages its layer constants into CST itself: that loop reads the layer's pointers where it uses them.
+// kernel stages its layer constants into CST itself, reading the layer's pointers where it uses them (k_encoder_fused:
+// cst_request / cst_store, a phase apart; k_encoder_fused16: one loop at the layer top).
 struct FusedArgs {
     const float* h_in; float* h_out; int M; int nlayers; int norm; float eps;
     eamrl_encoder_cache cache;   // cache.out null: no decoder cache; cache.gctx null: no graph context
@@ -96,49 +97,77 @@ __device__ __forceinline__ void load_h(const float* h_in, int M, const Lay L)
 // The init embedding computed into LDS (nn/env_embeddings/init.py: Linear(F -> E) of the node features; depot envs: row 0
 // is Linear(2 -> E) of the depot coordinates): each output is chain_k(x[k], W[c][k], F, bias[c]), the order of
 // eamrl_linear.  Thread = (row, four adjacent columns); the weights of its columns stay in registers over the rows.
-template <int ROWS, typename Lay>
-__device__ __forceinline__ void init_embedding(const eamrl_encoder_init in, int M, const Lay L)
+// Like load_h, a thread issues ALL its loads -- weights, biases, the depot coordinates and the features of every row trip --
+// before the first wait, and none of them sits under a branch: an index past F or M is clamped (the value is then not
+// used; so is row 0 of feat in a depot env), an absent pointer is replaced by W at index 0.  The init_out stores follow the
+// LDS stores.
+// KM: the number of feature loads per row, F <= KM (init_embedding dispatches once on F).
+template <int ROWS, int KM, typename Lay>
+__device__ __forceinline__ void init_embedding_f(const eamrl_encoder_init in, int M, const Lay L)
 {
+    constexpr int NT = ROWS / 16;
     const int tid = threadIdx.x;
     const int64_t inst = blockIdx.x;
     const int q4 = tid % (FE / 4), r0 = tid / (FE / 4);          // 32 column groups x 16 row phases
     const int F = in.F;
-    float w[4][8], wd[4][2], bb[4], bdv[4];
+    const bool has_depot = in.depot != nullptr;
+    const float* bp = in.b ? in.b : in.W;
+    const float* bdp = (has_depot && in.bd) ? in.bd : in.W;
+    const float* wdp = has_depot ? in.Wd : in.W;
+    const float* dp = has_depot ? in.depot + inst * in.depot_ld : in.W;
+    const int bm = in.b ? 1 : 0, bdm = (has_depot && in.bd) ? 1 : 0, dm = has_depot ? 1 : 0;
+    float w[4][KM], wd[4][2], bb[4], bdv[4], x[NT][KM];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-        bb[c] = in.b ? in.b[4 * q4 + c] : 0.0f;
-        bdv[c] = (in.depot && in.bd) ? in.bd[4 * q4 + c] : 0.0f;
+        bb[c] = bp[(4 * q4 + c) * bm];
+        bdv[c] = bdp[(4 * q4 + c) * bdm];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) w[c][k] = (k < F) ? in.W[(4 * q4 + c) * F + k] : 0.0f;
+        for (int k = 0; k < KM; ++k) w[c][k] = in.W[(4 * q4 + c) * F + (k < F ? k : F - 1)];
 #pragma unroll
-        for (int k = 0; k < 2; ++k) wd[c][k] = in.depot ? in.Wd[(4 * q4 + c) * 2 + k] : 0.0f;
+        for (int k = 0; k < 2; ++k) wd[c][k] = wdp[((4 * q4 + c) * 2 + k) * dm];
     }
+    const float x0 = dp[0], x1 = dp[dm];
     const float* fsrc = in.feat + inst * (int64_t)M * F;
-    float* iout = in.init_out ? in.init_out + inst * (int64_t)M * FE : nullptr;
-    for (int row = r0; row < ROWS; row += 16) {
-        float y[4] = {0.f, 0.f, 0.f, 0.f};
-        if (row < M) {
-            if (in.depot && row == 0) {
-                const float x0 = in.depot[inst * in.depot_ld], x1 = in.depot[inst * in.depot_ld + 1];
 #pragma unroll
-                for (int c = 0; c < 4; ++c) y[c] = fma_(x1, wd[c][1], fma_(x0, wd[c][0], bdv[c]));
-            } else {
-                float x[8];
+    for (int t = 0; t < NT; ++t) {
+        const int row = r0 + 16 * t;
+        const float* fr = fsrc + (int64_t)(row < M ? row : M - 1) * F;
 #pragma unroll
-                for (int k = 0; k < 8; ++k) x[k] = (k < F) ? fsrc[(int64_t)row * F + k] : 0.0f;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    float acc = bb[c];
-#pragma unroll
-                    for (int k = 0; k < 8; ++k)
-                        if (k < F) acc = fma_(x[k], w[c][k], acc);
-                    y[c] = acc;
-                }
-            }
-            if (iout) *reinterpret_cast<float4*>(iout + (int64_t)row * FE + 4 * q4) = make_float4(y[0], y[1], y[2], y[3]);
-        }
-        L.store4(row, q4, make_float4(y[0], y[1], y[2], y[3]));
+        for (int k = 0; k < KM; ++k) x[t][k] = fr[k < F ? k : F - 1];
     }
+    __builtin_amdgcn_sched_barrier(0);         // (left alone, the scheduler sinks the later rows' loads behind the first rows' waits)
+    float y[NT][4];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const int row = r0 + 16 * t;
+        const bool drow = has_depot && row == 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            float acc = bm ? bb[c] : 0.0f;
+#pragma unroll
+            for (int k = 0; k < KM; ++k) acc = (k < F) ? fma_(x[t][k], w[c][k], acc) : acc;
+            const float yd = fma_(x1, wd[c][1], fma_(x0, wd[c][0], bdm ? bdv[c] : 0.0f));
+            y[t][c] = row < M ? (drow ? yd : acc) : 0.0f;
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) L.store4(r0 + 16 * t, q4, make_float4(y[t][0], y[t][1], y[t][2], y[t][3]));
+    if (in.init_out) {
+        float* iout = in.init_out + inst * (int64_t)M * FE;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const int row = r0 + 16 * t;
+            if (row < M) *reinterpret_cast<float4*>(iout + (int64_t)row * FE + 4 * q4) = make_float4(y[t][0], y[t][1], y[t][2], y[t][3]);
+        }
+    }
+}
+
+template <int ROWS, typename Lay>
+__device__ __forceinline__ void init_embedding(const eamrl_encoder_init in, int M, const Lay L)
+{
+    if (in.F <= 2) init_embedding_f<ROWS, 2>(in, M, L);
+    else if (in.F <= 4) init_embedding_f<ROWS, 4>(in, M, L);
+    else init_embedding_f<ROWS, 8>(in, M, L);
 }
 
 // InstanceNorm1d(affine) in place: thread = channel, sequential over the M nodes (the order of k_norm_instance)
