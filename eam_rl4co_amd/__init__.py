@@ -11,6 +11,11 @@ from .evolution import EA, EACvrpDraws, EAPrizeDraws, EADraws, evolution_worker,
 from .search import EAS, EASEmb, EASLay, eas_loss_coefficients  # noqa: F401
 from .critic import CriticNetwork, create_critic_from_actor  # noqa: F401
 from .train import PPOStep, ppo_loss_terms  # noqa: F401
+from .baselines import (REINFORCE_BASELINES_REGISTRY, CriticBaseline, ExponentialBaseline, MeanBaseline, NoBaseline,  # noqa: F401
+                        REINFORCEBaseline, RewardScaler, RolloutBaseline, SharedBaseline, WarmupBaseline,
+                        get_reinforce_baseline, paired_ttest)
+from .train import PolicyGradientStep, eam_am_loss, fit, reinforce_loss  # noqa: F401
+from .envs import ExtraKeyDataset, TensorDictDataset  # noqa: F401
 from .tensordict_lite import TensorDict  # noqa: F401
 from .utils import batchify, gather_by_index, unbatchify  # noqa: F401
 

@@ -282,7 +282,21 @@ class TensorDictDataset(torch.utils.data.Dataset):
 
     def __init__(self, td):
         self.data_len = td.batch_size[0]
-        self.data = [{k: v[i] for k, v in td.items()} for i in range(self.data_len)]
+        self.td = td            # whole-dataset consumers (the rollout baseline, train.fit) read the TensorDict as it lies
+        self._data = None
+
+    @property
+    def data(self):
+        """The list of per-instance dicts (views of `td`'s tensors), built when an item is first asked for: a consumer that
+        slices `td` never pays for a million dicts."""
+        if self._data is None:
+            td = self.td
+            self._data = [{k: v[i] for k, v in td.items()} for i in range(self.data_len)]
+        return self._data
+
+    @data.setter
+    def data(self, value):
+        self._data = value
 
     def __len__(self):
         return self.data_len
@@ -290,10 +304,35 @@ class TensorDictDataset(torch.utils.data.Dataset):
     def __getitem__(self, idx):
         return self.data[idx]
 
+    def add_key(self, key, value):
+        return ExtraKeyDataset(self, value, key_name=key)
+
     @staticmethod
     def collate_fn(batch):
         return TensorDict({k: torch.stack([b[k] for b in batch]) for k in batch[0].keys()},
                           batch_size=torch.Size([len(batch)]))
+
+
+class ExtraKeyDataset(TensorDictDataset):
+    """A dataset plus one more key per item, e.g. the rollout baseline's rewards under "extra" (rl4co/data/dataset.py:77-94)."""
+
+    def __init__(self, dataset: TensorDictDataset, extra: torch.Tensor, key_name="extra"):
+        self.data_len = len(dataset)
+        assert self.data_len == len(extra), "Data and extra must be same length"
+        self._base, self._data = dataset, None
+        self.extra = extra
+        self.key_name = key_name
+        td = getattr(dataset, "td", None)
+        self.td = None if td is None or td.device != extra.device else TensorDict({**dict(td.items()), key_name: extra}, batch_size=td.batch_size)
+
+    @property
+    def data(self):
+        return self._base.data
+
+    def __getitem__(self, idx):
+        data = self.data[idx]
+        data[self.key_name] = self.extra[idx]
+        return data
 
 
 def load_npz_to_tensordict(filename):

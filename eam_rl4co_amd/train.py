@@ -986,8 +986,43 @@ def attach_log_likelihood_grad(policy, td, env, actions, native_logp, num_starts
     return native_logp.detach() + (re - re.detach())
 
 
+_LEGACY_BASELINES = ("shared", "mean", "no", "critic")
+
+
+def _calculate_loss(baseline, scaler, td, env, out, reward, log_likelihood, extra=None, eam_shapes=False):
+    """REINFORCE.calculate_loss (reinforce.py:73-115); eam_shapes: EAM.calculate_loss (earl/model.py:409-457), which first
+    reshapes a 1-D baseline value -- concatenated with itself where it has half the rows of `reward`, else unsqueezed and
+    expanded to `reward`.  Updates `out` with loss, reinforce_loss, bl_loss, bl_val."""
+    bl_val, bl_loss = (extra, 0) if extra is not None else baseline.eval(td, reward, env)
+    if eam_shapes and torch.is_tensor(bl_val) and bl_val.dim() == 1:
+        if bl_val.shape[0] * 2 == reward.shape[0]:
+            bl_val = torch.cat([bl_val, bl_val], dim=0)
+        else:
+            bl_val = bl_val.unsqueeze(1).expand_as(reward)
+    advantage = reward - bl_val
+    if scaler is not None:
+        advantage = scaler(advantage)
+    reinforce_loss = -(advantage * log_likelihood).mean()
+    out.update({"loss": reinforce_loss + bl_loss, "reinforce_loss": reinforce_loss, "bl_loss": bl_loss, "bl_val": bl_val})
+    return out
+
+
+def _resolve_baseline(baseline, **kw):
+    from .baselines import REINFORCEBaseline, get_reinforce_baseline
+
+    return baseline if isinstance(baseline, REINFORCEBaseline) else get_reinforce_baseline(baseline, **kw)
+
+
+def _resolve_scaler(reward_scale):
+    from .baselines import RewardScaler
+
+    if reward_scale is None or isinstance(reward_scale, RewardScaler):
+        return reward_scale
+    return RewardScaler(reward_scale)
+
+
 def reinforce_loss(policy, env, td, baseline: str = "shared", num_starts: int = 0, decode_type: str = None, critic=None,
-                   **rollout_kwargs):
+                   extra=None, reward_scale=None, **rollout_kwargs):
     """One REINFORCE forward as the reference's trainers run it (REINFORCE.shared_step + calculate_loss,
     reinforce.py:59-106; POMO.shared_step, pomo/model.py:89-112): `policy(td, env, phase="train")` under autograd ->
     loss = -((reward - bl) * log_likelihood).mean().
@@ -995,8 +1030,19 @@ def reinforce_loss(policy, env, td, baseline: str = "shared", num_starts: int = 
     baseline: "shared" (POMO: mean over the starts of an instance, needs num_starts > 1), "mean" (batch mean), "no", or
     "critic" (CriticBaseline.eval, baselines.py:140-159: v = critic(td).squeeze(-1); the baseline is v.detach() and
     F.mse_loss(v, reward) is added to the loss; `critic`: a critic.CriticNetwork, single rows per instance).
+    These four strings keep their own expressions below.  Anything else is a `baselines.REINFORCEBaseline` object or a name of
+    `baselines.get_reinforce_baseline` ("exponential", "rollout", "warmup", "rollout_only"; unknown names raise ValueError) and
+    runs REINFORCE.calculate_loss as written (reinforce.py:73-115): bl_val, bl_loss = (extra, 0) if `extra` is given -- the
+    values `RolloutBaseline.wrap_dataset` stored with the batch -- else baseline.eval(td, reward, env); the advantage passes
+    through `reward_scale` (None, an int, "norm" / "scale", or a `baselines.RewardScaler` that keeps its running statistics
+    between calls); the output gains reinforce_loss, bl_loss and bl_val.  A baseline with state (exponential, warm-up,
+    rollout) must be passed as an object: a name builds a fresh one per call.  With num_starts > 1 reward and
+    log-likelihood are [B, S] there, as in POMO.shared_step.
     Returns dict(loss, reward, log_likelihood, actions, ...)."""
-    if baseline == "critic":
+    legacy = isinstance(baseline, str) and baseline in _LEGACY_BASELINES and extra is None and reward_scale is None
+    if not legacy:
+        bl = _resolve_baseline(baseline, **({"critic": critic} if isinstance(baseline, str) and baseline == "critic" else {}))
+    elif baseline == "critic":
         if critic is None:
             raise ValueError("reinforce_loss(baseline='critic') needs critic= (critic.create_critic_from_actor(policy))")
         if num_starts > 1:
@@ -1011,6 +1057,11 @@ def reinforce_loss(policy, env, td, baseline: str = "shared", num_starts: int = 
     actions, reward, logp = out["actions"], out["reward"], out["log_likelihood"]
     # finished CVRP rows are padded with depot visits of probability 1: their log-prob is 0 and carries no gradient
     ll = logp.sum(1)
+    if not legacy:
+        out_ = {"reward": reward, "log_likelihood": ll, "actions": actions, "logp_steps": logp, "native_log_likelihood": ll.detach()}
+        r, l2 = (unbatchify(reward, num_starts), unbatchify(ll, num_starts)) if num_starts > 1 else (reward, ll)
+        with torch.enable_grad():
+            return _calculate_loss(bl, _resolve_scaler(reward_scale), td, env, out_, r, l2, extra)
     if baseline == "shared":
         assert num_starts > 1, "shared baseline needs multistart"
         r = unbatchify(reward, num_starts)
@@ -1074,6 +1125,70 @@ def _eam_loss(policy, env, td, ea, S, improve, draws, generator, return_entropy=
     r_all, ll_all = torch.cat(rs, 0), torch.cat(lls, 0)              # [B or 2B, S]
     adv = r_all - r_all.mean(1, keepdim=True)
     res["loss"] = -(adv * ll_all).mean()
+    return res
+
+
+def eam_am_loss(policy, env, td, ea, baseline, extra=None, improve: bool = True, draws=None, generator=None,
+                return_entropy: bool = True, reward_scale=None):
+    """One EAM training step of the fork with the attention model's baseline, `EAM(baseline="rollout")`
+    (rl4co/models/zoo/earl/model.py:150-244 with its calculate_loss, 409-457):
+
+    1. one sampled tour per instance, `policy(td, env, phase="train")` (log-likelihood with grad; return_entropy as in `eam_loss`);
+    2. the tours are improved by `evolution_worker` on the GPU (single-start population; an `EA` with method="am");
+    3. the improved tours are evaluated by `policy(td, env, phase="train", actions=improved)`, on the encoder graph of step 1;
+    4. calculate_loss on the sampled rows [B, 1] and then, with improved tours, on [original; improved] as [2B, 1] rows -- the
+       second result is the step's loss.  baseline.eval is therefore called twice in such a step, as in the reference (an
+       exponential baseline moves twice); with `extra` (the values `RolloutBaseline.wrap_dataset` stored, [B]) it is not called.
+
+    The shapes are the reference's own: a 1-D `extra` of length B is concatenated to [2B] and subtracted from rewards [2B, 1],
+    so the advantage is [2B, 2B] -- row i holds reward_i minus EVERY instance's baseline value -- and the mean over all of
+    it makes the effective baseline of a step with `extra` the batch mean of the stored values.
+    baseline: a `baselines.REINFORCEBaseline` (e.g. get_reinforce_baseline("rollout") after setup) or a name.
+    Returns dict(loss, reinforce_loss, bl_loss, bl_val, reward, log_likelihood, actions[, improved_*][, entropy])."""
+    bl, scaler = _resolve_baseline(baseline), _resolve_scaler(reward_scale)
+    with shared_decoder_tensors(policy):        # one differentiable encoder pass for the sampled and the improved tours
+        return _eam_am_loss(policy, env, td, ea, bl, scaler, extra, improve, draws, generator, return_entropy)
+
+
+def _eam_am_loss(policy, env, td, ea, bl, scaler, extra, improve, draws, generator, return_entropy):
+    from .evolution import evolution_worker
+
+    with torch.enable_grad():
+        out = policy(td, env, phase="train", decode_type="sampling", return_entropy=return_entropy)
+    actions, reward, ll = out["actions"], out["reward"], out["log_likelihood"]
+    res = {"reward": reward, "log_likelihood": ll, "actions": actions}
+    if return_entropy:
+        res["entropy"] = out["entropy"]
+    r0, ll0 = reward[:, None], ll[:, None]                                   # unbatchify(x, (0, 1)): [B, 1]
+    with torch.enable_grad():
+        _calculate_loss(bl, scaler, td, env, res, r0, ll0, extra, eam_shapes=True)
+    if not improve:
+        return res
+    with torch.no_grad():
+        improved, _ = evolution_worker(actions, td, ea, env, draws=draws, generator=generator)
+        if improved is not None and improved.shape[-1] + 1 == actions.shape[-1]:          # _align_improved_actions
+            improved = torch.cat([actions[:, :1], improved], dim=-1)
+        if improved is not None and getattr(env, "name", None) == "op":
+            # An empty sampled tour (depot first) is the one parent the OP crossover rebuilds -- into a row that still starts at
+            # the depot and then visits customers: not an episode of the env.  Re-evaluated, such a row either raises
+            # "infeasible action selected" (seen at OP-20: sampled [0, 0, 0, 0], rebuilt [0, 2, 0, 0]) or comes back with a
+            # log-likelihood of -inf, which would make the whole [2B] loss infinite.  Such a row keeps its sampled tour: an
+            # unimproved copy.  Only this case is covered: both the sampled and the rebuilt row start at the depot.
+            empty = (actions[:, 0] == 0) & (improved[:, 0] == 0)
+            improved = torch.where(empty[:, None], actions, improved)
+    if improved is None:
+        return res
+    with torch.enable_grad():
+        out2 = policy(td, env, phase="train", actions=improved)
+        r_imp, ll_imp = out2["reward"], out2["log_likelihood"]
+        res.update(improved_actions=improved, improved_reward=r_imp, improved_log_likelihood=ll_imp)
+        r_all, ll_all = torch.cat([r0, r_imp[:, None]], 0), torch.cat([ll0, ll_imp[:, None]], 0)      # [2B, 1]
+        td2 = td
+        if extra is None:       # combined_td (model.py:234-238): only a baseline evaluated on the fly reads it
+            from .tensordict_lite import TensorDict
+
+            td2 = TensorDict({k: torch.cat([v, v], 0) for k, v in td.items() if torch.is_tensor(v)}, batch_size=[2 * td.batch_size[0]])
+        _calculate_loss(bl, scaler, td2, env, res, r_all, ll_all, extra, eam_shapes=True)
     return res
 
 
@@ -1179,24 +1294,64 @@ class PolicyGradientStep:
     shard, are averaged over the ranks after the step (`sync_buffers`; DDP broadcasts rank 0's instead)."""
 
     def __init__(self, policy, env, num_starts: int = 0, baseline: str = None, lr: float = 1e-4, weight_decay: float = 1e-6,
-                 max_grad_norm: float = 1.0, optimizer=None):
+                 max_grad_norm: float = 1.0, optimizer=None, baseline_kwargs: dict = None, reward_scale=None):
         from .dist import FlatGradBuffer, broadcast_module_state
 
         broadcast_module_state(policy, src=0)        # before the optimizer reads the parameters
         self.sync_buffers = any(b.is_floating_point() for b in policy.buffers())
         self.policy, self.env, self.S = policy, env, int(num_starts)
         self.baseline = baseline or ("shared" if self.S > 1 else "mean")
+        # "shared" / "mean" / "no" / "critic" stay the strings of `reinforce_loss`; every other value is a baseline object of
+        # `baselines` (REINFORCE.__init__, reinforce.py:51-57), with the epoch hooks below
+        if not (isinstance(self.baseline, str) and self.baseline in _LEGACY_BASELINES):
+            from .baselines import CriticBaseline
+
+            self.baseline = _resolve_baseline(self.baseline, **(baseline_kwargs or {}))
+            if isinstance(self.baseline, CriticBaseline) or isinstance(getattr(self.baseline, "baseline", None), CriticBaseline):
+                raise NotImplementedError("PolicyGradientStep: a CriticBaseline's parameters are not in this step's gradient buffer "
+                                          "or optimizer (use reinforce_loss with your own optimizer, or PPOStep)")
+        self.reward_scale = _resolve_scaler(reward_scale)
+        self.val_batch_size, self.val_data_size = 64, None
         self.max_grad_norm = max_grad_norm
         self.grads = FlatGradBuffer(policy)
         policy._flat_grads = self.grads
         self.optimizer = optimizer or torch.optim.Adam(policy.parameters(), lr=lr, weight_decay=weight_decay)
 
-    def __call__(self, td, **rollout_kwargs) -> dict:
+    # ---- the epoch hooks of REINFORCE (reinforce.py:117-147); no-ops with the four string baselines --------------------
+    def _hooked(self) -> bool:
+        return not isinstance(self.baseline, str)
+
+    def _device(self):
+        return next(self.policy.parameters()).device
+
+    def setup(self, batch_size: int = 64, dataset_size: int = None):
+        """post_setup_hook: baseline.setup(policy, env, batch_size=val_batch_size, device, dataset_size=val_data_size).
+        dataset_size is the size of the rollout baseline's evaluation dataset: required (at least 2) with "rollout" /
+        "rollout_only", where its absence raises ValueError here; unused by the other baselines."""
+        self.val_batch_size, self.val_data_size = int(batch_size), dataset_size
+        if self._hooked():
+            self.baseline.setup(self.policy, self.env, batch_size=self.val_batch_size, device=self._device(),
+                                dataset_size=dataset_size)
+
+    def wrap_dataset(self, dataset):
+        """The epoch's training dataset as the baseline wants it (the rollout baseline adds its values under "extra")."""
+        if not self._hooked():
+            return dataset
+        return self.baseline.wrap_dataset(dataset, self.env, batch_size=self.val_batch_size, device=self._device())
+
+    def on_epoch_end(self, epoch: int):
+        """on_train_epoch_end: the baseline's epoch_callback (the rollout baseline's challenge, the warm-up's alpha)."""
+        if self._hooked():
+            self.baseline.epoch_callback(self.policy, env=self.env, batch_size=self.val_batch_size, device=self._device(),
+                                         epoch=epoch, dataset_size=self.val_data_size)
+
+    def __call__(self, td, extra=None, **rollout_kwargs) -> dict:
         self.grads.zero_()
         if getattr(self.policy.decoder, "is_polynet", False):       # PolyNet trains on its Poppy loss (num_starts = k in the reference)
             out = polynet_step_loss(self.policy, self.env, td, self.S, **rollout_kwargs)
-        else:
-            out = reinforce_loss(self.policy, self.env, td, baseline=self.baseline, num_starts=self.S, **rollout_kwargs)
+        else:       # (one of the four strings without extra / reward_scale: reinforce_loss's own expressions, as before)
+            out = reinforce_loss(self.policy, self.env, td, baseline=self.baseline, num_starts=self.S, extra=extra,
+                                 reward_scale=self.reward_scale, **rollout_kwargs)
         out["loss"].backward()
         if not self.grads.attached():
             raise RuntimeError("PolicyGradientStep: p.grad is no longer a view of the flat buffer (zero_grad(set_to_none)?)")
@@ -1208,6 +1363,53 @@ class PolicyGradientStep:
 
             allreduce_buffers(self.policy)
         return out
+
+
+def fit(step, env, epochs: int, train_data_size: int, batch_size: int, val_data_size: int, val_batch_size: int = None,
+        lr_milestones=None, lr_gamma: float = 0.1, on_step=None) -> list:
+    """The reference's training loop around a `PolicyGradientStep`, as a plain loop (RL4COLitModule's setup / train
+    dataloader regenerated per epoch / on_train_epoch_end, rl/common/base.py; REINFORCE's hooks, reinforce.py:117-147):
+
+        step.setup(val_batch_size, val_data_size)       # val_data_size: required by the rollout baseline (>= 2 instances)
+        per epoch:  data = step.wrap_dataset(env.dataset([train_data_size]) as one TensorDict on the policy's device)
+                    per batch, in order (the data is fresh every epoch: no shuffle):  step(env.reset(batch), extra=batch["extra"] if any)
+                    step.on_epoch_end(epoch);  MultiStepLR(lr_milestones, lr_gamma).step() if milestones are given
+
+    The dataset never leaves the device; an epoch's mean loss and reward are read once, at its end.  on_step(epoch, i, out):
+    optional callback.  -> one dict per epoch: epoch, loss, reward, steps[, alpha][, baseline_mean]."""
+    from .baselines import as_tensordict
+
+    device = next(step.policy.parameters()).device
+    step.setup(batch_size=val_batch_size or batch_size, dataset_size=val_data_size)
+    sched = None
+    if lr_milestones:
+        sched = torch.optim.lr_scheduler.MultiStepLR(step.optimizer, milestones=list(lr_milestones), gamma=lr_gamma)
+    history = []
+    for epoch in range(int(epochs)):
+        data = step.wrap_dataset(as_tensordict(env.dataset([train_data_size]), device))
+        data = as_tensordict(data, device)
+        n = data.batch_size[0]
+        losses, rewards = [], []
+        for bi, i in enumerate(range(0, n, batch_size)):
+            batch = data[i:i + batch_size]
+            out = step(env.reset(batch), extra=batch.get("extra", None))
+            losses.append(out["loss"].detach())
+            rewards.append(out["reward"].detach().mean())
+            if on_step is not None:
+                on_step(epoch, bi, out)
+        step.on_epoch_end(epoch)
+        if sched is not None:
+            sched.step()
+        rec = {"epoch": epoch, "steps": len(losses), "loss": float(torch.stack(losses).mean()),
+               "reward": float(torch.stack(rewards).mean())}
+        bl = step.baseline
+        if hasattr(bl, "alpha"):
+            rec["alpha"] = float(bl.alpha)
+        inner = getattr(bl, "baseline", bl)
+        if hasattr(inner, "mean") and not callable(inner.mean):
+            rec["baseline_mean"] = float(inner.mean)
+        history.append(rec)
+    return history
 
 
 # ------------------------------------------------------------------------------------------------------------
