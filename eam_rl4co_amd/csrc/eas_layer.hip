@@ -5,100 +5,44 @@
 // project_out) and the autograd step of zoo/eas/search.py:202-259.  For obj = sum glogp[r,t] logp[r,t] and every decode step
 //     pre = h W1[b] + b1[b];  a = relu(pre);  y = h + a W2[b] + b2[b];  u[n] = y . Lp[b][n];  z = process(u / sqrt(E));  logp = z[act] - lse
 //     dY = du Lp[b];  dW2[b] += a^T dY;  db2[b] += sum dY;  dpre = (dY W2[b]^T) o [pre > 0];  dW1[b] += h^T dpre;  db1[b] += sum dpre
-// with du exactly as k_reeval_bwd_lp computes it (reeval.hip), the normaliser recovered from the rollout's log-prob when no lse
-// is given.  h is the rollout's captured glimpse output (eamrl_reeval.heads): nothing upstream of it is adapted, so there is no
-// dh, no glimpse backward and no gather.
+// The logits of y, du (the normaliser recovered from the rollout's log-prob when no lse is given) and dY are the stages of
+// reeval_tile.hpp that the re-evaluation backward kernels of reeval.hip run: logit_tile on the y tile, logit_bwd_tile,
+// lpt_du.  A step with one feasible node and a step past heads_T take no gradient: that is this kernel's own `live`, which enters
+// logit_bwd_tile as g = 0.  h is the rollout's captured glimpse output (eamrl_reeval.heads): nothing upstream of it is adapted,
+// so there is no dh, no glimpse backward and no gather.
 //
 // Structure: the grid and 16-query tiling of k_reeval_bwd_lp -- one workgroup of 8 wavefronts per (instance, row chunk).  Wave w
 // owns the columns 16 w .. 16 w + 15 of pre / a / y / dY / dpre and the rows 16 w .. 16 w + 15 of dW1 and dW2: 2 x 8 accumulator
 // tiles = 64 registers per lane, kept across all tiles and flushed once with float atomics (nchunk workgroups share an
-// instance).  The forward weights stream from L2 in fragment order (w_load / w_gemm of the rollout kernel); the wave's 16 rows
-// of W2 for the dpre product (contraction over W2's columns) are 32 registers, loaded once.  Tiles are not software-pipelined:
-// seven barriers per tile (eight when the normaliser is recovered).
-// LDS: HT | AT | YT | DYT [16][TS] each (h, a, y then dpre, dY; A layout) | DU [16 RTT][DS] | LSE [16] | LPT [8][RTT][64][4].
-#include "kernels.hpp"
+// instance).  The forward weights stream from L2 in fragment order (w_load / w_gemm of mfma_tile.hpp, as in the rollout kernel);
+// the wave's 16 rows of W2 for the dpre product (contraction over W2's columns) are 32 registers, loaded once.  Tiles are not
+// software-pipelined: seven barriers per tile (eight when the normaliser is recovered).  LDS: LayLds.
+#include "reeval_tile.hpp"
 
 namespace eamrl {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
-constexpr int RE = 128;
-constexpr int TS = 140, TG = 34;     // A-layout tile buffers [16][TS]: element (j, c) at j * TS + (c & 3) * TG + (c >> 2)
-constexpr int DS = 17;               // row stride of the du tile ([n][q])
-constexpr float LOG2E = 1.44269504088896341f;
-
-__device__ __forceinline__ f32x4 mf(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x4 z4() { return (f32x4){0.f, 0.f, 0.f, 0.f}; }
-__device__ __forceinline__ float fexp(float x) { return __builtin_amdgcn_exp2f(x * LOG2E); }
-
-// z (processed logit) and dz/du of one accumulator value (as reeval.hip)
-__device__ __forceinline__ float process_logit(float u, float clip, float inv_temp, float& dzdu)
-{
-    u *= 0.08838834764831845f;                      // 1 / sqrt(128)
-    float z = u, d = 1.0f;
-    if (clip > 0.0f) {
-        const float e2 = fexp(2.0f * u);
-        const float th = 1.0f - 2.0f / (e2 + 1.0f);
-        z = clip * th;
-        d = clip * (1.0f - th * th);
-    }
-    dzdu = d * inv_temp * 0.08838834764831845f;
-    return z * inv_temp;
-}
-
-// walks the queries l = tile * 16 + lane slot of a row chunk: l = sl * T + t
-struct QWalk {
-    int sl, t;
-    __device__ __forceinline__ void init(int l, int T) { sl = l / T; t = l - sl * T; }
-    __device__ __forceinline__ void next(int T)
-    {
-        t += 16;
-        while (t >= T) { t -= T; ++sl; }
-    }
+template <int RTT>
+struct LayLds {         // the kernel's dynamic LDS (float offsets): its carve-up and the byte count at its launch both read this
+    static constexpr int HT = 0;                        // [16][TS]  h
+    static constexpr int AT = HT + 16 * TS;             // [16][TS]  a = relu(pre)
+    static constexpr int YT = AT + 16 * TS;             // [16][TS]  y, then dpre
+    static constexpr int DYT = YT + 16 * TS;            // [16][TS]  dY
+    static constexpr int DU = DYT + 16 * TS;            // [16 RTT][DS]
+    static constexpr int LSE = DU + 16 * RTT * DS;      // [16]
+    static constexpr int LPT = LSE + 16;                // [8 waves][RTT][64 lanes][4]  Lp^T fragments of the dY product
+    static constexpr int END = LPT + 8 * RTT * 256;
+    static constexpr size_t bytes = (size_t)END * sizeof(float);
 };
-
-// fragment-order weight stream (eamrl_eas_layer): a piece = four 16-byte A-fragment loads = 16 k-steps of one row tile
-constexpr int PQ = 4;
-__device__ __forceinline__ void w_load(f32x4 (&dst)[PQ], const float* W, int piece, int lane)
-{
-    const f32x4* wp = reinterpret_cast<const f32x4*>(W) + piece * (PQ * 64) + lane;
-#pragma unroll
-    for (int i = 0; i < PQ; ++i) dst[i] = wp[64 * i];
-}
-__device__ __forceinline__ void w_gemm(const f32x4 (&w)[PQ], const float* hp, f32x4& acc0, f32x4& acc1)
-{
-#pragma unroll
-    for (int i = 0; i < PQ; ++i) {
-        const float2 lo = *reinterpret_cast<const float2*>(hp + 4 * i), hi = *reinterpret_cast<const float2*>(hp + 4 * i + 2);
-        f32x4& acc = (i & 1) ? acc1 : acc0;
-        acc = mf(w[i][0], lo.x, acc); acc = mf(w[i][1], lo.y, acc);
-        acc = mf(w[i][2], hi.x, acc); acc = mf(w[i][3], hi.y, acc);
-    }
-}
-
-// sum over the 16 lanes that share a lane group (the tile's 16 queries)
-__device__ __forceinline__ float row16_sum(float v)
-{
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    v += __shfl_xor(v, 4, 64);
-    v += __shfl_xor(v, 8, 64);
-    return v;
-}
 
 template <int RTT>
 __global__ __launch_bounds__(512) void k_eas_layer_bwd(ReevalArgs a, eamrl_eas_layer ly)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* HT = lds;                                // [16][TS]  h
-    float* AT = HT + 16 * TS;                       // [16][TS]  a = relu(pre)
-    float* YT = AT + 16 * TS;                       // [16][TS]  y, then dpre
-    float* DYT = YT + 16 * TS;                      // [16][TS]  dY
-    float* DU = DYT + 16 * TS;                      // [16 RTT][DS]
-    float* LSE = DU + 16 * RTT * DS;                // [16]
-    float* LPT = LSE + 16;                          // [8 waves][RTT][64 lanes][4]  Lp^T fragments of the dY product
+    using L = LayLds<RTT>;
+    float *HT = lds + L::HT, *AT = lds + L::AT, *YT = lds + L::YT, *DYT = lds + L::DYT, *DU = lds + L::DU, *LSE = lds + L::LSE;
+    float* LPT = lds + L::LPT;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 15, G = lane >> 4;
@@ -114,23 +58,10 @@ __global__ __launch_bounds__(512) void k_eas_layer_bwd(ReevalArgs a, eamrl_eas_l
     const float* W2b = ly.W2 + b * (RE * RE);
 
     // ---- instance operands (once) --------------------------------------------------------------------------------------
-    float lpf[32];                                  // Lp rows of key tile wv (keys in pi order), as k_reeval_bwd_lp
-    {
-        const int kt = wv < RTT ? wv : RTT - 1, n = 16 * kt + 4 * (j & 3) + (j >> 2);
-#pragma unroll
-        for (int t = 0; t < 32; ++t) lpf[t] = n < a.M ? a.Lp[(b * a.M + n) * a.ld + 4 * t + G] : 0.0f;
-    }
+    float lpf[32];                                  // Lp rows of key tile wv (keys in pi order)
+    load_lp_frags(a, b, wv < RTT ? wv : RTT - 1, lane, lpf);       // (waves >= RTT compute no logits)
     float4* lpt = reinterpret_cast<float4*>(LPT) + wv * RTT * 64 + lane;
-#pragma unroll
-    for (int t4 = 0; t4 < RTT; ++t4) {              // Lp^T: row e = 16 wv + j, k index = key 4 t + G, t = 4 t4 + i
-        float kk[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int n = 4 * (4 * t4 + i) + G;
-            kk[i] = n < a.M ? a.Lp[(b * a.M + n) * a.ld + 16 * wv + j] : 0.0f;
-        }
-        lpt[t4 * 64] = make_float4(kk[0], kk[1], kk[2], kk[3]);
-    }
+    fill_lpt<RTT>(a, b, wv, lane, lpt);
     // W2 rows 16 wv + j as the A operand of dpre = dY W2^T: w2r[t] = W2[16 wv + j][4 t + G], picked out of the fragment order
     // (block float 4 ((T 8 + q) 64 + l) + i holds W[16 q + 4 i + l / 16][16 T + l % 16])
     float w2r[32];
@@ -173,7 +104,7 @@ __global__ __launch_bounds__(512) void k_eas_layer_bwd(ReevalArgs a, eamrl_eas_l
         const bool live = qj >= 0 && tj >= a.tstart && tj - a.tstart < a.heads_T && nfeas > 1;
         const int act = qj >= 0 ? (int)a.actions[qjc] : -1;
         const float g = live ? a.glogp[qjc] : 0.0f;
-        float lse = live ? (derive_lse ? a.logp[qjc] : a.lse[qjc]) : 0.0f;
+        const float lse = live ? (derive_lse ? a.logp[qjc] : a.lse[qjc]) : 0.0f;
         f32x4 wa[PQ], wb[PQ];
         w_load(wa, W1b, 2 * wv, lane);
         w_load(wb, W1b, 2 * wv + 1, lane);
@@ -212,57 +143,16 @@ __global__ __launch_bounds__(512) void k_eas_layer_bwd(ReevalArgs a, eamrl_eas_l
             for (int r = 0; r < 4; ++r) yp[r * TG] = y[r];
         }
         __syncthreads();                // (3) y is published
-        // ---- logits of key tile wv and du, as k_reeval_bwd_lp --------------------------------------------------------------------
-        float zr[4] = {0.f, 0.f, 0.f, 0.f}, dz[4] = {0.f, 0.f, 0.f, 0.f};
-        if (wv < RTT) {
-            const float* hp = YT + j * TS + G * TG;
+        // ---- logits of key tile wv (of y) and du; the eighth barrier is inside, when the normaliser is recovered -----------------
+        {
             f32x4 u = z4();
-#pragma unroll
-            for (int g4 = 0; g4 < 8; ++g4) {
-                const float2 lo = *reinterpret_cast<const float2*>(hp + 4 * g4), hi = *reinterpret_cast<const float2*>(hp + 4 * g4 + 2);
-                u = mf(lpf[4 * g4 + 0], lo.x, u);
-                u = mf(lpf[4 * g4 + 1], lo.y, u);
-                u = mf(lpf[4 * g4 + 2], hi.x, u);
-                u = mf(lpf[4 * g4 + 3], hi.y, u);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) zr[r] = process_logit(u[r], a.clip, inv_temp, dz[r]);
-        }
-        if (derive_lse) {               // the lane that owns the chosen node publishes z[action] - logp for its query
-            if (wv < RTT) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if (16 * wv + 4 * r + G == act && g != 0.0f) LSE[j] = zr[r] - lse;
-            }
-            __syncthreads();
-            if (g != 0.0f) lse = LSE[j];
-        }
-        if (wv < RTT) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int n0 = 16 * wv + 4 * r;
-                const uint32_t w = (n0 >> 5) == 0 ? mb.x : (n0 >> 5) == 1 ? mb.y : (n0 >> 5) == 2 ? mb.z : mb.w;
-                const bool ok = (w >> ((n0 & 31) + G)) & 1u;
-                float du = 0.0f;
-                if (ok && g != 0.0f) {
-                    const float p = fexp(zr[r] - lse);
-                    du = g * ((n0 + G == act ? 1.0f : 0.0f) - p) * dz[r];
-                }
-                DU[(n0 + G) * DS + j] = du;
-            }
+            if (wv < RTT) u = logit_tile(lpf, YT, lane);
+            logit_bwd_tile(u, wv < RTT, wv, lane, mb, act, g, lse, derive_lse, a.clip, inv_temp, LSE, DU);
         }
         __syncthreads();                // (4) du is published
         // ---- dY = du Lp: columns 16 wv + 4 G + r of query j -------------------------------------------------------------------
         {
-            f32x4 dy = z4();
-#pragma unroll
-            for (int t4 = 0; t4 < RTT; ++t4) {
-                const float4 ll = lpt[t4 * 64];
-                dy = mf(ll.x, DU[(16 * t4 + G) * DS + j], dy);
-                dy = mf(ll.y, DU[(16 * t4 + 4 + G) * DS + j], dy);
-                dy = mf(ll.z, DU[(16 * t4 + 8 + G) * DS + j], dy);
-                dy = mf(ll.w, DU[(16 * t4 + 12 + G) * DS + j], dy);
-            }
+            const f32x4 dy = lpt_du<RTT>(lpt, DU, lane);
             float* yp = DYT + j * TS + 4 * wv + G;
 #pragma unroll
             for (int r = 0; r < 4; ++r) yp[r * TG] = dy[r];
@@ -291,18 +181,14 @@ __global__ __launch_bounds__(512) void k_eas_layer_bwd(ReevalArgs a, eamrl_eas_l
         // ---- dW2 += a^T dY, dW1 += h^T dpre: wave wv the rows 16 wv .. + 15, contraction over the tile's 16 queries --------------
         {
             float aa[4], ha[4];
-            const int c = 16 * wv + j;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                aa[t] = AT[(4 * t + G) * TS + (c & 3) * TG + (c >> 2)];
-                ha[t] = HT[(4 * t + G) * TS + (c & 3) * TG + (c >> 2)];
-            }
+            load_tile_col(AT, wv, lane, aa);
+            load_tile_col(HT, wv, lane, ha);
 #pragma unroll
             for (int nt = 0; nt < 8; ++nt) {
                 const int c2 = 16 * nt + j;
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
-                    const int o = (4 * t + G) * TS + (c2 & 3) * TG + (c2 >> 2);
+                    const int o = (4 * t + G) * TS + a_off(c2);
                     dW2[nt] = mf(aa[t], DYT[o], dW2[nt]);
                     dW1[nt] = mf(ha[t], YT[o], dW1[nt]);
                 }
@@ -334,7 +220,8 @@ __global__ __launch_bounds__(512) void k_eas_layer_bwd(ReevalArgs a, eamrl_eas_l
 template <int RTT>
 int launch_t(const ReevalArgs& a, const eamrl_eas_layer& ly, hipStream_t st)
 {
-    const size_t lds = (size_t)(4 * 16 * TS + 16 * RTT * DS + 16 + 8 * RTT * 256) * sizeof(float);
+    const size_t lds = LayLds<RTT>::bytes;
+    static_assert(lds == (size_t)(4 * 16 * TS + 16 * RTT * DS + 16 + 8 * RTT * 256) * sizeof(float), "the byte count spelled out before LayLds");
     auto k = k_eas_layer_bwd<RTT>;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return EAMRL_E_LAUNCH;

@@ -19,36 +19,21 @@
 // the instance (K, V, Lp slices) live in REGISTERS as MFMA fragments for the whole launch, LDS only stages the tile's query /
 // head vectors.  Score tiles are computed transposed (S^T = K Q^T: lane = query, registers = keys) with the keys placed on
 // MFMA rows so that the accumulators are directly the B operand of the products that contract over the keys.
-#include "kernels.hpp"
+#include "reeval_tile.hpp"
 
 namespace eamrl {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
-constexpr int RE = 128, RH = 8;      // embed dim, heads (D = 16)
-constexpr int TS = 140, TG = 34;     // A-layout tile buffers [16][TS]: element (j, c) at j * TS + (c & 3) * TG + (c >> 2)
-constexpr float LOG2E = 1.44269504088896341f;
+constexpr int RH = 8;                // heads (D = 16; the embed dim RE is reeval_tile.hpp's)
 
-__device__ __forceinline__ f32x4 mf(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x4 z4() { return (f32x4){0.f, 0.f, 0.f, 0.f}; }
-__device__ __forceinline__ float fexp(float x) { return __builtin_amdgcn_exp2f(x * LOG2E); }
-
-// combine over the four lane groups (lanes l, l^16, l^32, l^48) that share a query
+// maximum over the four lane groups that share a query (its own copy: fmaxf here, where rollout_multistart.hip's takes vmax_raw)
 __device__ __forceinline__ float group_max(float v)
 {
     auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
     v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
     auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
     return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float group_sum(float v)
-{
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
 }
 
 // ---- SDVRP: the dynamic embedding (rl4co/models/nn/env_embeddings/dynamic.py:59-78) ---------------------------------------
@@ -308,24 +293,7 @@ __device__ __forceinline__ void glimpse_tile(const float (&kf)[RTT][4], const fl
     for (int r = 0; r < 4; ++r) hp[r * TG] = o[r] * iz;
 }
 
-// u^T tile of key tile kt against the heads tile: A = Lp rows (keys in pi order), B = heads^T
-__device__ __forceinline__ f32x4 logit_tile(const float (&lpf)[32], const float* HT, int lane)
-{
-    const int j = lane & 15, G = lane >> 4;
-    const float* hp = HT + j * TS + G * TG;
-    f32x4 u = z4();
-#pragma unroll
-    for (int g4 = 0; g4 < 8; ++g4) {
-        const float2 lo = *reinterpret_cast<const float2*>(hp + 4 * g4), hi = *reinterpret_cast<const float2*>(hp + 4 * g4 + 2);
-        u = mf(lpf[4 * g4 + 0], lo.x, u);
-        u = mf(lpf[4 * g4 + 1], lo.y, u);
-        u = mf(lpf[4 * g4 + 2], hi.x, u);
-        u = mf(lpf[4 * g4 + 3], hi.y, u);
-    }
-    return u;
-}
-
-// DYN: also hl = heads[j] . lw for the lane's query (lw_in[4 g4 + i] = lw[16 g4 + 4 i + G], the staged heads' layout; registers in
+// logit_tile with DYN: also hl = heads[j] . lw for the lane's query (lw_in[4 g4 + i] = lw[16 g4 + 4 i + G], the staged heads' layout; registers in
 // the forward kernel, an LDS copy [G][32] in the backward one, which has none to spare)
 template <typename LW>
 __device__ __forceinline__ f32x4 logit_tile_dyn(const float (&lpf)[32], const float* HT, int lane, const LW& lw_in, float& hl)
@@ -352,28 +320,6 @@ __device__ __forceinline__ void load_lw_in(const float* dyn, int G, float (&lw_i
     for (int g4 = 0; g4 < 8; ++g4)
 #pragma unroll
         for (int i = 0; i < 4; ++i) lw_in[4 * g4 + i] = dyn[2 * RE + 16 * g4 + 4 * i + G];
-}
-
-__device__ __forceinline__ void load_lp_frags(const ReevalArgs& a, int64_t b, int kt, int lane, float (&lpf)[32])
-{
-    const int j = lane & 15, G = lane >> 4, n = 16 * kt + 4 * (j & 3) + (j >> 2);
-#pragma unroll
-    for (int t = 0; t < 32; ++t) lpf[t] = n < a.M ? a.Lp[(b * a.M + n) * a.ld + 4 * t + G] : 0.0f;
-}
-
-// z (processed logit) and dz/du of one accumulator value
-__device__ __forceinline__ float process_logit(float u, float clip, float inv_temp, float& dzdu)
-{
-    u *= 0.08838834764831845f;                      // 1 / sqrt(128)
-    float z = u, d = 1.0f;
-    if (clip > 0.0f) {
-        const float e2 = fexp(2.0f * u);
-        const float th = 1.0f - 2.0f / (e2 + 1.0f);
-        z = clip * th;
-        d = clip * (1.0f - th * th);
-    }
-    dzdu = d * inv_temp * 0.08838834764831845f;
-    return z * inv_temp;
 }
 
 }  // namespace
@@ -734,18 +680,6 @@ int launch_reeval_fwd(const ReevalArgs& a0, hipStream_t st)
 // products that consume tile i's du -- two barriers per tile (three when the normaliser is derived from the rollout's
 // log-probs), with MFMA work of every wave on both sides of each.
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int DS = 17;        // row stride of the du tile ([n][q])
-
-struct QWalk {          // query l = first, first + 16, ... of the chunk as (start offset, step)
-    int sl, t;
-    __device__ __forceinline__ void init(int l, int T) { sl = l / T; t = l - sl * T; }
-    __device__ __forceinline__ void next(int T)
-    {
-        t += 16;
-        while (t >= T) { t -= T; ++sl; }
-    }
-};
-
 // One thread's share (query jq, columns 4 e4 ..) of a tile's inputs.  The loads are branch-free: an exec-masked load
 // into a register that the loop later overwrites makes the compiler wait for EVERY outstanding load before the overwrite
 // (the pending-load state merges over the skipped branch), which serialises the prefetch.  Queries past the end of the
@@ -816,18 +750,30 @@ __device__ __forceinline__ uint4 load_mask_words(const ReevalArgs& a, int qi)
 // infeasible node never enters (no 0 * -inf), a step before tstart or past the chunk has gent forced to 0, and a step whose
 // forward entropy is exactly 0 -- what the forward writes for a single feasible node -- takes no entropy gradient at all.
 // ENT = false is the kernel as it was: no extra load, register or branch.
+// The kernel's dynamic LDS (float offsets): the carve-up in the kernel and the byte count at its launch both read this.
+template <int RTT>
+struct LogitsLds {
+    static constexpr int QTB = 0;                       // [2][16][TS]   q~ tiles (A layout)
+    static constexpr int HTB = QTB + 2 * 16 * TS;       // [2][16][TS]   heads tiles
+    static constexpr int LPT = HTB + 2 * 16 * TS;       // [8 waves][RTT][64 lanes][4]  Lp^T fragments of the dheads product
+    static constexpr int CV = LPT + 8 * RTT * 256;      // [2][128] state-column vectors
+    static constexpr int DU = CV + 2 * RE;              // [16 RTT][DS]
+    static constexpr int LSE = DU + 16 * RTT * DS;      // [16]
+    static constexpr int SDR = LSE + 16;                // DYN: [2][16]  sum_n du[q][n] rem[q][n], summed over the key tiles (LDS atomics)
+    static constexpr int REMB = SDR + 32;               // DYN: [2][16][16 RTT]  staged remaining demands
+    static constexpr int LWL = REMB + 2 * 16 * 16 * RTT;    // DYN: [4 lane groups][32]  lw in the staged heads' layout
+    static constexpr int DYNL = LWL + 128;              // DYN: [2][E]  wk | wv
+    static constexpr int END = DYNL + 2 * RE;
+    static constexpr size_t bytes(bool dyn) { return (size_t)(dyn ? END : REMB) * sizeof(float); }      // (SDR is carved either way)
+};
+
 template <int RTT, bool HEADS, bool DYN = false, bool ENT = false>
 __global__ __launch_bounds__(512, 2) void k_reeval_bwd_logits(ReevalArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* QTB = lds;                               // [2][16][TS]   q~ tiles (A layout)
-    float* HTB = QTB + 2 * 16 * TS;                 // [2][16][TS]   heads tiles
-    float* LPT = HTB + 2 * 16 * TS;                 // [8 waves][RTT][64 lanes][4]  Lp^T fragments of the dheads product
-    float* CV = LPT + 8 * RTT * 256;                // [2][128] state-column vectors
-    float* DU = CV + 2 * RE;                        // [16 RTT][DS]
-    float* LSE = DU + 16 * RTT * DS;                // [16]
-    float* SDR = LSE + 16;                          // DYN: [2][16]  sum_n du[q][n] rem[q][n], summed over the key tiles (LDS atomics)
-    float* REMB = SDR + 32;                         // DYN: [2][16][16 RTT]  staged remaining demands
+    using L = LogitsLds<RTT>;
+    float *QTB = lds + L::QTB, *HTB = lds + L::HTB, *LPT = lds + L::LPT, *CV = lds + L::CV, *DU = lds + L::DU, *LSE = lds + L::LSE;
+    float *SDR = lds + L::SDR, *REMB = lds + L::REMB, *LWL = lds + L::LWL, *DYNL = lds + L::DYNL;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 15, G = lane >> 4;
@@ -845,8 +791,6 @@ __global__ __launch_bounds__(512, 2) void k_reeval_bwd_logits(ReevalArgs a)
     const bool derive_lse = a.lse == nullptr;
 
     float kf[RTT][4], vtf[4 * RTT], lpf[32], lw_out[4] = {0.f, 0.f, 0.f, 0.f}, dlw_acc = 0.0f;
-    float* LWL = REMB + 2 * 16 * 16 * RTT;         // DYN: [4 lane groups][32]  lw in the staged heads' layout
-    float* DYNL = LWL + 128;                        // DYN: [2][E]  wk | wv
     const float* lw_in = LWL + 32 * G;
     const DynLane dl = {DYNL, wv, G};
     if (!HEADS) load_head_frags<RTT>(a, b, wv, lane, kf, vtf);
@@ -858,16 +802,7 @@ __global__ __launch_bounds__(512, 2) void k_reeval_bwd_logits(ReevalArgs a)
         for (int r = 0; r < 4; ++r) lw_out[r] = a.dyn[2 * RE + 16 * wv + 4 * G + r];      // the dheads accumulator's columns
     }
     float4* lpt = reinterpret_cast<float4*>(LPT) + wv * RTT * 64 + lane;
-#pragma unroll
-    for (int t4 = 0; t4 < RTT; ++t4) {              // Lp^T: row e = 16 wv + j, k index = key 4 t + G, t = 4 t4 + i
-        float kk[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int n = 4 * (4 * t4 + i) + G;
-            kk[i] = n < a.M ? a.Lp[(b * a.M + n) * a.ld + 16 * wv + j] : 0.0f;
-        }
-        lpt[t4 * 64] = make_float4(kk[0], kk[1], kk[2], kk[3]);
-    }
+    fill_lpt<RTT>(a, b, wv, lane, lpt);
     for (int i = tid; i < 2 * RE; i += blockDim.x) CV[i] = i < a.NC * RE ? a.Cvec[i] : 0.0f;
     float4 gc = make_float4(0.f, 0.f, 0.f, 0.f);
     if (a.gctx) gc = *reinterpret_cast<const float4*>(a.gctx + b * RE + 4 * e4);
@@ -880,18 +815,10 @@ __global__ __launch_bounds__(512, 2) void k_reeval_bwd_logits(ReevalArgs a)
     auto qi_of = [&](const QWalk& w) -> int { return w.sl < ns ? ((s0 + w.sl) * (int)a.B + (int)b) * T + w.t : -1; };
     // HEADS: the rollout kept every step's glimpse output (eamrl_state.heads_out) -- the tile's heads rows are fetched
     // instead of the query rows and nothing of the glimpse is recomputed
-    auto load_heads = [&](const QWalk& w, RowPre& p) {
+    auto load_heads_rem = [&](const QWalk& w, RowPre& p) {
         const int qi = qi_of(w);
-        const int64_t r = (int64_t)(s0 + min(w.sl, ns - 1)) * a.B + b;
-        const int th = max(w.t - a.tstart, 0);
-        p.fl = (qi >= 0 ? 1 : 0) | (w.t >= a.tstart && th < a.heads_T ? 8 : 0);
-        p.dh = *reinterpret_cast<const float4*>(a.heads + (r * a.heads_T + min(th, a.heads_T - 1)) * RE + 4 * e4);
+        load_heads(a, b, s0, ns, e4, w, qi, p.fl, p.dh);
         if (DYN) p.rem = *reinterpret_cast<const float4*>(a.rem + (int64_t)max(qi, 0) * (RMP * a.nkc) + 4 * e4);
-    };
-    auto stage_heads = [&](const RowPre& p, int buf) {
-        const bool ok = (p.fl & 9) == 9;
-        float* dp = HTB + buf * 16 * TS + jq * TS + e4;
-        dp[0] = ok ? p.dh.x : 0.0f; dp[TG] = ok ? p.dh.y : 0.0f; dp[2 * TG] = ok ? p.dh.z : 0.0f; dp[3 * TG] = ok ? p.dh.w : 0.0f;
     };
     // ---- prologue: tile 0 staged, indices of tile 1 in flight --------------------------------------------------------
     QWalk wr, wj;                       // the staging role (query jq) and the MFMA role (query j) of this thread
@@ -901,8 +828,8 @@ __global__ __launch_bounds__(512, 2) void k_reeval_bwd_logits(ReevalArgs a)
     {
         RowPre pre;
         if (HEADS) {
-            load_heads(wr, pre);
-            stage_heads(pre, 0);
+            load_heads_rem(wr, pre);
+            stage_heads(pre.fl, pre.dh, HTB, jq, e4);
             if (DYN) stage_rem<RTT>(REMB, jq, e4, pre.rem, pre.fl & 1);
         } else {
             load_idx(a, qr, ia, ib);
@@ -929,7 +856,7 @@ __global__ __launch_bounds__(512, 2) void k_reeval_bwd_logits(ReevalArgs a)
         if (tile >= 0) {
             RowPre pre;
             if (HEADS) {
-                load_heads(wr, pre);                                // heads rows of tile + 1
+                load_heads_rem(wr, pre);                            // heads rows of tile + 1
                 wr.next(T);
             } else {
                 load_rows<false, DYN>(a, b, e4, qr, wr.t, ia, ib, pre);  // rows of tile + 1 (indices fetched one iteration ago)
@@ -965,6 +892,9 @@ __global__ __launch_bounds__(512, 2) void k_reeval_bwd_logits(ReevalArgs a)
             const float g = live ? g_l : 0.0f;
             float lse = live ? lse_l : 0.0f;
             const float H = H_l, ge = (ENT && live && H_l != 0.0f) ? ge_l : 0.0f;     // (H == 0: a forced step, no entropy gradient)
+            // The logit stage is logit_bwd_tile (reeval_tile.hpp) with the ENT and DYN terms, written out here: called as a function
+            // the RTT = 7 HEADS instantiation ran 3 % longer (10.59 against 10.25 ms in the POMO-100 training step; the schedule
+            // around the barriers came out differently).  tests/test_gpu_eas_kernel.py holds this copy to the shared one bit for bit.
             float zr[4] = {0.f, 0.f, 0.f, 0.f}, dz[4] = {0.f, 0.f, 0.f, 0.f};
             if (wv < RTT) {
 #pragma unroll
@@ -1004,20 +934,12 @@ __global__ __launch_bounds__(512, 2) void k_reeval_bwd_logits(ReevalArgs a)
                     if (G == 0) atomicAdd(&SDR[cur * 16 + j], sdr);
                 }
             }
-            if (HEADS) stage_heads(pre, nxt);
+            if (HEADS) stage_heads(pre.fl, pre.dh, HTB + nxt * 16 * TS, jq, e4);
             else stage_rows<false>(pre, gc, CV, QTB + nxt * 16 * TS, nullptr, jq, e4);
             if (DYN) stage_rem<RTT>(REMB + nxt * 16 * 16 * RTT, jq, e4, pre.rem, pre.fl & 1);
             __syncthreads();            // du of this tile and q~ of the next one visible
             // wave wv: embedding columns 16 wv .. 16 wv + 15
-            f32x4 dh = z4();
-#pragma unroll
-            for (int t4 = 0; t4 < RTT; ++t4) {
-                const float4 ll = lpt[t4 * 64];
-                dh = mf(ll.x, DU[(16 * t4 + G) * DS + j], dh);
-                dh = mf(ll.y, DU[(16 * t4 + 4 + G) * DS + j], dh);
-                dh = mf(ll.z, DU[(16 * t4 + 8 + G) * DS + j], dh);
-                dh = mf(ll.w, DU[(16 * t4 + 12 + G) * DS + j], dh);
-            }
+            f32x4 dh = lpt_du<RTT>(lpt, DU, lane);
             if (DYN) {                  // dheads += (sum_n du rem) lw
                 const float sq = SDR[cur * 16 + j];
 #pragma unroll
@@ -1026,17 +948,12 @@ __global__ __launch_bounds__(512, 2) void k_reeval_bwd_logits(ReevalArgs a)
             if (qj >= 0)
                 *reinterpret_cast<float4*>(a.dheads + (int64_t)qj * RE + 16 * wv + 4 * G) = make_float4(dh[0], dh[1], dh[2], dh[3]);
             float hb[4];
-            const int c = 16 * wv + j;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) hb[t] = HT[(4 * t + G) * TS + (c & 3) * TG + (c >> 2)];
+            load_tile_col(HT, wv, lane, hb);
             if (DYN) {                  // dlw[c] += sum_q (sum_n du rem)[q] heads[q][c], this lane: the queries 4 t + G
 #pragma unroll
                 for (int t = 0; t < 4; ++t) dlw_acc = fmaf(SDR[cur * 16 + 4 * t + G], hb[t], dlw_acc);
             }
-#pragma unroll
-            for (int nt = 0; nt < RTT; ++nt)
-#pragma unroll
-                for (int t = 0; t < 4; ++t) dLp[nt] = mf(DU[(16 * nt + j) * DS + 4 * t + G], hb[t], dLp[nt]);
+            dlp_accumulate<RTT>(DU, hb, lane, dLp);
         } else {
             __syncthreads();            // q~ of tile 0 visible
         }
@@ -1048,14 +965,7 @@ __global__ __launch_bounds__(512, 2) void k_reeval_bwd_logits(ReevalArgs a)
         dlw_acc = group_sum(dlw_acc);
         if (G == 0) atomicAdd(a.ddyn + 2 * RE + 16 * wv + j, dlw_acc);
     }
-    // dLp: lane (column 16 wv + j, G), register r -> key 16 nt + 4 G + r
-#pragma unroll
-    for (int nt = 0; nt < RTT; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int n = 16 * nt + 4 * G + r;
-            if (n < a.M) atomicAdd(a.dLp + (b * a.M + n) * a.ldg + 16 * wv + j, dLp[nt][r]);
-        }
+    dlp_flush<RTT>(a, b, wv, lane, dLp);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1064,21 +974,29 @@ __global__ __launch_bounds__(512, 2) void k_reeval_bwd_logits(ReevalArgs a)
 // the log-probs through u = heads . Lp / sqrt(E) alone and nothing upstream of the glimpse output depends on it, so the other
 // products of k_reeval_bwd_logits fall away exactly: no Lp^T fragments in LDS, no dheads product, no dheads write, and no
 // glimpse / gather kernels behind it.  Same grid, tiles and software pipeline as k_reeval_bwd_logits (two barriers per tile,
-// three when the normaliser is derived from the rollout's log-probs); single-chunk graphs, no dynamic embedding.
-// LDS: HTB [2][16][TS] | DU [16 RTT][DS] | LSE [16] and, when the glimpse is recomputed, QTB [2][16][TS] | CV [2][128].
+// three when the normaliser is derived from the rollout's log-probs) around the same stages of reeval_tile.hpp -- logit_tile,
+// logit_bwd_tile, dlp_accumulate, dlp_flush -- on a smaller LDS map; single-chunk graphs, no dynamic embedding.
 // ---------------------------------------------------------------------------------------------------------------------
+template <int RTT>
+struct LpLds {          // float offsets, as LogitsLds
+    static constexpr int HTB = 0;                       // [2][16][TS]   heads tiles (A layout)
+    static constexpr int DU = HTB + 2 * 16 * TS;        // [16 RTT][DS]
+    static constexpr int LSE = DU + 16 * RTT * DS;      // [16]
+    static constexpr int QTB = LSE + 16;                // !HEADS: [2][16][TS]   q~ tiles
+    static constexpr int CV = QTB + 2 * 16 * TS;        // !HEADS: [2][128] state-column vectors
+    static constexpr int END = CV + 2 * RE;
+    static constexpr size_t bytes(bool heads) { return (size_t)(heads ? QTB : END) * sizeof(float); }
+};
+
 template <int RTT, bool HEADS>
 __global__ __launch_bounds__(512, 2) void k_reeval_bwd_lp(ReevalArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* HTB = lds;                               // [2][16][TS]   heads tiles (A layout)
-    float* DU = HTB + 2 * 16 * TS;                  // [16 RTT][DS]
-    float* LSE = DU + 16 * RTT * DS;                // [16]
-    float* QTB = LSE + 16;                          // !HEADS: [2][16][TS]   q~ tiles
-    float* CV = QTB + 2 * 16 * TS;                  // !HEADS: [2][128] state-column vectors
+    using L = LpLds<RTT>;
+    float *HTB = lds + L::HTB, *DU = lds + L::DU, *LSE = lds + L::LSE, *QTB = lds + L::QTB, *CV = lds + L::CV;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int j = lane & 15, G = lane >> 4;
+    const int j = lane & 15;
     const int jq = tid >> 5, e4 = tid & 31;
     const Blk blk = decode_block(a);
     const int64_t b = blk.b;
@@ -1102,18 +1020,6 @@ __global__ __launch_bounds__(512, 2) void k_reeval_bwd_lp(ReevalArgs a)
     const float inv_temp = 1.0f / a.temp;
 
     auto qi_of = [&](const QWalk& w) -> int { return w.sl < ns ? ((s0 + w.sl) * (int)a.B + (int)b) * T + w.t : -1; };
-    auto load_heads = [&](const QWalk& w, RowPre& p) {
-        const int qi = qi_of(w);
-        const int64_t r = (int64_t)(s0 + min(w.sl, ns - 1)) * a.B + b;
-        const int th = max(w.t - a.tstart, 0);
-        p.fl = (qi >= 0 ? 1 : 0) | (w.t >= a.tstart && th < a.heads_T ? 8 : 0);
-        p.dh = *reinterpret_cast<const float4*>(a.heads + (r * a.heads_T + min(th, a.heads_T - 1)) * RE + 4 * e4);
-    };
-    auto stage_heads = [&](const RowPre& p, int buf) {
-        const bool ok = (p.fl & 9) == 9;
-        float* dp = HTB + buf * 16 * TS + jq * TS + e4;
-        dp[0] = ok ? p.dh.x : 0.0f; dp[TG] = ok ? p.dh.y : 0.0f; dp[2 * TG] = ok ? p.dh.z : 0.0f; dp[3 * TG] = ok ? p.dh.w : 0.0f;
-    };
     // ---- prologue: tile 0 staged, indices of tile 1 in flight --------------------------------------------------------
     QWalk wr, wj;                       // the staging role (query jq) and the MFMA role (query j) of this thread
     wr.init(jq, T);
@@ -1122,8 +1028,8 @@ __global__ __launch_bounds__(512, 2) void k_reeval_bwd_lp(ReevalArgs a)
     {
         RowPre pre;
         if (HEADS) {
-            load_heads(wr, pre);
-            stage_heads(pre, 0);
+            load_heads(a, b, s0, ns, e4, wr, qr, pre.fl, pre.dh);
+            stage_heads(pre.fl, pre.dh, HTB, jq, e4);
         } else {
             load_idx(a, qr, ia, ib);
             load_rows<false>(a, b, e4, qr, wr.t, ia, ib, pre);
@@ -1146,7 +1052,7 @@ __global__ __launch_bounds__(512, 2) void k_reeval_bwd_lp(ReevalArgs a)
         if (tile >= 0) {
             RowPre pre;
             if (HEADS) {
-                load_heads(wr, pre);                                // heads rows of tile + 1
+                load_heads(a, b, s0, ns, e4, wr, qi_of(wr), pre.fl, pre.dh);       // heads rows of tile + 1
                 wr.next(T);
             } else {
                 load_rows<false>(a, b, e4, qr, wr.t, ia, ib, pre);  // rows of tile + 1 (indices fetched one iteration ago)
@@ -1167,47 +1073,15 @@ __global__ __launch_bounds__(512, 2) void k_reeval_bwd_lp(ReevalArgs a)
             if (wv < RTT) u = logit_tile(lpf, HT, lane);
             const int act = qj >= 0 ? act_l : -1;
             const float g = live ? g_l : 0.0f;
-            float lse = live ? lse_l : 0.0f;
-            float zr[4] = {0.f, 0.f, 0.f, 0.f}, dz[4] = {0.f, 0.f, 0.f, 0.f};
-            if (wv < RTT) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) zr[r] = process_logit(u[r], a.clip, inv_temp, dz[r]);
-            }
-            if (derive_lse) {           // the lane that owns the chosen node publishes z[action] - logp for its query
-                if (wv < RTT) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (16 * wv + 4 * r + G == act && g != 0.0f) LSE[j] = zr[r] - lse;
-                }
-                __syncthreads();
-                if (g != 0.0f) lse = LSE[j];
-            }
-            if (wv < RTT) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int n0 = 16 * wv + 4 * r;
-                    const uint32_t w = (n0 >> 5) == 0 ? mb.x : (n0 >> 5) == 1 ? mb.y : (n0 >> 5) == 2 ? mb.z : mb.w;
-                    const bool ok = (w >> ((n0 & 31) + G)) & 1u;
-                    float du = 0.0f;
-                    if (ok && g != 0.0f) {
-                        const float p = fexp(zr[r] - lse);
-                        du = g * ((n0 + G == act ? 1.0f : 0.0f) - p) * dz[r];
-                    }
-                    DU[(n0 + G) * DS + j] = du;
-                }
-            }
-            if (HEADS) stage_heads(pre, nxt);
+            const float lse = live ? lse_l : 0.0f;
+            // (a third barrier inside when the normaliser is derived)
+            logit_bwd_tile(u, wv < RTT, wv, lane, mb, act, g, lse, derive_lse, a.clip, inv_temp, LSE, DU);
+            if (HEADS) stage_heads(pre.fl, pre.dh, HTB + nxt * 16 * TS, jq, e4);
             else stage_rows<false>(pre, gc, CV, QTB + nxt * 16 * TS, nullptr, jq, e4);
             __syncthreads();            // du of this tile and the rows of the next one visible
-            // wave wv: embedding columns 16 wv .. 16 wv + 15 of every key tile
             float hb[4];
-            const int c = 16 * wv + j;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) hb[t] = HT[(4 * t + G) * TS + (c & 3) * TG + (c >> 2)];
-#pragma unroll
-            for (int nt = 0; nt < RTT; ++nt)
-#pragma unroll
-                for (int t = 0; t < 4; ++t) dLp[nt] = mf(DU[(16 * nt + j) * DS + 4 * t + G], hb[t], dLp[nt]);
+            load_tile_col(HT, wv, lane, hb);
+            dlp_accumulate<RTT>(DU, hb, lane, dLp);
         } else {
             __syncthreads();            // q~ (or heads) of tile 0 visible
         }
@@ -1215,15 +1089,7 @@ __global__ __launch_bounds__(512, 2) void k_reeval_bwd_lp(ReevalArgs a)
         if (!HEADS && tile + 1 < ntiles)
             glimpse_tile<RTT>(kf, vtf, QTB + nxt * 16 * TS, HTB + nxt * 16 * TS, wv, lane, mb, a.M);
     }
-    // dLp: lane (column 16 wv + j, G), register r -> key 16 nt + 4 G + r.  The caller's buffer is accumulated into and nchunk
-    // workgroups share an instance: float atomics, as k_reeval_bwd_logits
-#pragma unroll
-    for (int nt = 0; nt < RTT; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int n = 16 * nt + 4 * G + r;
-            if (n < a.M) atomicAdd(a.dLp + (b * a.M + n) * a.ldg + 16 * wv + j, dLp[nt][r]);
-        }
+    dlp_flush<RTT>(a, b, wv, lane, dLp);
 }
 
 // One tile (16 queries) of attention backward for head h, shared by the glimpse backward (queries = decode steps) and the
@@ -1375,18 +1241,27 @@ __device__ __forceinline__ void attention_bwd_tile(const float (&kf)[RTT][4], co
 // (Round-2 history: with the gathers, two barriers and an LDS-atomic scatter inside the loop this kernel took 37.3 ms at the
 //  POMO training size; 15.6 ms now, plus 2.0 ms of k_reeval_bwd_gather.)
 // ---------------------------------------------------------------------------------------------------------------------
+template <int RTT>
+struct GlimpseLds {     // float offsets, as LogitsLds
+    static constexpr int QTB = 0;                       // [2][16][TS]   q~ tiles (A layout)
+    static constexpr int DHB = QTB + 2 * 16 * TS;       // [2][16][TS]   dheads tiles
+    static constexpr int STG = DHB + 2 * 16 * TS;       // [8 waves][2 parities][a | ds][16 keys][16 queries]
+    static constexpr int KTL = STG + 8 * 4 * 256;       // [8 waves][RTT][64 lanes][4]  K^T fragments of the dq~ product
+    static constexpr int CV = KTL + 8 * RTT * 256;      // [2][128] state-column vectors
+    static constexpr int SRW = CV + 2 * RE;             // DYN: [8 waves][32]  per-query sums of the tile, wave-private
+    static constexpr int REMB = SRW + 8 * 32;           // DYN: [2][16][16 RTT]  staged remaining demands
+    static constexpr int DYNL = REMB + 2 * 16 * 16 * RTT;   // DYN: [2][E]  wk | wv
+    static constexpr int END = DYNL + 2 * RE;
+    static constexpr size_t bytes(bool dyn) { return (size_t)(dyn ? END : REMB) * sizeof(float); }      // (SRW is carved either way)
+};
+
 template <int RTT, bool DYN = false, bool MC = false>
 __global__ __launch_bounds__(512, 2) void k_reeval_bwd_glimpse(ReevalArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* QTB = lds;                               // [2][16][TS]   q~ tiles (A layout)
-    float* DHB = QTB + 2 * 16 * TS;                 // [2][16][TS]   dheads tiles
-    float* STG = DHB + 2 * 16 * TS;                 // [8 waves][2 parities][a | ds][16 keys][16 queries]
-    float* KTL = STG + 8 * 4 * 256;                 // [8 waves][RTT][64 lanes][4]  K^T fragments of the dq~ product
-    float* CV = KTL + 8 * RTT * 256;                // [2][128] state-column vectors
-    float* SRW = CV + 2 * RE;                       // DYN: [8 waves][32]  per-query sums of the tile, wave-private
-    float* REMB = SRW + 8 * 32;                     // DYN: [2][16][16 RTT]  staged remaining demands
-    float* DYNL = REMB + 2 * 16 * 16 * RTT;         // DYN: [2][E]  wk | wv
+    using L = GlimpseLds<RTT>;
+    float *QTB = lds + L::QTB, *DHB = lds + L::DHB, *STG = lds + L::STG, *KTL = lds + L::KTL, *CV = lds + L::CV;
+    float *SRW = lds + L::SRW, *REMB = lds + L::REMB, *DYNL = lds + L::DYNL;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 15, G = lane >> 4, pi = 4 * (j & 3) + (j >> 2);
@@ -1629,27 +1504,9 @@ __global__ __launch_bounds__(512) void k_reeval_bwd_gather(ReevalArgs a, int nch
     }
 }
 
-template <int RTT>
-static int launch_bwd_t(const ReevalArgs& a, hipStream_t st)
+// the gather kernel sorts its chunk's queries in LDS: at most GCAP of them per workgroup, so it may take more chunks than a.nchunk
+static int launch_gather(const ReevalArgs& a, hipStream_t st)
 {
-    const unsigned grid = (unsigned)(a.B * a.nchunk);
-    const bool dyn = a.dyn != nullptr;
-    const size_t ldl = (4 * 16 * (size_t)TS + 8 * RTT * 256 + 2 * RE + 16 * RTT * DS + 16 + 32 + (dyn ? 2 * 16 * 16 * RTT + 128 + 2 * RE : 0)) * sizeof(float);
-    auto kl = dyn ? k_reeval_bwd_logits<RTT, false, true> : a.heads ? k_reeval_bwd_logits<RTT, true> : k_reeval_bwd_logits<RTT, false>;
-    if (a.gent)         // the entropy term lives in its own instantiations: a NULL gent runs the kernels above, untouched
-        kl = dyn ? k_reeval_bwd_logits<RTT, false, true, true>
-                 : a.heads ? k_reeval_bwd_logits<RTT, true, false, true> : k_reeval_bwd_logits<RTT, false, false, true>;
-    if (ldl > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kl), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldl) != hipSuccess)
-        return EAMRL_E_LAUNCH;
-    hipLaunchKernelGGL(kl, dim3(grid), dim3(512), ldl, st, a);
-    const size_t lds = (4 * 16 * (size_t)TS + 8 * 4 * 256 + 8 * RTT * 256 + 2 * RE + 8 * 32 + (dyn ? 2 * 16 * 16 * RTT + 2 * RE : 0)) * sizeof(float);
-    auto k = dyn ? k_reeval_bwd_glimpse<RTT, true> : k_reeval_bwd_glimpse<RTT, false>;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return EAMRL_E_LAUNCH;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(512), lds, st, a);
-    // the gather kernel sorts its chunk's queries in LDS: at most GCAP of them per workgroup
     int ng = a.nchunk;
     while ((int64_t)((a.S + ng - 1) / ng) * a.T > GCAP && ng < a.S) ++ng;
     if ((int64_t)((a.S + ng - 1) / ng) * a.T > GCAP) return EAMRL_E_LAUNCH;
@@ -1659,6 +1516,43 @@ static int launch_bwd_t(const ReevalArgs& a, hipStream_t st)
         return EAMRL_E_LAUNCH;
     hipLaunchKernelGGL(k_reeval_bwd_gather, dim3((unsigned)(a.B * ng)), dim3(512), ldg, st, a, ng);
     return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
+}
+
+// The byte counts that the layouts give are those of the formulas the launchers spelled out before the layouts existed.
+template <int RTT>
+constexpr bool lds_bytes_unchanged()
+{
+    constexpr size_t F = sizeof(float);
+    return LogitsLds<RTT>::bytes(false) == (4 * 16 * TS + 8 * RTT * 256 + 2 * RE + 16 * RTT * DS + 16 + 32) * F &&
+           LogitsLds<RTT>::bytes(true) == (4 * 16 * TS + 8 * RTT * 256 + 2 * RE + 16 * RTT * DS + 16 + 32 + 2 * 16 * 16 * RTT + 128 + 2 * RE) * F &&
+           GlimpseLds<RTT>::bytes(false) == (4 * 16 * TS + 8 * 4 * 256 + 8 * RTT * 256 + 2 * RE + 8 * 32) * F &&
+           GlimpseLds<RTT>::bytes(true) == (4 * 16 * TS + 8 * 4 * 256 + 8 * RTT * 256 + 2 * RE + 8 * 32 + 2 * 16 * 16 * RTT + 2 * RE) * F &&
+           LpLds<RTT>::bytes(true) == (2 * 16 * TS + 16 * RTT * DS + 16) * F &&
+           LpLds<RTT>::bytes(false) == (2 * 16 * TS + 16 * RTT * DS + 16 + 2 * 16 * TS + 2 * RE) * F;
+}
+static_assert(lds_bytes_unchanged<2>() && lds_bytes_unchanged<4>() && lds_bytes_unchanged<7>(), "dynamic LDS byte counts");
+
+template <int RTT>
+static int launch_bwd_t(const ReevalArgs& a, hipStream_t st)
+{
+    const unsigned grid = (unsigned)(a.B * a.nchunk);
+    const bool dyn = a.dyn != nullptr;
+    const size_t ldl = LogitsLds<RTT>::bytes(dyn);
+    auto kl = dyn ? k_reeval_bwd_logits<RTT, false, true> : a.heads ? k_reeval_bwd_logits<RTT, true> : k_reeval_bwd_logits<RTT, false>;
+    if (a.gent)         // the entropy term lives in its own instantiations: a NULL gent runs the kernels above, untouched
+        kl = dyn ? k_reeval_bwd_logits<RTT, false, true, true>
+                 : a.heads ? k_reeval_bwd_logits<RTT, true, false, true> : k_reeval_bwd_logits<RTT, false, false, true>;
+    if (ldl > 64 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(kl), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldl) != hipSuccess)
+        return EAMRL_E_LAUNCH;
+    hipLaunchKernelGGL(kl, dim3(grid), dim3(512), ldl, st, a);
+    const size_t lds = GlimpseLds<RTT>::bytes(dyn);
+    auto k = dyn ? k_reeval_bwd_glimpse<RTT, true> : k_reeval_bwd_glimpse<RTT, false>;
+    if (lds > 64 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return EAMRL_E_LAUNCH;
+    hipLaunchKernelGGL(k, dim3(grid), dim3(512), lds, st, a);
+    return launch_gather(a, st);
 }
 
 // key chunks: the forward call has left heads, the glimpse statistics and lse in the scratch / the caller's buffers
@@ -1672,26 +1566,18 @@ static int launch_bwd_mc(const ReevalArgs& a0, hipStream_t st)
     ReevalArgs l = a;
     l.heads = heads; l.heads_T = a.T;
     const bool dyn = a.dyn != nullptr;
-    const size_t ldl = (4 * 16 * (size_t)TS + 8 * RTT * 256 + 2 * RE + 16 * RTT * DS + 16 + 32 + (dyn ? 2 * 16 * 16 * RTT + 128 + 2 * RE : 0)) * sizeof(float);
+    const size_t ldl = LogitsLds<RTT>::bytes(dyn);
     auto kl = dyn ? k_reeval_bwd_logits<RTT, true, true> : k_reeval_bwd_logits<RTT, true>;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kl), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldl) != hipSuccess)
         return EAMRL_E_LAUNCH;
     hipLaunchKernelGGL(kl, dim3(grid), dim3(512), ldl, st, l);
     hipLaunchKernelGGL(k_reeval_mc_sum_dheads, dim3((unsigned)((RT * 32 + 255) / 256)), dim3(256), 0, st, a, heads);
-    const size_t lds = (4 * 16 * (size_t)TS + 8 * 4 * 256 + 8 * RTT * 256 + 2 * RE + 8 * 32 + (dyn ? 2 * 16 * 16 * RTT + 2 * RE : 0)) * sizeof(float);
+    const size_t lds = GlimpseLds<RTT>::bytes(dyn);
     auto k = dyn ? k_reeval_bwd_glimpse<RTT, true, true> : k_reeval_bwd_glimpse<RTT, false, true>;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return EAMRL_E_LAUNCH;
     hipLaunchKernelGGL(k, dim3(grid), dim3(512), lds, st, a);
-    int ng = a.nchunk;
-    while ((int64_t)((a.S + ng - 1) / ng) * a.T > GCAP && ng < a.S) ++ng;
-    if ((int64_t)((a.S + ng - 1) / ng) * a.T > GCAP) return EAMRL_E_LAUNCH;
-    const size_t ldg = (2 * GBINS + (size_t)((a.S + ng - 1) / ng) * a.T) * sizeof(int);
-    if (ldg > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(k_reeval_bwd_gather),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldg) != hipSuccess)
-        return EAMRL_E_LAUNCH;
-    hipLaunchKernelGGL(k_reeval_bwd_gather, dim3((unsigned)(a.B * ng)), dim3(512), ldg, st, a, ng);
-    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
+    return launch_gather(a, st);
 }
 
 int launch_reeval_bwd(const ReevalArgs& a0, hipStream_t st)
@@ -1709,7 +1595,7 @@ template <int RTT>
 static int launch_bwd_lp_t(const ReevalArgs& a, hipStream_t st)
 {
     const bool heads = a.heads != nullptr;
-    const size_t lds = (2 * 16 * (size_t)TS + 16 * RTT * DS + 16 + (heads ? 0 : 2 * 16 * TS + 2 * RE)) * sizeof(float);
+    const size_t lds = LpLds<RTT>::bytes(heads);
     auto k = heads ? k_reeval_bwd_lp<RTT, true> : k_reeval_bwd_lp<RTT, false>;
     hipLaunchKernelGGL(k, dim3((unsigned)(a.B * a.nchunk)), dim3(512), lds, st, a);
     return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;

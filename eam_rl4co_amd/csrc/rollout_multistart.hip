@@ -23,12 +23,11 @@
 //
 // Reference loop replaced: rl4co/models/common/constructive/base.py:236-250 with the multistart layout of
 // rl4co/utils/decoding.py:284-344 and rl4co/models/zoo/am/decoder.py:183-198 (K/V/L shared by the S queries of an instance).
-#include "kernels.hpp"
+#include "mfma_tile.hpp"
 #include "env_rule.hpp"
 
 namespace eamrl {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 // a * b for operands below 2^32 (rows, steps per row: rollout_ms_mfma_supports): one v_mad_u64_u32 where the 64 x 64 product of two
 // int64 is three quarter-rate multiplies -- per-lane row offsets are computed once per tile in the finish phase
 __device__ __forceinline__ int64_t mul32w(int64_t a, int64_t b) { return (int64_t)((uint64_t)(uint32_t)a * (uint32_t)b); }
@@ -43,29 +42,19 @@ __device__ unsigned long long g_ms_stamps[24];
 namespace {
 
 constexpr int ME = 128, MH = 8;
-constexpr int TS = 140, TG = 34;      // A-layout tile buffers [16][TS]: element (j, c) at j * TS + (c & 3) * TG + (c >> 2)
 constexpr int SMAX = 128;             // starts per instance
 constexpr int PD = 256;               // PolyNet: poly_layer_dim
 constexpr int TS2 = 268, TG2 = 66;    // ... its hidden tile [16][TS2]: element (j, c) at j * TS2 + (c & 3) * TG2 + (c >> 2)
 
-__device__ __forceinline__ f32x4 mf(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x4 z4() { return (f32x4){0.f, 0.f, 0.f, 0.f}; }
-
 // combine over the four lane groups (lanes l, l^16, l^32, l^48): first the ^16 partner, then the ^32 one -- the order of the
-// lane tree's levels 4 and 8 for keys laid out 4 per lane
+// lane tree's levels 4 and 8 for keys laid out 4 per lane (group_sum of mfma_tile.hpp alike)
+// (its own copy: vmax_raw, because this kernel is bit-exact to the oracle; reeval.hip's takes fmaxf)
 __device__ __forceinline__ float group_max(float v)
 {
     auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
     v = vmax_raw(__uint_as_float(a[0]), __uint_as_float(a[1]));
     auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
     return vmax_raw(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float group_sum(float v)
-{
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
 }
 // Sum over the four lane groups of one chunk's partial sums in the canonical order: lane group G holds the nodes 4 t + G, i.e. the
 // chunk's position class (G - start) & 3, and Z_g = (P0 + P1) + (P2 + P3) over POSITION classes.  Even chunk start: the pairs are
@@ -118,26 +107,6 @@ __device__ __forceinline__ int half_min(int v)
     v = min(v, dpp_i<DPP_MIRROR>(v));
     auto r = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
     return min((int)r[0], (int)r[1]);
-}
-
-// PolyNet weight stream: a piece = PQ consecutive 16-byte A-fragment loads of one row tile (fragment order, eamrl_polynet)
-constexpr int PQ = 4;
-__device__ __forceinline__ void w_load(f32x4 (&dst)[PQ], const float* W, int piece, int lane)
-{
-    const f32x4* wp = reinterpret_cast<const f32x4*>(W) + piece * (PQ * 64) + lane;
-#pragma unroll
-    for (int i = 0; i < PQ; ++i) dst[i] = wp[64 * i];
-}
-// acc0 / acc1 += the piece's A fragments x 16 k-steps of a tile (hp: this lane's row of an A-layout tile, at the piece's first k-step)
-__device__ __forceinline__ void w_gemm(const f32x4 (&w)[PQ], const float* hp, f32x4& acc0, f32x4& acc1)
-{
-#pragma unroll
-    for (int i = 0; i < PQ; ++i) {
-        const float2 lo = *reinterpret_cast<const float2*>(hp + 4 * i), hi = *reinterpret_cast<const float2*>(hp + 4 * i + 2);
-        f32x4& acc = (i & 1) ? acc1 : acc0;
-        acc = mf(w[i][0], lo.x, acc); acc = mf(w[i][1], lo.y, acc);
-        acc = mf(w[i][2], hi.x, acc); acc = mf(w[i][3], hi.y, acc);
-    }
 }
 
 __device__ __forceinline__ PolyArgs poly_args() { return PolyArgs{}; }

@@ -27,13 +27,20 @@ def dev(x):
     return None if x is None else x.to(DEV).contiguous()
 
 
-def make_plan(name, cache_layout=False):
+def make_plan(name, cache_layout=False, S=None):
     """The plan of case `name` as tests/test_gpu_reeval.py builds it, with lse from a forward pass unless the case hands in the
-    rollout's log-probs.  cache_layout: the operands in a decoder cache's slot order (K | V | L | Pa | Pb | Lp), read in place."""
+    rollout's log-probs.  cache_layout: the operands in a decoder cache's slot order (K | V | L | Pa | Pb | Lp), read in place.
+    S: only the case's first S starts (rows are in "(s b)" order: its first S * B rows)."""
     from eam_rl4co_amd import ops
 
     c = rc.CASES[name]
     op, glogp, r64, _ = rc.reference(name)
+    logp64 = r64["logp"]
+    if S is not None:
+        R = S * c["B"]
+        op = {k: v[:, :R] if k == "sc" and v is not None else v[:R] if k in ("idxA", "idxB", "mask", "actions", "heads") and v is not None
+              else v for k, v in op.items()}
+        c, glogp, logp64 = dict(c, S=S), glogp[:R], logp64[:R]
     names = ["K", "V", "Lp", "Pa"] + (["Pb"] if c["pb"] else [])
     slots = None
     if cache_layout:
@@ -44,7 +51,7 @@ def make_plan(name, cache_layout=False):
         buf = dev(torch.cat([op[k] for k in names], dim=-1))
     pack = rr.pack_mask_bits_chunked if c["M"] > rr.KEY_CHUNK else rr.pack_mask_bits
     t0 = c["tstart"]
-    fed = r64["logp"].float() if c["rollout_logp"] else None
+    fed = logp64.float() if c["rollout_logp"] else None
     plan = ops.ReevalPlan(buf, c["pb"], dev(op["gctx"]), dev(op["Cvec"]), dev(op["idxA"]), dev(op["idxB"]), dev(op["sc"]),
                           dev(pack(op["mask"].numpy())), dev(op["actions"]), c["S"], t0, c["clip"], c["temp"],
                           rollout_logp=dev(fed), rollout_heads=dev(op["heads"][:, t0:]) if c["rollout_heads"] else None,
@@ -101,3 +108,19 @@ def test_backward_lp_refuses_key_chunks_and_the_dynamic_embedding(name):
         plan.backward_lp(g, out=out)
     torch.cuda.synchronize()
     assert (out == 0).all()          # nothing was launched
+
+
+@pytest.mark.parametrize("name", ["ops_pb", "ops_rollout_heads", "edge_M33", "edge_M65", "ops_rollout_logp_M65"])
+def test_backward_lp_is_the_full_backwards_dLp_bit_for_bit(name):
+    """k_reeval_bwd_lp and k_reeval_bwd_logits run the same stages (csrc/reeval_tile.hpp; the full backward writes the logit
+    stage out with its extra terms) over the same tiles, so with one start per instance -- nchunk = 1: one workgroup owns an
+    instance and every dLp address takes exactly one atomic add, no order to differ in -- the two kernels' dLp are the same bits
+    (M = 20, 33, 65: the 2, 4 and 7 key-tile instantiations; the glimpse recomputed, the rollout's heads handed in, the
+    normaliser recovered from the rollout's log-probs)."""
+    plan, g = make_plan(name, S=1)
+    assert plan.nchunk == 1
+    E = rr.E
+    full = plan.backward(g)[0][..., 2 * E:3 * E]           # (the operands lie K | V | Lp | Pa [| Pb])
+    lp = plan.backward_lp(g)
+    assert float(full.abs().max()) > 0
+    assert torch.equal(lp, full)
