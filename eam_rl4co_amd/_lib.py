@@ -13,6 +13,7 @@ ENV_TSP, ENV_CVRP, ENV_SDVRP, ENV_PCTSP, ENV_OP, ENV_CVRPTW, ENV_PDP = 0, 1, 2, 
 GREEDY, SAMPLE, EVALUATE = 0, 1, 2
 NORM_BATCH_EVAL, NORM_INSTANCE = 0, 1
 ST_NAN_LOGITS, ST_INFEASIBLE, ST_STEP_OVERRUN = 1, 2, 4
+LINEAR_NONE = 0      # EAMRL_LINEAR_NONE: eamrl_linear_variant's answer for rows == 0 (the other ids: include/eamrl.h)
 
 _vp, _i64, _i32, _f32 = C.c_void_p, C.c_int64, C.c_int, C.c_float
 
@@ -97,6 +98,7 @@ PROTOTYPES = {
     "eamrl_linear": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp],
     "eamrl_linear_bn": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp],
     "eamrl_matmul_right": [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _vp],
+    "eamrl_linear_variant": [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32],
     "eamrl_linear_wgrad_scratch": [_i64, _i32, _i32],
     "eamrl_linear_wgrad": [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp],
     "eamrl_augment_xy": [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _f32, _vp],

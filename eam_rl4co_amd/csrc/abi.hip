@@ -227,8 +227,25 @@ __attribute__((visibility("default"))) int eamrl_matmul_right(const float* x, in
 {
     REQUIRE(x && Wt && y, "eamrl_matmul_right");
     REQUIRE(rows >= 0 && in_dim > 0 && out_dim > 0 && ldx >= in_dim && ldy >= out_dim, "eamrl_matmul_right");
+    REQUIRE((rows + 127) / 128 <= 0x7fffffffLL, "eamrl_matmul_right");
     GemmArgs g{x, ldx, Wt, out_dim, 1, nullptr, nullptr, 0, y, ldy, rows, in_dim, out_dim, 0, nullptr, nullptr, nullptr, nullptr, 0.f};
     return launched(launch_linear(g, (hipStream_t)stream), "eamrl_matmul_right");
+}
+
+__attribute__((visibility("default"))) int eamrl_linear_variant(const float* x, int64_t ldx, const float* W, int64_t ldw, int wt,
+                                                               const float* bias, const float* res, int64_t ldres,
+                                                               const float* y, int64_t ldy, int64_t rows, int in_dim,
+                                                               int out_dim, int relu, int bn)
+{
+    // the requirements of eamrl_linear / eamrl_linear_bn (wt = 0) and of eamrl_matmul_right (wt = 1)
+    REQUIRE(x && W && y, "eamrl_linear_variant");
+    REQUIRE(rows >= 0 && in_dim > 0 && out_dim > 0, "eamrl_linear_variant");
+    REQUIRE(ldx >= in_dim && ldw >= (wt ? out_dim : in_dim) && ldy >= out_dim && (!res || ldres >= out_dim), "eamrl_linear_variant");
+    REQUIRE((rows + 127) / 128 <= 0x7fffffffLL, "eamrl_linear_variant");
+    // a fused batch-norm shows in the dispatch only as "bn_gamma is set": any non-null pointer stands for it here
+    const float* set = bn ? x : nullptr;
+    GemmArgs g{x, ldx, W, ldw, wt, bias, res, ldres, const_cast<float*>(y), ldy, rows, in_dim, out_dim, relu, set, set, set, set, 0.f};
+    return linear_variant(g);
 }
 
 __attribute__((visibility("default"))) int eamrl_mha_encoder_backward_supported(int N, int E, int H)

@@ -423,55 +423,72 @@ __global__ __launch_bounds__(256) void k_small_linear4(GemmArgs g)
     *reinterpret_cast<float4*>(g.y + r * g.ldy + j) = acc;
 }
 
+// The 32-bit per-thread offsets of gemm_offsets reach 127 * ld + 124 (row 127 of a 128-row tile plus a row segment; k row 31
+// plus column 124 of a transposed tile): a leading dimension beyond this takes the VALU kernel, whose addressing is 64-bit.
+constexpr int64_t GEMM_LD_MAX = (0x7fffffffLL - 124) / 127;
+
+// The dispatch, stated once: which instantiation launch_linear runs for g (EAMRL_LINEAR_*).  Pure host arithmetic on the
+// shape, the leading dimensions, the pointers' alignment and the debug keys; no pointer is dereferenced.
+int linear_variant(const GemmArgs& g)
+{
+    const bool force_valu = g_debug[0] != 0;
+    if (g.rows <= 0) return EAMRL_LINEAR_NONE;
+    if (g.in_dim >= 2 && g.in_dim <= 4 && !g.wt && !g.relu && !g.res && !g.bn_gamma && (g.out_dim & 3) == 0 && (g.ldy & 3) == 0 &&
+        ((uintptr_t)g.y & 15) == 0 && (!g.bias || ((uintptr_t)g.bias & 15) == 0) && !force_valu)
+        return g.in_dim == 2 ? EAMRL_LINEAR_SMALL4_K2 : g.in_dim == 3 ? EAMRL_LINEAR_SMALL4_K3 : EAMRL_LINEAR_SMALL4_K4;
+    if (g.in_dim <= 4) return EAMRL_LINEAR_SMALL;
+    if (!force_valu && g.rows * g.out_dim <= 16384) return EAMRL_LINEAR_THIN;
+    if (force_valu || (g.in_dim % GK) || (g.ldx & 3) || ((uintptr_t)g.x & 15) || (g.ldw & 3) || ((uintptr_t)g.W & 15) ||
+        (g.wt && (g.out_dim & 3)) || g.ldx > GEMM_LD_MAX || g.ldw > GEMM_LD_MAX)
+        return EAMRL_LINEAR_VALU;
+    // compile-time epilogue where the output is whole 128-column tiles of 16-byte aligned rows
+    const bool aligned = (g.out_dim % GT == 0) && ((g.ldy & 3) == 0) && (((uintptr_t)g.y & 15) == 0) &&
+                         (!g.res || (((g.ldres & 3) == 0) && (((uintptr_t)g.res & 15) == 0)));
+    int epi = -1;
+    if (aligned && !g_debug[10]) {
+        if (g.res && g.bn_gamma && !g.relu) epi = 3;
+        else if (g.res && !g.bn_gamma && !g.relu) epi = 2;
+        else if (!g.res && !g.bn_gamma) epi = g.relu ? 1 : 0;
+    }
+    if (g_debug[4]) return g.wt ? EAMRL_LINEAR_MFMA128_WT_RT : EAMRL_LINEAR_MFMA128_RT;
+    if (g.wt) return epi == 0 ? EAMRL_LINEAR_MFMA64_WT_EPI0 : EAMRL_LINEAR_MFMA64_WT_RT;
+    switch (epi) {
+    case 0: return EAMRL_LINEAR_MFMA64_EPI0;
+    case 1: return EAMRL_LINEAR_MFMA64_EPI1;
+    case 2: return EAMRL_LINEAR_MFMA64_EPI2;
+    case 3: return EAMRL_LINEAR_MFMA64_EPI3;
+    default: return EAMRL_LINEAR_MFMA64_RT;
+    }
+}
+
 int launch_linear(const GemmArgs& g0, hipStream_t st)
 {
     GemmArgs g = g0;
-    const bool force_valu = g_debug[0] != 0;
-    if (g.rows <= 0) return 0;
-    if (g.in_dim >= 2 && g.in_dim <= 4 && !g.wt && !g.relu && !g.res && !g.bn_gamma && (g.out_dim & 3) == 0 && (g.ldy & 3) == 0 &&
-        ((uintptr_t)g.y & 15) == 0 && (!g.bias || ((uintptr_t)g.bias & 15) == 0) && !force_valu) {
-        const int64_t n = g.rows * (g.out_dim >> 2);
-        const dim3 grid((unsigned)((n + 255) / 256));
-        if (g.in_dim == 2) hipLaunchKernelGGL(k_small_linear4<2>, grid, dim3(256), 0, st, g);
-        else if (g.in_dim == 3) hipLaunchKernelGGL(k_small_linear4<3>, grid, dim3(256), 0, st, g);
-        else hipLaunchKernelGGL(k_small_linear4<4>, grid, dim3(256), 0, st, g);
-    } else if (g.in_dim <= 4) {
-        const int64_t n = g.rows * g.out_dim;
-        hipLaunchKernelGGL(k_small_linear, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g);
-    } else if (!force_valu && g.rows * g.out_dim <= 16384) {
-        const int64_t n = g.rows * g.out_dim;
-        hipLaunchKernelGGL(k_thin_linear, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g);
-    } else if (force_valu || (g.in_dim % GK) || (g.ldx & 3) || ((uintptr_t)g.x & 15) || (g.ldw & 3) ||
-               ((uintptr_t)g.W & 15) || (g.wt && (g.out_dim & 3))) {
-        dim3 grid((unsigned)((g.rows + 63) / 64), (unsigned)((g.out_dim + 63) / 64));
-        hipLaunchKernelGGL(k_linear_valu, grid, dim3(256), 0, st, g);
-    } else {
-        const int bm = g_debug[4] ? 128 : 64;
-        dim3 grid((unsigned)((g.rows + bm - 1) / bm), (unsigned)((g.out_dim + GT - 1) / GT));
-        // compile-time epilogue where the output is whole 128-column tiles of 16-byte aligned rows
-        const bool aligned = (g.out_dim % GT == 0) && ((g.ldy & 3) == 0) && (((uintptr_t)g.y & 15) == 0) &&
-                             (!g.res || (((g.ldres & 3) == 0) && (((uintptr_t)g.res & 15) == 0)));
-        int epi = -1;
-        if (aligned && !g_debug[10]) {
-            if (g.res && g.bn_gamma && !g.relu) epi = 3;
-            else if (g.res && !g.bn_gamma && !g.relu) epi = 2;
-            else if (!g.res && !g.bn_gamma) epi = g.relu ? 1 : 0;
-        }
-        if (bm == 64 && !g.wt) {
-            switch (epi) {
-            case 0: hipLaunchKernelGGL((k_linear_mfma<false, 64, 0>), grid, dim3(256), 0, st, g); break;
-            case 1: hipLaunchKernelGGL((k_linear_mfma<false, 64, 1>), grid, dim3(256), 0, st, g); break;
-            case 2: hipLaunchKernelGGL((k_linear_mfma<false, 64, 2>), grid, dim3(256), 0, st, g); break;
-            case 3: hipLaunchKernelGGL((k_linear_mfma<false, 64, 3>), grid, dim3(256), 0, st, g); break;
-            default: hipLaunchKernelGGL((k_linear_mfma<false, 64, -1>), grid, dim3(256), 0, st, g); break;
-            }
-        } else if (bm == 64) {
-            if (epi == 0) hipLaunchKernelGGL((k_linear_mfma<true, 64, 0>), grid, dim3(256), 0, st, g);
-            else hipLaunchKernelGGL((k_linear_mfma<true, 64, -1>), grid, dim3(256), 0, st, g);
-        } else {
-            if (g.wt) hipLaunchKernelGGL((k_linear_mfma<true, 128, -1>), grid, dim3(256), 0, st, g);
-            else hipLaunchKernelGGL((k_linear_mfma<false, 128, -1>), grid, dim3(256), 0, st, g);
-        }
+    const int variant = linear_variant(g);
+    if (variant == EAMRL_LINEAR_NONE) return 0;
+    const dim3 block(256);
+    const dim3 per4((unsigned)((g.rows * (g.out_dim >> 2) + 255) / 256));      // one thread per four outputs
+    const dim3 per1((unsigned)((g.rows * g.out_dim + 255) / 256));             // one thread per output
+    const dim3 valu((unsigned)((g.rows + 63) / 64), (unsigned)((g.out_dim + 63) / 64));
+    const dim3 mfma64((unsigned)((g.rows + 63) / 64), (unsigned)((g.out_dim + GT - 1) / GT));
+    const dim3 mfma128((unsigned)((g.rows + 127) / 128), (unsigned)((g.out_dim + GT - 1) / GT));
+    switch (variant) {
+    case EAMRL_LINEAR_SMALL4_K2: hipLaunchKernelGGL(k_small_linear4<2>, per4, block, 0, st, g); break;
+    case EAMRL_LINEAR_SMALL4_K3: hipLaunchKernelGGL(k_small_linear4<3>, per4, block, 0, st, g); break;
+    case EAMRL_LINEAR_SMALL4_K4: hipLaunchKernelGGL(k_small_linear4<4>, per4, block, 0, st, g); break;
+    case EAMRL_LINEAR_SMALL: hipLaunchKernelGGL(k_small_linear, per1, block, 0, st, g); break;
+    case EAMRL_LINEAR_THIN: hipLaunchKernelGGL(k_thin_linear, per1, block, 0, st, g); break;
+    case EAMRL_LINEAR_VALU: hipLaunchKernelGGL(k_linear_valu, valu, block, 0, st, g); break;
+    case EAMRL_LINEAR_MFMA64_EPI0: hipLaunchKernelGGL((k_linear_mfma<false, 64, 0>), mfma64, block, 0, st, g); break;
+    case EAMRL_LINEAR_MFMA64_EPI1: hipLaunchKernelGGL((k_linear_mfma<false, 64, 1>), mfma64, block, 0, st, g); break;
+    case EAMRL_LINEAR_MFMA64_EPI2: hipLaunchKernelGGL((k_linear_mfma<false, 64, 2>), mfma64, block, 0, st, g); break;
+    case EAMRL_LINEAR_MFMA64_EPI3: hipLaunchKernelGGL((k_linear_mfma<false, 64, 3>), mfma64, block, 0, st, g); break;
+    case EAMRL_LINEAR_MFMA64_RT: hipLaunchKernelGGL((k_linear_mfma<false, 64, -1>), mfma64, block, 0, st, g); break;
+    case EAMRL_LINEAR_MFMA64_WT_EPI0: hipLaunchKernelGGL((k_linear_mfma<true, 64, 0>), mfma64, block, 0, st, g); break;
+    case EAMRL_LINEAR_MFMA64_WT_RT: hipLaunchKernelGGL((k_linear_mfma<true, 64, -1>), mfma64, block, 0, st, g); break;
+    case EAMRL_LINEAR_MFMA128_RT: hipLaunchKernelGGL((k_linear_mfma<false, 128, -1>), mfma128, block, 0, st, g); break;
+    case EAMRL_LINEAR_MFMA128_WT_RT: hipLaunchKernelGGL((k_linear_mfma<true, 128, -1>), mfma128, block, 0, st, g); break;
+    default: return EAMRL_E_ARG;
     }
     return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
 }

@@ -16,6 +16,7 @@ struct GemmArgs {
 
 extern int g_debug[16];   // eamrl_debug_set knobs
 
+int linear_variant(const GemmArgs& g);   // EAMRL_LINEAR_*: the instantiation launch_linear runs (host arithmetic only)
 int launch_linear(const GemmArgs& g, hipStream_t st);
 int launch_mha_encoder(const float* qkv, float* out, int64_t B, int N, int E, int H, hipStream_t st);
 int launch_ea_cvrp(const float* locs, const float* demand, const float* vcap, int64_t* pop, float* fitness, int64_t B, int S,

@@ -53,10 +53,9 @@ def _bytes(t):
 # ------------------------------------------------------------------------------------------------------
 # encoder / cache
 # ------------------------------------------------------------------------------------------------------
-def linear(x, W, bias=None, relu=False, residual=None, out=None, w_cols=None, bn=None):
-    """y = [residual +] act(x @ W[:, w_cols].T + bias), optionally followed by BatchNorm1d(eval) in the same launch
-    (bn = (gamma, beta, running_mean, running_var, eps)).  x [..., in] (last dim contiguous, rows strided ok)."""
-    lib = _lib.load()
+def _linear_views(x, W, residual, out, w_cols):
+    """The 2-D operand views eamrl_linear is handed: (x2, Wv, res2, out, o2).  x is copied if its inner stride is not 1; W, the
+    residual and `out` must have unit inner stride; `out` is allocated when None."""
     _need_gpu(x, "x")
     in_dim = x.shape[-1] if w_cols is None else w_cols[1] - w_cols[0]
     x2 = x.reshape(-1, x.shape[-1])
@@ -79,6 +78,16 @@ def linear(x, W, bias=None, relu=False, residual=None, out=None, w_cols=None, bn
         res2 = residual.reshape(-1, residual.shape[-1])
         if res2.stride(-1) != 1 or res2.shape != (rows, out_dim) or res2.dtype != torch.float32:
             raise ValueError("linear: bad residual")
+    return x2, Wv, res2, out, o2
+
+
+def linear(x, W, bias=None, relu=False, residual=None, out=None, w_cols=None, bn=None):
+    """y = [residual +] act(x @ W[:, w_cols].T + bias), optionally followed by BatchNorm1d(eval) in the same launch
+    (bn = (gamma, beta, running_mean, running_var, eps)).  x [..., in] (last dim contiguous, rows strided ok)."""
+    lib = _lib.load()
+    x2, Wv, res2, out, o2 = _linear_views(x, W, residual, out, w_cols)
+    rows, in_dim = x2.shape
+    out_dim = Wv.shape[0]
     if bias is not None:
         _chk(bias, "bias", torch.float32, (out_dim,))
     if bn is not None:
@@ -87,6 +96,9 @@ def linear(x, W, bias=None, relu=False, residual=None, out=None, w_cols=None, bn
         gamma, beta, mean, var, eps = bn
         for nm, t in (("gamma", gamma), ("beta", beta), ("running_mean", mean), ("running_var", var)):
             _chk(t, nm, torch.float32, (out_dim,))
+    if rows == 0:       # an empty batch: nothing to launch (and torch hands out a null data_ptr for empty tensors)
+        return out
+    if bn is not None:
         _lib.check(lib.eamrl_linear_bn(_ptr(x2), x2.stride(0), _ptr(Wv), Wv.stride(0), _ptr(bias), _ptr(res2),
                                        res2.stride(0) if res2 is not None else 0, _ptr(o2), o2.stride(0), rows, in_dim,
                                        out_dim, _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(var), float(eps), _stream(x)),
@@ -98,9 +110,8 @@ def linear(x, W, bias=None, relu=False, residual=None, out=None, w_cols=None, bn
     return out
 
 
-def matmul_right(x, Wt, out=None):
-    """y = x @ Wt   (Wt [in][out], contiguous)."""
-    lib = _lib.load()
+def _matmul_right_views(x, Wt, out):
+    """(x2, out, o2) of eamrl_matmul_right; `out` is allocated when None."""
     _chk(Wt, "Wt", torch.float32)
     x2 = x.reshape(-1, x.shape[-1])
     if x2.stride(-1) != 1 or x2.dtype != torch.float32:
@@ -115,9 +126,46 @@ def matmul_right(x, Wt, out=None):
     o2 = out.reshape(-1, out.shape[-1]) if out.dim() != 2 else out
     if o2.stride(-1) != 1 or o2.shape != (rows, out_dim):
         raise ValueError("matmul_right: bad output buffer")
-    _lib.check(lib.eamrl_matmul_right(_ptr(x2), x2.stride(0), _ptr(Wt), _ptr(o2), o2.stride(0), rows, in_dim, out_dim,
+    return x2, out, o2
+
+
+def matmul_right(x, Wt, out=None):
+    """y = x @ Wt   (Wt [in][out], contiguous)."""
+    lib = _lib.load()
+    x2, out, o2 = _matmul_right_views(x, Wt, out)
+    rows, in_dim = x2.shape
+    if rows == 0:       # an empty batch: nothing to launch (and torch hands out a null data_ptr for empty tensors)
+        return out
+    _lib.check(lib.eamrl_matmul_right(_ptr(x2), x2.stride(0), _ptr(Wt), _ptr(o2), o2.stride(0), rows, in_dim, Wt.shape[1],
                                       _stream(x)), "eamrl_matmul_right")
     return out
+
+
+def linear_variant(x, W, bias=None, relu=False, residual=None, out=None, w_cols=None, bn=None, transposed=False):
+    """The EAMRL_LINEAR_* id of the kernel that linear(x, W, bias, relu, residual, out, w_cols, bn) -- or, with transposed=True,
+    matmul_right(x, W, out) -- launches for these very tensors under the current debug keys (eamrl_linear_variant).  Nothing is
+    launched; an `out` left to the call stands for the fresh, aligned tensor it would allocate."""
+    lib = _lib.load()
+    if transposed:
+        if bias is not None or relu or residual is not None or w_cols is not None or bn is not None:
+            raise ValueError("linear_variant: matmul_right takes x, Wt and out only")
+        x2, _, o2 = _matmul_right_views(x, W, out)
+        Wv, res2, ldw = W, None, W.shape[1]
+    else:
+        x2, Wv, res2, _, o2 = _linear_views(x, W, residual, out, w_cols)
+        ldw = Wv.stride(0)
+        if bn is not None and relu:
+            raise ValueError("linear: relu and fused batch-norm are not combined")
+    rows, in_dim = x2.shape
+    out_dim = W.shape[1] if transposed else Wv.shape[0]
+    if rows == 0:       # what linear / matmul_right do with an empty batch
+        return _lib.LINEAR_NONE
+    rc = lib.eamrl_linear_variant(_ptr(x2), x2.stride(0), _ptr(Wv), ldw, int(transposed), _ptr(bias), _ptr(res2),
+                                  res2.stride(0) if res2 is not None else 0, _ptr(o2), o2.stride(0), rows, in_dim, out_dim,
+                                  int(relu), int(bn is not None))
+    if rc < 0:
+        _lib.check(rc, "eamrl_linear_variant")
+    return rc
 
 
 def linear_wgrad_supported(out_dim: int, in_dim: int) -> bool:

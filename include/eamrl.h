@@ -172,6 +172,31 @@ int eamrl_linear_bn(const float* x, int64_t ldx, const float* W, int64_t ldw, co
 int eamrl_matmul_right(const float* x, int64_t ldx, const float* Wt, float* y, int64_t ldy, int64_t rows,
                        int in_dim, int out_dim, void* stream);
 
+/* Which kernel instantiation eamrl_linear / eamrl_linear_bn (wt = 0) or eamrl_matmul_right (wt = 1: W is Wt [in][out], ldw = out_dim)
+ * runs for these arguments under the current debug keys: one of EAMRL_LINEAR_*, or EAMRL_E_ARG where the entry points reject
+ * the call.  Pure host arithmetic: the choice depends on the shape, the leading dimensions, the 16-byte alignment of x, W, bias,
+ * res and y, on relu, on whether a residual is given and on bn (1 = fused batch-norm); no pointer is dereferenced and nothing
+ * is enqueued.  Results never depend on the variant -- this is what the tests ask to know which kernel they pinned. */
+#define EAMRL_LINEAR_NONE 0            /* rows == 0: nothing is launched */
+#define EAMRL_LINEAR_SMALL4_K2 1       /* k_small_linear4<in_dim>: in_dim 2 .. 4, bias only, four outputs per 16-byte store */
+#define EAMRL_LINEAR_SMALL4_K3 2
+#define EAMRL_LINEAR_SMALL4_K4 3
+#define EAMRL_LINEAR_SMALL 4           /* k_small_linear: every other call with in_dim <= 4 */
+#define EAMRL_LINEAR_THIN 5            /* k_thin_linear: rows * out_dim <= 16384 */
+#define EAMRL_LINEAR_VALU 6            /* k_linear_valu: debug key 0, in_dim % 32, unaligned x / W rows, a leading dimension of
+                                          x or W whose 128-row tile does not fit 32-bit offsets, Wt with out_dim % 4 */
+#define EAMRL_LINEAR_MFMA64_EPI0 7     /* k_linear_mfma<false, 64, EPI>: compile-time epilogue 0 plain, 1 ReLU, 2 residual, */
+#define EAMRL_LINEAR_MFMA64_EPI1 8     /* 3 residual + batch-norm (whole 128-column tiles, 16-byte aligned y / res rows) */
+#define EAMRL_LINEAR_MFMA64_EPI2 9
+#define EAMRL_LINEAR_MFMA64_EPI3 10
+#define EAMRL_LINEAR_MFMA64_RT 11      /* k_linear_mfma<false, 64, -1>: epilogue configured at run time */
+#define EAMRL_LINEAR_MFMA64_WT_EPI0 12 /* k_linear_mfma<true, 64, 0> */
+#define EAMRL_LINEAR_MFMA64_WT_RT 13   /* k_linear_mfma<true, 64, -1> */
+#define EAMRL_LINEAR_MFMA128_RT 14     /* k_linear_mfma<false, 128, -1> (debug key 4) */
+#define EAMRL_LINEAR_MFMA128_WT_RT 15  /* k_linear_mfma<true, 128, -1> (debug key 4) */
+int eamrl_linear_variant(const float* x, int64_t ldx, const float* W, int64_t ldw, int wt, const float* bias, const float* res,
+                         int64_t ldres, const float* y, int64_t ldy, int64_t rows, int in_dim, int out_dim, int relu, int bn);
+
 /* Weight and bias gradient of torch.nn.Linear for the training graph (the encoder's and the cache projections' Linears as
  * differentiated by loss.backward() of the REINFORCE / POMO / EAM trainers  [models/rl/reinforce/reinforce.py:62-64,103-106;
  * zoo/pomo/model.py:103-112; zoo/earl/model.py:179-195]):  dW[o][i] = sum_r dy[r][o] x[r][i]  ([out_dim][in_dim], written,
