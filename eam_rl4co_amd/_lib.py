@@ -168,12 +168,18 @@ PROTOTYPES = {
     "eamrl_ea_prize_run": [_i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, C.c_double, C.c_double, C.c_double, _i32,
                            _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "eamrl_ea_tsp_run": [_vp, _vp, _vp, _i64, _i32, _i32, _i32, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp],
+    "eamrl_ea_kernel": [_i32, _i32, _i32, _i32],
+    "eamrl_ea_large_scratch_bytes": [_i32, _i64, _i32, _i32, C.c_double],
+    "eamrl_ea_tsp_run_large": [_vp, _vp, _vp, _i64, _i32, _i32, _i32, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp,
+                               _vp, C.c_size_t, _vp],
+    "eamrl_ea_cvrp_run_large": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, C.c_double, C.c_double, C.c_double, _i32,
+                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp],
     "eamrl_math_probe": [_i32, _vp, _vp, _i64, _vp],
     "eamrl_wave_probe": [_i32, _vp, _vp, _vp, _vp, _i64, _vp],
 }
 _RESTYPES = {"eamrl_last_error": C.c_char_p, "eamrl_linear_wgrad_scratch": C.c_int64,
              "eamrl_small_linear_wgrad_scratch": C.c_int64, "eamrl_batchnorm_backward_scratch": C.c_int64,
-             "eamrl_reeval_scratch_floats": C.c_int64}
+             "eamrl_reeval_scratch_floats": C.c_int64, "eamrl_ea_large_scratch_bytes": C.c_size_t}
 
 _lib = None
 

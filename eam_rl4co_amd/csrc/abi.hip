@@ -1065,6 +1065,89 @@ __attribute__((visibility("default"))) int eamrl_beam_topk(const float* logprobs
                     "eamrl_beam_topk");
 }
 
+// The shapes the LDS kernel k_ea serves (three int16 populations of one instance in the LDS of one workgroup) and the ones
+// the device-memory path serves -- the one place that states either; the entry points and eamrl_ea_kernel ask here.
+static bool ea_tsp_lds_shape(int S, int N) { return S >= 1 && S <= 128 && N >= 2 && N <= 128; }
+static bool ea_cvrp_lds_dims(int S, int N, int L) { return S >= 1 && S <= 128 && N >= 1 && N <= 127 && L >= 2 && L <= 256; }
+static bool ea_cvrp_lds_fits(int S, int L) { return (int64_t)S * L <= 24000; }
+static bool ea_prize_lds_shape(int S, int N, int L) { return S >= 1 && S <= 128 && N >= 1 && N <= 127 && L >= 2 && L <= 128; }
+static bool ea_tsp_large_shape(int S, int N) { return S >= 1 && S <= 1024 && N >= 2 && N <= 1024; }
+static bool ea_cvrp_large_shape(int S, int N, int L) { return S >= 1 && S <= 1024 && N >= 1 && N <= 1023 && L >= 2 && L <= 2 * (N + 1) + 1; }
+
+__attribute__((visibility("default"))) int eamrl_ea_kernel(int env, int S, int N, int L)
+{
+    switch (env) {
+    case EAMRL_ENV_TSP:
+        if (ea_tsp_lds_shape(S, N)) return EAMRL_EA_KERNEL_LDS;
+        REQUIRE(ea_tsp_large_shape(S, N), "eamrl_ea_kernel (TSP: 1 <= S <= 1024, 2 <= N <= 1024)");
+        return EAMRL_EA_KERNEL_LARGE;
+    case EAMRL_ENV_CVRP:
+        if (ea_cvrp_lds_dims(S, N, L) && ea_cvrp_lds_fits(S, L)) return EAMRL_EA_KERNEL_LDS;
+        REQUIRE(ea_cvrp_large_shape(S, N, L), "eamrl_ea_kernel (CVRP: 1 <= S <= 1024, 1 <= N <= 1023 customers, 2 <= L <= 2 N + 3)");
+        return EAMRL_EA_KERNEL_LARGE;
+    case EAMRL_ENV_PCTSP:
+    case EAMRL_ENV_OP:
+        REQUIRE(ea_prize_lds_shape(S, N, L), "eamrl_ea_kernel (PCTSP, OP: S <= 128, N <= 127 customers, 2 <= L <= 128)");
+        return EAMRL_EA_KERNEL_LDS;
+    }
+    return fail(EAMRL_E_ARG, "eamrl_ea_kernel: env must be TSP, CVRP, PCTSP or OP");
+}
+
+__attribute__((visibility("default"))) size_t eamrl_ea_large_scratch_bytes(int env, int64_t B, int S, int L, double selection_rate)
+{
+    const bool ok = (env == EAMRL_ENV_TSP || env == EAMRL_ENV_CVRP) && B >= 0 && B <= 0x7fffffffLL && S >= 1 && S <= 1024 &&
+                    L >= 2 && L <= 2 * 1024 + 1 && selection_rate >= 0.0;
+    if (!ok) { fail(EAMRL_E_ARG, "eamrl_ea_large_scratch_bytes: env TSP or CVRP, B >= 0, 1 <= S <= 1024, 2 <= L <= 2049"); return 0; }
+    return ea_large_scratch_bytes(B > 0 ? B : 1, S, L);
+}
+
+__attribute__((visibility("default"))) int eamrl_ea_tsp_run_large(const float* locs, int64_t* pop, float* fitness, int64_t B,
+                                                                 int S, int N, int num_generations, double mutation_rate,
+                                                                 double crossover_rate, double selection_rate,
+                                                                 const double* cross_rand, const int32_t* cross_idx,
+                                                                 const double* mut_rand, const int32_t* mut_idx,
+                                                                 void* scratch, size_t scratch_bytes, void* stream)
+{
+    REQUIRE(locs && pop && fitness, "eamrl_ea_tsp_run_large");
+    REQUIRE(B >= 0 && B <= 0x7fffffffLL && ea_tsp_large_shape(S, N) && num_generations >= 0,
+            "eamrl_ea_tsp_run_large (population and tour length are limited to 1024)");
+    REQUIRE(mutation_rate == mutation_rate && crossover_rate == crossover_rate && selection_rate >= 0.0,
+            "eamrl_ea_tsp_run_large");
+    if (num_generations > 0 && ea_num_elites(selection_rate, S) / 2 > 0)
+        REQUIRE(cross_rand && cross_idx && mut_rand && mut_idx, "eamrl_ea_tsp_run_large (draws)");
+    REQUIRE(scratch && ((uintptr_t)scratch & 15) == 0 && scratch_bytes >= ea_large_scratch_bytes(B > 0 ? B : 1, S, N),
+            "eamrl_ea_tsp_run_large (scratch: eamrl_ea_large_scratch_bytes, 16-byte aligned)");
+    if (B == 0) return 0;
+    return launched(launch_ea_tsp_large(locs, pop, fitness, B, S, N, num_generations, mutation_rate, crossover_rate,
+                                        selection_rate, cross_rand, cross_idx, mut_rand, mut_idx, scratch, scratch_bytes,
+                                        (hipStream_t)stream), "eamrl_ea_tsp_run_large");
+}
+
+__attribute__((visibility("default"))) int eamrl_ea_cvrp_run_large(const float* locs, const float* demand, const float* vcap,
+                                                                  int64_t* pop, float* fitness, int64_t B, int S, int N, int L,
+                                                                  int num_generations, double mutation_rate,
+                                                                  double crossover_rate, double selection_rate, int top_k,
+                                                                  const double* init_mut_rand, const double* init_mut_u,
+                                                                  const double* cross_rand, const double* cross_u,
+                                                                  const double* mut_rand, const double* mut_u, void* scratch,
+                                                                  size_t scratch_bytes, void* stream)
+{
+    REQUIRE(locs && demand && vcap && pop && fitness && init_mut_rand && init_mut_u, "eamrl_ea_cvrp_run_large");
+    REQUIRE(B >= 0 && B <= 0x7fffffffLL && ea_cvrp_large_shape(S, N, L) && num_generations >= 0,
+            "eamrl_ea_cvrp_run_large (S <= 1024, N <= 1023 customers, 2 <= L <= 2 N + 3)");
+    REQUIRE(mutation_rate == mutation_rate && crossover_rate == crossover_rate && selection_rate >= 0.0,
+            "eamrl_ea_cvrp_run_large");
+    if (num_generations > 0 && ea_num_elites(selection_rate, S) / 2 > 0)
+        REQUIRE(cross_rand && cross_u && mut_rand && mut_u, "eamrl_ea_cvrp_run_large (draws)");
+    REQUIRE(scratch && ((uintptr_t)scratch & 15) == 0 && scratch_bytes >= ea_large_scratch_bytes(B > 0 ? B : 1, S, L),
+            "eamrl_ea_cvrp_run_large (scratch: eamrl_ea_large_scratch_bytes, 16-byte aligned)");
+    if (B == 0) return 0;
+    return launched(launch_ea_cvrp_large(locs, demand, vcap, pop, fitness, B, S, N, L, num_generations, mutation_rate,
+                                         crossover_rate, selection_rate, top_k, init_mut_rand, init_mut_u, cross_rand, cross_u,
+                                         mut_rand, mut_u, scratch, scratch_bytes, (hipStream_t)stream),
+                    "eamrl_ea_cvrp_run_large");
+}
+
 __attribute__((visibility("default"))) int eamrl_ea_tsp_run(const float* locs, int64_t* pop, float* fitness, int64_t B,
                                                            int S, int N, int num_generations, double mutation_rate,
                                                            double crossover_rate, double selection_rate,
@@ -1072,7 +1155,7 @@ __attribute__((visibility("default"))) int eamrl_ea_tsp_run(const float* locs, i
                                                            const double* mut_rand, const int32_t* mut_idx, void* stream)
 {
     REQUIRE(locs && pop && fitness, "eamrl_ea_tsp_run");
-    REQUIRE(B >= 0 && B <= 0x7fffffffLL && S >= 1 && S <= 128 && N >= 2 && N <= 128 && num_generations >= 0,
+    REQUIRE(B >= 0 && B <= 0x7fffffffLL && ea_tsp_lds_shape(S, N) && num_generations >= 0,
             "eamrl_ea_tsp_run (population and tour length are limited to 128)");
     REQUIRE(mutation_rate == mutation_rate && crossover_rate == crossover_rate && selection_rate >= 0.0,
             "eamrl_ea_tsp_run");
@@ -1094,9 +1177,9 @@ __attribute__((visibility("default"))) int eamrl_ea_cvrp_run(const float* locs, 
                                                             const double* mut_rand, const double* mut_u, void* stream)
 {
     REQUIRE(locs && demand && vcap && pop && fitness && init_mut_rand && init_mut_u, "eamrl_ea_cvrp_run");
-    REQUIRE(B >= 0 && B <= 0x7fffffffLL && S >= 1 && S <= 128 && N >= 1 && N <= 127 && L >= 2 && L <= 256 &&
-            num_generations >= 0, "eamrl_ea_cvrp_run (S <= 128, N <= 127 customers, L <= 256)");
-    REQUIRE((int64_t)S * L <= 24000, "eamrl_ea_cvrp_run (S * L <= 24000: three int16 populations must fit LDS)");
+    REQUIRE(B >= 0 && B <= 0x7fffffffLL && ea_cvrp_lds_dims(S, N, L) && num_generations >= 0,
+            "eamrl_ea_cvrp_run (S <= 128, N <= 127 customers, L <= 256)");
+    REQUIRE(ea_cvrp_lds_fits(S, L), "eamrl_ea_cvrp_run (S * L <= 24000: three int16 populations must fit LDS)");
     REQUIRE(mutation_rate == mutation_rate && crossover_rate == crossover_rate && selection_rate >= 0.0,
             "eamrl_ea_cvrp_run");
     if (num_generations > 0 && ea_num_elites(selection_rate, S) / 2 > 0)
@@ -1117,8 +1200,8 @@ __attribute__((visibility("default"))) int eamrl_ea_prize_run(int env, const flo
 {
     REQUIRE(env == EAMRL_ENV_PCTSP || env == EAMRL_ENV_OP, "eamrl_ea_prize_run (env: PCTSP or OP)");
     REQUIRE(locs && prize && aux && pop && fitness && init_mut_rand && init_mut_u, "eamrl_ea_prize_run");
-    REQUIRE(B >= 0 && B <= 0x7fffffffLL && S >= 1 && S <= 128 && N >= 1 && N <= 127 && L >= 2 && L <= 128 &&
-            num_generations >= 0, "eamrl_ea_prize_run (S <= 128, N <= 127 customers, L <= 128)");
+    REQUIRE(B >= 0 && B <= 0x7fffffffLL && ea_prize_lds_shape(S, N, L) && num_generations >= 0,
+            "eamrl_ea_prize_run (S <= 128, N <= 127 customers, L <= 128)");
     REQUIRE(mutation_rate == mutation_rate && crossover_rate == crossover_rate && selection_rate >= 0.0,
             "eamrl_ea_prize_run");
     if (num_generations > 0 && ea_num_elites(selection_rate, S) / 2 > 0)

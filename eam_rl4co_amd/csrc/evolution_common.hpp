@@ -4,8 +4,8 @@
 // The reference draws random numbers inside the operators (numba's per-thread generators); here every draw is an
 // input (see eamrl.h), which is what makes the operators reproducible and testable.
 //
-// k_ea<Ops> is the generation loop; an env supplies its operators as a policy type Ops (evolution.hip: TSP, CVRP;
-// evolution_prize.hip: PCTSP, OP) with
+// k_ea<Ops> is the generation loop; an env supplies its operators as a policy type Ops (evolution_routes.hpp: TSP, CVRP,
+// launched from evolution.hip; evolution_prize.hip: PCTSP, OP) with
 //   ENV_FLOATS, tail_bytes(O) ... LDS the env wants for itself: floats after `loc`, bytes after `tmp`
 //   INIT_MUTATE ................. whether EA.run mutates the initial population (every env but TSP)
 //   load(a, b, env, tail, loc, lane)  per-instance arrays into the env's LDS, per-thread constants (runs before the
@@ -15,6 +15,8 @@
 //   mutate(a, o, dm) ............ the mutation of offspring draw dm
 //   fitness(row, lane) .......... by one wavefront, every lane gets the value
 // Every hook is __forceinline__ and Ops holds scalars and LDS pointers only, so it lives in registers.
+// The per-offspring rule (ea_offspring) and the order of a sort (ea_before) are functions of their own: the phase kernels of
+// evolution_large.hip, which run the same loop on populations in device memory, call them too.
 // Sorting is stable ascending (ties keep index order) where the reference leaves tie order to numpy's argsort.
 #pragma once
 #include "kernels.hpp"
@@ -51,7 +53,12 @@ __device__ __forceinline__ int rint_u(int lo, int hi, double u)
     return lo + k;
 }
 
+// Node sets of the operators ("already in the child").  An operator takes its set type as a template parameter and gets an
+// empty set from the type's Pool, which the env's Ops carries: Bits128 lives in two registers and its pool is empty;
+// BitsLds (up to 1024 nodes, the device-memory path of evolution_large.hip) keeps its words in LDS, one slot per offspring
+// being built, because a register array indexed by a node would go to scratch memory.
 struct Bits128 {
+    struct Pool { __device__ __forceinline__ Bits128 get(int) const { return Bits128{}; } };
     unsigned long long lo = 0ull, hi = 0ull;
     __device__ __forceinline__ bool test(int i) const { return i < 64 ? (lo >> i) & 1ull : (hi >> (i - 64)) & 1ull; }
     __device__ __forceinline__ void set(int i) { if (i < 64) lo |= 1ull << i; else hi |= 1ull << (i - 64); }
@@ -59,6 +66,28 @@ struct Bits128 {
     __device__ __forceinline__ bool any() const { return (lo | hi) != 0ull; }
     __device__ __forceinline__ int lowest() const { return lo ? __builtin_ctzll(lo) : 64 + __builtin_ctzll(hi); }
     __device__ __forceinline__ int count() const { return __builtin_popcountll(lo) + __builtin_popcountll(hi); }
+};
+
+struct BitsLds {
+    static constexpr int WORDS = 16;               // 1024 nodes
+    struct Pool {
+        unsigned long long* words;                 // [slots][WORDS] in LDS
+        __device__ __forceinline__ BitsLds get(int slot) const
+        {
+            BitsLds s{words + slot * WORDS};
+            for (int i = 0; i < WORDS; ++i) s.w[i] = 0ull;
+            return s;
+        }
+    };
+    unsigned long long* w;
+    __device__ __forceinline__ bool test(int i) const { return (w[i >> 6] >> (i & 63)) & 1ull; }
+    __device__ __forceinline__ void set(int i) { w[i >> 6] |= 1ull << (i & 63); }
+    __device__ __forceinline__ int count() const
+    {
+        int n = 0;
+        for (int i = 0; i < WORDS; ++i) n += __builtin_popcountll(w[i]);
+        return n;
+    }
 };
 
 // reverse o[lo..hi]
@@ -118,11 +147,39 @@ constexpr size_t ea_fixed_lds()
     return EV_MAX * sizeof(float2) + (Ops::ENV_FLOATS + 2 * EV_MAX) * sizeof(float) + 5 * EV_MAX * sizeof(int16_t) + 16;
 }
 
+// stable ascending order (ties keep index order): does candidate j come before candidate i?
+__device__ __forceinline__ int ea_before(float fj, int j, float fi, int i) { return (fj < fi) | ((fj == fi) & (j < i)); }
+
+// Offspring t = 2 p + role of generation g of instance b, by one thread: the crossover of pair p (p1 / p2 in pair order; pair 0
+// always crosses, the others with the adjusted rate) or a copy of the offspring's own parent, then the mutation.  Draws are
+// indexed dp = (g B + b) P + p and dm = (g B + b) O + t.  slot: what Ops::child gets as the thread's scratch slot.
+template <class Ops>
+__device__ __forceinline__ void ea_offspring(const Ops& ops, const EaArgs& a, int g, int64_t b, int t, const int16_t* p1,
+                                             const int16_t* p2, int16_t* o, int slot)
+{
+    const int L = a.L, P = a.P, O = 2 * a.P;
+    const int p = t >> 1, role = t & 1;
+    const int16_t* own = role ? p2 : p1;
+    const int64_t dp = ((int64_t)g * a.B + b) * P + p;
+    double rate = a.crossover_rate;
+    if (p > 0 && P > 1) {
+        rate = ((double)P * a.crossover_rate - 1.0) / (double)(P - 1);
+        rate = rate > 1.0 ? 1.0 : rate;
+        rate = rate < 0.0 ? 0.0 : rate;
+    }
+    const double r = (p == 0) ? 0.0 : a.cross_rand[dp];
+    bool keep_parent = !(r < rate);
+    if (!keep_parent) keep_parent = ops.child(a, p1, p2, role, o, dp, slot);
+    if (keep_parent) for (int j = 0; j < L; ++j) o[j] = own[j];
+    const int64_t dm = ((int64_t)g * a.B + b) * O + t;
+    if (a.mut_rand[dm] < a.mutation_rate) ops.mutate(a, o, dm);
+}
+
 template <class Ops>
 __global__ __launch_bounds__(EVB) void k_ea(EaArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int S = a.S, L = a.L, M = a.M, P = a.P, O = 2 * a.P;
+    const int S = a.S, L = a.L, M = a.M, O = 2 * a.P;
     float2* loc = reinterpret_cast<float2*>(smem);                        // [M <= 128]
     float* env = reinterpret_cast<float*>(loc + EV_MAX);                  // [Ops::ENV_FLOATS] the env's own arrays
     float* fit = env + Ops::ENV_FLOATS;                                   // [S]
@@ -171,31 +228,15 @@ __global__ __launch_bounds__(EVB) void k_ea(EaArgs a)
         } else if (tid < S) {
             const float f = fit[tid];
             int rank = 0;
-            for (int j = 0; j < S; ++j) rank += (fit[j] < f) | ((fit[j] == f) & (j < tid));
+            for (int j = 0; j < S; ++j) rank += ea_before(fit[j], j, f, tid);
             if (rank >= S - a.ne) sel[rank - (S - a.ne)] = (int16_t)tid;
         }
         __syncthreads();
 
         // ---- crossover + mutation: thread t builds offspring t of pair t / 2 -----------------------------------------
         if (tid < O) {
-            const int p = tid >> 1, role = tid & 1;
-            const int16_t* p1 = pop + (int)sel[2 * p] * L;
-            const int16_t* p2 = pop + (int)sel[2 * p + 1] * L;
-            const int16_t* own = role ? p2 : p1;
-            int16_t* o = off + tid * L;
-            const int64_t dp = ((int64_t)g * a.B + b) * P + p;
-            double rate = a.crossover_rate;
-            if (p > 0 && P > 1) {
-                rate = ((double)P * a.crossover_rate - 1.0) / (double)(P - 1);
-                rate = rate > 1.0 ? 1.0 : rate;
-                rate = rate < 0.0 ? 0.0 : rate;
-            }
-            const double r = (p == 0) ? 0.0 : a.cross_rand[dp];
-            bool keep_parent = !(r < rate);
-            if (!keep_parent) keep_parent = ops.child(a, p1, p2, role, o, dp, tid);
-            if (keep_parent) for (int j = 0; j < L; ++j) o[j] = own[j];
-            const int64_t dm = ((int64_t)g * a.B + b) * O + tid;
-            if (a.mut_rand[dm] < a.mutation_rate) ops.mutate(a, o, dm);
+            const int p = tid >> 1;
+            ea_offspring(ops, a, g, b, tid, pop + (int)sel[2 * p] * L, pop + (int)sel[2 * p + 1] * L, off + tid * L, tid);
         }
         __syncthreads();
 
@@ -230,7 +271,7 @@ __global__ __launch_bounds__(EVB) void k_ea(EaArgs a)
                 int rank = 0;
                 for (int j = 0; j < C; ++j) {
                     const float fj = j < S ? fit[j] : ofit[j - S];
-                    rank += (fj < f) | ((fj == f) & (j < tid));
+                    rank += ea_before(fj, j, f, tid);
                 }
                 order[tid] = (int16_t)(C - 1 - rank);           // position in descending order
             }

@@ -159,6 +159,17 @@ inline int ea_num_elites(double selection_rate, int S)
 int launch_ea_tsp(const float* locs, int64_t* pop, float* fitness, int64_t B, int S, int N, int G, double mutation_rate,
                   double crossover_rate, double selection_rate, const double* cross_rand, const int32_t* cross_idx,
                   const double* mut_rand, const int32_t* mut_idx, hipStream_t st);
+// the device-memory path of the same two runs for populations and graphs of up to 1024 (evolution_large.hip); scratch: at
+// least ea_large_scratch_bytes(B, S, L) bytes of device memory, 16-byte aligned
+size_t ea_large_scratch_bytes(int64_t B, int S, int L);
+int launch_ea_tsp_large(const float* locs, int64_t* pop, float* fitness, int64_t B, int S, int N, int G, double mutation_rate,
+                        double crossover_rate, double selection_rate, const double* cross_rand, const int32_t* cross_idx,
+                        const double* mut_rand, const int32_t* mut_idx, void* scratch, size_t scratch_bytes, hipStream_t st);
+int launch_ea_cvrp_large(const float* locs, const float* demand, const float* vcap, int64_t* pop, float* fitness, int64_t B,
+                         int S, int N, int L, int G, double mutation_rate, double crossover_rate, double selection_rate,
+                         int top_k, const double* init_mut_rand, const double* init_mut_u, const double* cross_rand,
+                         const double* cross_u, const double* mut_rand, const double* mut_u, void* scratch,
+                         size_t scratch_bytes, hipStream_t st);
 // TSP 2-opt local search, all sweeps in one launch (local_search.hip)
 int launch_tsp_two_opt(const float* locs, const float* distances, const int64_t* actions_in, int64_t* actions_out,
                        int32_t* iters, int32_t* status, int64_t B, int N, int max_iterations, hipStream_t st);

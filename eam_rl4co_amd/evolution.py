@@ -4,7 +4,10 @@ rl4co/models/zoo/earl/evolution.py: `EA` (:125-354) and `evolution_worker` (:28-
 The reference moves the sampled tours to the CPU, spreads the instances over a thread pool and runs numba
 operators per instance, every training step.  Here the whole batch is one launch of `eamrl_ea_tsp_run`
 (the generation loop `k_ea` of csrc/evolution_common.hpp with the env's operators): one workgroup per instance
-keeps its population in LDS for all generations, and the tours never leave the GPU.
+keeps its population in LDS for all generations, and the tours never leave the GPU.  Populations or graphs beyond what
+the LDS of a workgroup holds (TSP and CVRP, up to 1024 tours and 1024 nodes) go through `eamrl_ea_*_run_large`
+(csrc/evolution_large.hip): the same operators and draws on populations in device memory, one launch per phase of a
+generation; `ops.ea_kernel` names the path a shape takes and `EA.run(..., kernel=)` can ask for one.
 
 Randomness: the reference draws inside the operators from numba's per-thread `np.random`, so it is not
 reproducible; here the draws are explicit tensors (`EADraws`), generated on the device from a `torch.Generator`
@@ -14,7 +17,7 @@ or supplied by the caller -- the form in which the operators are tested against 
 Built: TSP (order crossover, inversion mutation, elitism, per-start-node / top-k replacement, single-start
 rotation population), CVRP (route-prefix crossover with capacity repair, in-route inversion, initial
 mutation pass), PCTSP (cycle crossover with prize top-up, prefix inversion) and OP (budget-checked rebuild and
-inversion) -- operators in csrc/evolution.hip and, for the last two, csrc/evolution_prize.hip.  FFSP (not a routing env of this path) raises
+inversion) -- operators in csrc/evolution_routes.hpp and, for the last two, csrc/evolution_prize.hip.  FFSP (not a routing env of this path) raises
 NotImplementedError.
 """
 from __future__ import annotations
@@ -149,8 +152,10 @@ class EA:
 
     # -- the run ----------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def run(self, init_pop: torch.Tensor, td, draws: EADraws = None, generator=None):
-        """init_pop [B, S, N] int64 on the GPU (not modified) -> (pop [B, S, N], fitness [B, S])."""
+    def run(self, init_pop: torch.Tensor, td, draws: EADraws = None, generator=None, kernel=None):
+        """init_pop [B, S, N] int64 on the GPU (not modified) -> (pop [B, S, N], fitness [B, S]).  kernel: None = the
+        library's dispatch (ops.ea_kernel: the LDS kernel where it accepts the shape, the device-memory path for TSP / CVRP
+        up to 1024 otherwise); "lds" / "large" ask for one of them -- same results where both serve the shape."""
         squeeze = init_pop.dim() == 2
         pop = (init_pop[None] if squeeze else init_pop).to(torch.int64).contiguous().clone()
         B, S, N = pop.shape
@@ -162,9 +167,11 @@ class EA:
                                    td["vehicle_capacity"].reshape(B).to(torch.float32).contiguous(), pop, G,
                                    float(self.mutation_rate), float(self.crossover_rate), float(self.selection_rate),
                                    self.method == "am", draws.init_mut_rand, draws.init_mut_u, draws.cross_rand,
-                                   draws.cross_u, draws.mut_rand, draws.mut_u)
+                                   draws.cross_u, draws.mut_rand, draws.mut_u, kernel=kernel)
             return (pop[0], fit[0]) if squeeze else (pop, fit)
         if self.env_name in ("pctsp", "op"):
+            if kernel not in (None, "lds"):
+                raise ValueError(f"EA.run on {self.env_name} has the LDS kernel only (S <= 128, N <= 127, L <= 128)")
             draws = (EAPrizeDraws.sample(G, B, S, self.selection_rate, pop.device, generator) if draws is None
                      else draws.to(pop.device))
             pctsp = self.env_name == "pctsp"
@@ -182,7 +189,7 @@ class EA:
         rate32 = float(np.float32(self.crossover_rate))      # order_crossover_tsp's signature takes float32
         fit = ops.ea_tsp_run_(td["locs"].contiguous(), pop, G, float(self.mutation_rate), rate32,
                               float(self.selection_rate), draws.cross_rand, draws.cross_idx, draws.mut_rand,
-                              draws.mut_idx)
+                              draws.mut_idx, kernel=kernel)
         return (pop[0], fit[0]) if squeeze else (pop, fit)
 
 

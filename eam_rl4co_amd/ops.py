@@ -1305,13 +1305,46 @@ def ea_num_pairs(selection_rate: float, pop_size: int) -> int:
     return ne // 2
 
 
-def ea_tsp_run_(locs, pop, num_generations, mutation_rate, crossover_rate, selection_rate, cross_rand, cross_idx,
-                mut_rand, mut_idx):
-    """In place on pop [B, S, N] (int64); returns fitness [B, S].  Draw tensors: see include/eamrl.h."""
+EA_KERNELS = ("lds", "large")          # EAMRL_EA_KERNEL_* of include/eamrl.h
+
+
+def ea_kernel(env_name: str, S: int, N: int, L: int = 0, kernel: str | None = None) -> str:
+    """The kernel an EA.run of population size S on N nodes / customers with rows of L entries runs on: "lds" (one
+    workgroup per instance, populations in LDS: up to 128 x 128) or "large" (one launch per phase, populations in device
+    memory: TSP and CVRP up to 1024) -- the library's own dispatch (eamrl_ea_kernel).  kernel="lds" / "large" asks for that
+    path instead.  ValueError with the limit where no kernel, or not the requested one, serves the shape."""
+    if kernel not in (None,) + EA_KERNELS:
+        raise ValueError(f"ea kernel must be None, 'lds' or 'large', not {kernel!r}")
     lib = _lib.load()
+    rc = lib.eamrl_ea_kernel(ENVS[env_name], int(S), int(N), int(L))
+    if rc < 0:
+        raise ValueError(f"EA.run on {env_name} with population {S}, {N} nodes, rows of {L or N}: "
+                         f"{lib.eamrl_last_error().decode()}")
+    served = EA_KERNELS[rc]
+    if kernel == "lds" and served != "lds":
+        raise ValueError(f"EA.run on {env_name} with population {S}, {N} nodes, rows of {L or N} is beyond the LDS kernel "
+                         "(TSP: S, N <= 128; CVRP: S <= 128, N <= 127, L <= 256, S * L <= 24000)")
+    if kernel == "large" and env_name not in ("tsp", "cvrp"):
+        raise ValueError(f"the large EA path is built for tsp and cvrp, not {env_name} (S <= 128, N <= 127, L <= 128 there)")
+    return kernel or served
+
+
+def _ea_scratch(lib, env_name, B, S, L, selection_rate, device):
+    nbytes = lib.eamrl_ea_large_scratch_bytes(ENVS[env_name], B, S, L, float(selection_rate))
+    if nbytes == 0:
+        raise ValueError(lib.eamrl_last_error().decode())
+    return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+
+
+def ea_tsp_run_(locs, pop, num_generations, mutation_rate, crossover_rate, selection_rate, cross_rand, cross_idx,
+                mut_rand, mut_idx, kernel=None):
+    """In place on pop [B, S, N] (int64); returns fitness [B, S].  Draw tensors: see include/eamrl.h.  kernel: see
+    ea_kernel."""
+    lib = _lib.load()
+    B, S, N = pop.shape
+    kernel = ea_kernel("tsp", S, N, N, kernel)        # the shape's limits first: a ValueError needs no device
     _chk(locs, "locs", torch.float32)
     _chk(pop, "pop", torch.int64)
-    B, S, N = pop.shape
     if locs.shape != (B, N, 2):
         raise ValueError(f"ea_tsp_run: locs {tuple(locs.shape)} does not match pop {tuple(pop.shape)}")
     P = ea_num_pairs(selection_rate, S)
@@ -1323,19 +1356,25 @@ def ea_tsp_run_(locs, pop, num_generations, mutation_rate, crossover_rate, selec
         _chk(mut_idx, "mut_idx", torch.int32, (G, B, 2 * P, 2))
     fitness = torch.empty(B, S, device=pop.device, dtype=torch.float32)
     nul = lambda t: _ptr(t) if (G > 0 and P > 0) else None
-    _lib.check(lib.eamrl_ea_tsp_run(_ptr(locs), _ptr(pop), _ptr(fitness), B, S, N, G, float(mutation_rate),
-                                    float(crossover_rate), float(selection_rate), nul(cross_rand), nul(cross_idx),
-                                    nul(mut_rand), nul(mut_idx), _stream(pop)), "eamrl_ea_tsp_run")
+    args = (_ptr(locs), _ptr(pop), _ptr(fitness), B, S, N, G, float(mutation_rate), float(crossover_rate),
+            float(selection_rate), nul(cross_rand), nul(cross_idx), nul(mut_rand), nul(mut_idx))
+    if kernel == "large":
+        scratch, nbytes = _ea_scratch(lib, "tsp", B, S, N, selection_rate, pop.device)
+        _lib.check(lib.eamrl_ea_tsp_run_large(*args, _ptr(scratch), nbytes, _stream(pop)), "eamrl_ea_tsp_run_large")
+    else:
+        _lib.check(lib.eamrl_ea_tsp_run(*args, _stream(pop)), "eamrl_ea_tsp_run")
     return fitness
 
 
 def ea_cvrp_run_(locs, demand, vcap, pop, num_generations, mutation_rate, crossover_rate, selection_rate, top_k,
-                 init_mut_rand, init_mut_u, cross_rand, cross_u, mut_rand, mut_u):
-    """In place on pop [B, S, L] (int64 action rows, 0 = depot); returns fitness [B, S].  See include/eamrl.h."""
+                 init_mut_rand, init_mut_u, cross_rand, cross_u, mut_rand, mut_u, kernel=None):
+    """In place on pop [B, S, L] (int64 action rows, 0 = depot); returns fitness [B, S].  See include/eamrl.h.  kernel: see
+    ea_kernel."""
     lib = _lib.load()
-    _chk(pop, "pop", torch.int64)
     B, S, L = pop.shape
     N = demand.shape[-1]
+    kernel = ea_kernel("cvrp", S, N, L, kernel)
+    _chk(pop, "pop", torch.int64)
     _chk(locs, "locs", torch.float32, (B, N + 1, 2))
     _chk(demand, "demand", torch.float32, (B, N))
     _chk(vcap, "vcap", torch.float32, (B,))
@@ -1350,10 +1389,14 @@ def ea_cvrp_run_(locs, demand, vcap, pop, num_generations, mutation_rate, crosso
         _chk(mut_u, "mut_u", torch.float64, (G, B, 2 * P, 3))
     fitness = torch.empty(B, S, device=pop.device, dtype=torch.float32)
     nul = lambda t: _ptr(t) if (G > 0 and P > 0) else None
-    _lib.check(lib.eamrl_ea_cvrp_run(_ptr(locs), _ptr(demand), _ptr(vcap), _ptr(pop), _ptr(fitness), B, S, N, L, G,
-                                     float(mutation_rate), float(crossover_rate), float(selection_rate), int(bool(top_k)),
-                                     _ptr(init_mut_rand), _ptr(init_mut_u), nul(cross_rand), nul(cross_u),
-                                     nul(mut_rand), nul(mut_u), _stream(pop)), "eamrl_ea_cvrp_run")
+    args = (_ptr(locs), _ptr(demand), _ptr(vcap), _ptr(pop), _ptr(fitness), B, S, N, L, G, float(mutation_rate),
+            float(crossover_rate), float(selection_rate), int(bool(top_k)), _ptr(init_mut_rand), _ptr(init_mut_u),
+            nul(cross_rand), nul(cross_u), nul(mut_rand), nul(mut_u))
+    if kernel == "large":
+        scratch, nbytes = _ea_scratch(lib, "cvrp", B, S, L, selection_rate, pop.device)
+        _lib.check(lib.eamrl_ea_cvrp_run_large(*args, _ptr(scratch), nbytes, _stream(pop)), "eamrl_ea_cvrp_run_large")
+    else:
+        _lib.check(lib.eamrl_ea_cvrp_run(*args, _stream(pop)), "eamrl_ea_cvrp_run")
     return fitness
 
 
@@ -1364,9 +1407,10 @@ def ea_prize_run_(env_name, locs, prize, aux, pop, num_generations, mutation_rat
     lib = _lib.load()
     if env_name not in ("pctsp", "op"):
         raise ValueError("ea_prize_run: env must be pctsp or op")
-    _chk(pop, "pop", torch.int64)
     B, S, L = pop.shape
     M = locs.shape[1]
+    ea_kernel(env_name, S, M - 1, L)
+    _chk(pop, "pop", torch.int64)
     _chk(locs, "locs", torch.float32, (B, M, 2))
     _chk(prize, "prize", torch.float32, (B, M))
     _chk(aux, "penalty / max_length", torch.float32, (B, M))

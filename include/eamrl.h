@@ -23,6 +23,7 @@
 #ifndef EAMRL_H
 #define EAMRL_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -825,6 +826,42 @@ int eamrl_ea_cvrp_run(const float* locs, const float* demand, const float* vcap,
                       double selection_rate, int top_k, const double* init_mut_rand, const double* init_mut_u,
                       const double* cross_rand, const double* cross_u, const double* mut_rand, const double* mut_u,
                       void* stream);
+
+/* Which kernel serves an EA.run of this shape: EAMRL_EA_KERNEL_LDS | _LARGE (< 0: no kernel serves it, text via
+ * eamrl_last_error).  Host only, nothing is launched; it is the function the dispatcher itself branches on.  S population
+ * size, N TSP nodes / customers, L row length (ignored for TSP, whose rows are N long).  The LDS kernel is the answer exactly
+ * where eamrl_ea_tsp_run / eamrl_ea_cvrp_run / eamrl_ea_prize_run accept the shape; EAMRL_ENV_PCTSP and EAMRL_ENV_OP have no
+ * other. */
+#define EAMRL_EA_KERNEL_LDS 0   /* one workgroup per instance, populations in LDS (eamrl_ea_*_run) */
+#define EAMRL_EA_KERNEL_LARGE 1 /* one launch per phase, populations in device memory (eamrl_ea_*_run_large) */
+int eamrl_ea_kernel(int env, int S, int N, int L);
+
+/* Bytes of device scratch eamrl_ea_tsp_run_large / eamrl_ea_cvrp_run_large need (env = EAMRL_ENV_TSP with L = N, or
+ * EAMRL_ENV_CVRP); 0 = bad arguments (eamrl_last_error).  Host only.  Three int16 populations [B][S][L], fitness and sort
+ * scratch; sized for the largest elite set a selection rate can give, so one buffer serves every rate (selection_rate is
+ * only validated), and non-decreasing in B, S and L. */
+size_t eamrl_ea_large_scratch_bytes(int env, int64_t B, int S, int L, double selection_rate);
+
+/* eamrl_ea_tsp_run for 1 <= S <= 1024, 2 <= N <= 1024  [the same reference lines: evolution.py:252-354, :356-362,
+ * :1103-1108, :392-488, :490-517; replaces evolution_worker's thread pool :28-123].  Same arguments, same draws, same
+ * arithmetic and tie rules, same results bit for bit where both accept the shape; the populations live in `scratch` (device
+ * memory, 16-byte aligned, at least eamrl_ea_large_scratch_bytes; contents undefined before and after) and every phase of a
+ * generation is a launch of its own on `stream`: init, then per generation select / offspring (one 64-thread workgroup per
+ * instance and crossover pair) / rank / move / settle, then final -- 2 + 5 * num_generations launches, no host
+ * synchronisation and no allocation. */
+int eamrl_ea_tsp_run_large(const float* locs, int64_t* pop, float* fitness, int64_t B, int S, int N, int num_generations,
+                           double mutation_rate, double crossover_rate, double selection_rate, const double* cross_rand,
+                           const int32_t* cross_idx, const double* mut_rand, const int32_t* mut_idx, void* scratch,
+                           size_t scratch_bytes, void* stream);
+
+/* eamrl_ea_cvrp_run for 1 <= S <= 1024, 1 <= N <= 1023 customers, 2 <= L <= 2 (N + 1) + 1 (what a CVRP rollout can
+ * produce)  [evolution.py:252-354, :364-370, :585-788, :519-553, initial mutation :273-274].  Arguments, draws and results as
+ * eamrl_ea_cvrp_run; scratch and launches as eamrl_ea_tsp_run_large. */
+int eamrl_ea_cvrp_run_large(const float* locs, const float* demand, const float* vcap, int64_t* pop, float* fitness,
+                            int64_t B, int S, int N, int L, int num_generations, double mutation_rate,
+                            double crossover_rate, double selection_rate, int top_k, const double* init_mut_rand,
+                            const double* init_mut_u, const double* cross_rand, const double* cross_u,
+                            const double* mut_rand, const double* mut_u, void* scratch, size_t scratch_bytes, void* stream);
 
 /* EA.run for PCTSP (env = EAMRL_ENV_PCTSP) and OP (env = EAMRL_ENV_OP) populations  [evolution.py:252-354;
  *  PCTSP: :364-370 (fitness = f32(2.5*L) - cost, cost = -PCTSPEnv reward), :905-1101 (cycle_crossover_pctsp: cycles of the
