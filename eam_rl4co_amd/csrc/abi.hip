@@ -693,6 +693,27 @@ static int fill_args(const char* what, int env, const eamrl_cache* c, const eamr
     return 0;
 }
 
+// The eamrl_state members the fused env step of `env` reads or writes beyond what fill_args requires of every call: the one list,
+// for eamrl_am_decode_step with fuse_env_step and for every whole-rollout entry point (rollout_call).
+static int require_env_state(const char* what, int env, const DecArgs& a)
+{
+    REQUIRE(a.done, what);
+    if (env == EAMRL_ENV_CVRP) REQUIRE(a.visited && a.demand, what);
+    if (env == EAMRL_ENV_PCTSP) REQUIRE(a.visited && a.demand && a.istep, what);
+    if (env == EAMRL_ENV_OP) REQUIRE(a.visited && a.demand && a.istep && a.locs, what);
+    if (env == EAMRL_ENV_CVRPTW) REQUIRE(a.visited && a.demand && a.locs && a.tw && a.dur, what);
+    if (env == EAMRL_ENV_PDP) REQUIRE(a.visited && a.to_deliver, what);
+    return 0;
+}
+
+// DecArgs that carry the cache's shape and the row count alone: what the shape predicates of the rollout kernels read
+static DecArgs shape_args(const eamrl_cache* c, int64_t R)
+{
+    DecArgs a{};
+    a.B = c->B; a.M = c->M; a.E = c->E; a.H = c->H; a.ld = c->ld; a.R = R;
+    return a;
+}
+
 __attribute__((visibility("default"))) int eamrl_am_decode_step(int env, const eamrl_cache* cache_host,
                                                                const eamrl_state* state_host, int64_t R, int mode,
                                                                const float* noise, const int64_t* given, float tanh_clip,
@@ -706,152 +727,104 @@ __attribute__((visibility("default"))) int eamrl_am_decode_step(int env, const e
                        top_k, top_p, status, a);
     if (rc) return rc;
     REQUIRE(action && logp, "eamrl_am_decode_step");
-    if (fuse_env_step) {
-        REQUIRE(a.done, "eamrl_am_decode_step");
-        if (env == EAMRL_ENV_CVRP) REQUIRE(a.visited && a.demand, "eamrl_am_decode_step");
-        if (env == EAMRL_ENV_PCTSP) REQUIRE(a.visited && a.demand && a.istep, "eamrl_am_decode_step");
-        if (env == EAMRL_ENV_OP) REQUIRE(a.visited && a.demand && a.istep && a.locs, "eamrl_am_decode_step");
-        if (env == EAMRL_ENV_CVRPTW) REQUIRE(a.visited && a.demand && a.locs && a.tw && a.dur, "eamrl_am_decode_step");
-        if (env == EAMRL_ENV_PDP) REQUIRE(a.visited && a.to_deliver, "eamrl_am_decode_step");
-    }
+    if (fuse_env_step && (rc = require_env_state("eamrl_am_decode_step", env, a))) return rc;
     a.fuse_env = fuse_env_step;
     a.action = action; a.logp = logp; a.logprobs_all = logprobs_all; a.logits_raw = logits_raw;
     return launched(launch_decode_step(env, a, (hipStream_t)stream), "eamrl_am_decode_step");
 }
 
-// The kernel a whole-rollout call runs on -- the one place that decides it (eamrl_am_rollout, eamrl_am_rollout_seeded and the
-// eamrl_rollout_kernel query all ask here).  The start-sharing MFMA kernel does not filter; the register-resident one does
-// (graphs up to 112 nodes under a filter, 128 without); everything else streams.  shape_only: asked before a state exists.
-static int rollout_kernel_for(int env, const DecArgs& a, bool shape_only)
+// ---- the whole-rollout call path (DESIGN.md "The whole-rollout call path") -------------------------------------------------------
+// The kernel a whole-rollout call runs on -- the one place that decides it (rollout_call and the eamrl_rollout_kernel query ask
+// here).  The start-sharing MFMA kernel does not filter; the register-resident one does (graphs up to 112 nodes under a filter,
+// 128 without); everything else streams.  Shape, row count and filter settings alone decide.
+static int rollout_kernel_for(int env, const DecArgs& a)
 {
-    if (!g_debug[11] && rollout_ms_mfma_supports(env, a, shape_only)) return EAMRL_KERNEL_MS_MFMA;
+    if (!g_debug[11] && rollout_ms_mfma_supports(env, a)) return EAMRL_KERNEL_MS_MFMA;
     if (!g_debug[1] && rollout_resident_supports(env, a)) return EAMRL_KERNEL_RESIDENT;
     return EAMRL_KERNEL_STREAM;
 }
 
-__attribute__((visibility("default"))) int eamrl_rollout_kernel(int env, const eamrl_cache* cache_host, int64_t R, int t_max,
-                                                               int top_k, double top_p)
+// PolyNet and EAS-Lay: whether the start-sharing kernel with an extension takes this env, cache shape and row count.  A launch
+// covers at most 128 rows per instance; `split`: more are served by further launches (they differ in their row count only).
+static bool ext_shape_ok(int env, const eamrl_cache* c, int64_t R, bool split)
 {
-    const char* what = "eamrl_rollout_kernel";
-    REQUIRE(cache_host, what);
-    REQUIRE(env >= EAMRL_ENV_TSP && env <= EAMRL_ENV_PDP, what);
-    REQUIRE(cache_host->B > 0 && cache_host->M > 0 && cache_host->E > 0 && cache_host->H > 0, what);
-    REQUIRE(R > 0 && R % cache_host->B == 0 && R <= 0x7fffffffLL && t_max > 0, what);
-    REQUIRE(top_k >= 0 && top_p >= 0.0 && top_p <= 1.0, what);
-    DecArgs a{};
-    a.B = cache_host->B; a.M = cache_host->M; a.E = cache_host->E; a.H = cache_host->H; a.ld = cache_host->ld; a.R = R;
-    a.t_max = t_max; a.top_k = top_k; a.top_p = top_p;
-    return rollout_kernel_for(env, a, true);
+    if (c->B <= 0 || R <= 0 || R % c->B != 0 || R > 0x7fffffffLL) return false;
+    const int64_t S = R / c->B;
+    return rollout_ms_ext_supports(env, shape_args(c, (split && S > 128 ? 128 : S) * c->B));
 }
 
-__attribute__((visibility("default"))) int eamrl_am_rollout(int env, const eamrl_cache* cache_host,
-                                                           const eamrl_state* state_host, int64_t R, int mode,
-                                                           const float* noise, const int64_t* given, int t_given,
-                                                           float tanh_clip, float temperature, int top_k, double top_p,
-                                                           int t_max, int64_t* actions, float* logps, int32_t* steps_out,
-                                                           uint32_t* status, void* stream)
+enum { EXT_NONE, EXT_POLYNET, EXT_EAS_LAYER };
+
+// What the five whole-rollout entry points pass, in one record (the adapters below fill it member by member, in this order).
+struct RolloutCall {
+    int mode; const float* noise; const int64_t* given; int t_given;
+    bool seeded; uint64_t seed; const uint64_t* seed_dev; float* noise_scratch;
+    float clip, temp; int top_k; double top_p; int t_max;
+    int64_t* actions; float* logps; int32_t* steps_out; uint32_t* status;
+    int ext; const eamrl_polynet* poly; const eamrl_eas_layer* layer;       // ext: EXT_*, which of the two operand structs is required
+};
+
+// Every whole-rollout call: all requirements, in the order of the numbered steps, then the first launch.
+static int rollout_call(const char* what, int env, const eamrl_cache* cache, const eamrl_state* state, int64_t R,
+                        const RolloutCall& k, hipStream_t st)
 {
+    // 1. cache, state, sizes, mode and filter settings
     DecArgs a;
-    int rc = fill_args("eamrl_am_rollout", env, cache_host, state_host, R, mode, noise, given, tanh_clip, temperature,
-                       top_k, top_p, status, a);
+    int rc = fill_args(what, env, cache, state, R, k.mode, k.noise, k.given, k.clip, k.temp, k.top_k, k.top_p, k.status, a, k.seeded);
     if (rc) return rc;
-    REQUIRE(actions && logps && steps_out && a.done && t_max > 0, "eamrl_am_rollout");
-    if (env == EAMRL_ENV_CVRP) REQUIRE(a.visited && a.demand, "eamrl_am_rollout");
-    if (env == EAMRL_ENV_PCTSP) REQUIRE(a.visited && a.demand && a.istep, "eamrl_am_rollout");
-    if (env == EAMRL_ENV_OP) REQUIRE(a.visited && a.demand && a.istep && a.locs, "eamrl_am_rollout");
-    if (env == EAMRL_ENV_CVRPTW) REQUIRE(a.visited && a.demand && a.locs && a.tw && a.dur, "eamrl_am_rollout");
-    if (env == EAMRL_ENV_PDP) REQUIRE(a.visited && a.to_deliver, "eamrl_am_rollout");
-    if (mode == EAMRL_EVALUATE) REQUIRE(t_given > 0, "eamrl_am_rollout");
-    a.fuse_env = 1; a.t_max = t_max; a.t_given = t_given;
-    a.action = actions; a.logp = logps; a.steps_out = steps_out;
-    const int kernel = rollout_kernel_for(env, a, false);
-    if (kernel == EAMRL_KERNEL_MS_MFMA)
-        return launched(launch_rollout_ms_mfma(env, a, (hipStream_t)stream), "eamrl_am_rollout");
-    if (kernel == EAMRL_KERNEL_RESIDENT)
-        return launched(launch_rollout_resident(env, a, (hipStream_t)stream), "eamrl_am_rollout");
-    return launched(launch_rollout_stream(env, a, (hipStream_t)stream), "eamrl_am_rollout");
-}
-
-__attribute__((visibility("default"))) int eamrl_exp1_noise(uint64_t seed, const uint64_t* seed_dev, float* noise, int64_t R,
-                                                           int T, int M, void* stream)
-{
-    REQUIRE(noise && R >= 0 && T > 0 && M > 0, "eamrl_exp1_noise");
-    return launched(launch_exp1_noise(seed, seed_dev, noise, R, T, M, (hipStream_t)stream), "eamrl_exp1_noise");
-}
-
-__attribute__((visibility("default"))) int eamrl_rollout_rng_native(int env, const eamrl_cache* cache_host, int64_t R)
-{
-    if (!cache_host || R <= 0 || g_debug[11]) return 0;
-    DecArgs a{};
-    a.B = cache_host->B; a.M = cache_host->M; a.E = cache_host->E; a.H = cache_host->H; a.ld = cache_host->ld; a.R = R;
-    return rollout_ms_mfma_supports(env, a, true) ? 1 : 0;
-}
-
-__attribute__((visibility("default"))) int eamrl_am_rollout_seeded(int env, const eamrl_cache* cache_host,
-                                                                  const eamrl_state* state_host, int64_t R, uint64_t seed,
-                                                                  const uint64_t* seed_dev, float* noise_scratch,
-                                                                  float tanh_clip, float temperature,
-                                                                  int t_max, int64_t* actions, float* logps,
-                                                                  int32_t* steps_out, uint32_t* status, void* stream)
-{
-    DecArgs a;
-    int rc = fill_args("eamrl_am_rollout_seeded", env, cache_host, state_host, R, EAMRL_SAMPLE, nullptr, nullptr, tanh_clip,
-                       temperature, 0, 0.0, status, a, true);
-    if (rc) return rc;
-    REQUIRE(actions && logps && steps_out && a.done && t_max > 0, "eamrl_am_rollout_seeded");
-    a.fuse_env = 1; a.t_max = t_max; a.t_given = 0;
-    a.action = actions; a.logp = logps; a.steps_out = steps_out;
-    if (rollout_kernel_for(env, a, false) == EAMRL_KERNEL_MS_MFMA) {
-        a.seed = seed; a.seed_dev = seed_dev; a.use_rng = 1;
-        return launched(launch_rollout_ms_mfma(env, a, (hipStream_t)stream), "eamrl_am_rollout_seeded");
-    }
-    // kernels without in-place noise: the same draws as a tensor in the caller's scratch
-    REQUIRE(noise_scratch != nullptr, "eamrl_am_rollout_seeded (noise_scratch [R][t_max][M] needed for this shape)");
-    rc = launch_exp1_noise(seed, seed_dev, noise_scratch, R, t_max, a.M, (hipStream_t)stream);
-    if (rc) return launched(rc, "eamrl_am_rollout_seeded");
-    return eamrl_am_rollout(env, cache_host, state_host, R, EAMRL_SAMPLE, noise_scratch, nullptr, 0, tanh_clip, temperature, 0,
-                            0.0, t_max, actions, logps, steps_out, status, stream);
-}
-
-// PolyNet rollouts (PolyNetAttention.forward, nn/attention.py:519-556, inside the decode loop of constructive/base.py:236-250).
-static bool polynet_shape_ok(int env, const eamrl_cache* c, int64_t R)
-{
-    if (env != EAMRL_ENV_TSP && env != EAMRL_ENV_CVRP) return false;
-    if (c->B <= 0 || R <= 0 || R % c->B != 0 || R > 0x7fffffffLL || R / c->B < 2) return false;
-    DecArgs a{};
-    a.B = c->B; a.M = c->M; a.E = c->E; a.H = c->H; a.ld = c->ld;
-    a.R = (R / c->B > 128 ? 128 : R / c->B) * c->B;         // the first launch (later ones differ in their number of solutions only)
-    return rollout_ms_poly_supports(env, a, true);
-}
-
-static int polynet_rollout(const char* what, int env, const eamrl_cache* cache_host, const eamrl_state* state_host,
-                           const eamrl_polynet* poly, int64_t R, int mode, const float* noise, const int64_t* given, int t_given,
-                           float tanh_clip, float temperature, int t_max, int64_t* actions, float* logps, int32_t* steps_out,
-                           uint32_t* status, bool seeded, uint64_t seed, const uint64_t* seed_dev, void* stream)
-{
-    DecArgs a;
-    int rc = fill_args(what, env, cache_host, state_host, R, mode, noise, given, tanh_clip, temperature, 0, 0.0, status, a, seeded);
-    if (rc) return rc;
-    REQUIRE(poly != nullptr, what);
-    REQUIRE(poly->Wout && poly->W1 && poly->ctab && poly->W2 && poly->b2 && poly->L, what);
-    REQUIRE(((uintptr_t)poly->Wout % 16 == 0) && ((uintptr_t)poly->W1 % 16 == 0) && ((uintptr_t)poly->ctab % 16 == 0) &&
-            ((uintptr_t)poly->W2 % 16 == 0) && ((uintptr_t)poly->b2 % 16 == 0) && ((uintptr_t)poly->L % 16 == 0), what);
-    REQUIRE(poly->P == 256 && poly->k >= 1 && poly->k <= (1 << 20) && poly->s_offset >= 0, what);
-    REQUIRE(polynet_shape_ok(env, cache_host, R), what);
+    // 2. the env's state
+    if ((rc = require_env_state(what, env, a))) return rc;
+    // 3. outputs and step counts
+    REQUIRE(k.actions && k.logps && k.steps_out && k.t_max > 0, what);
+    if (k.mode == EAMRL_EVALUATE) REQUIRE(k.t_given > 0, what);
+    a.fuse_env = 1; a.t_max = k.t_max; a.t_given = k.t_given;
+    a.action = k.actions; a.logp = k.logps; a.steps_out = k.steps_out;
+    // 4. the extension's operands and shape
     const int64_t B = a.B, S = R / B;
-    REQUIRE(((int64_t)poly->s_offset + S) * B <= 0x7fffffffLL, what);
-    REQUIRE(actions && logps && steps_out && a.done && t_max > 0 && a.heads_out == nullptr, what);
-    if (env == EAMRL_ENV_CVRP) REQUIRE(a.visited && a.demand, what);
-    if (mode == EAMRL_EVALUATE) REQUIRE(t_given > 0, what);
-    a.fuse_env = 1; a.t_max = t_max; a.t_given = t_given;
-    a.steps_out = steps_out;
-    a.Lp = poly->L;
-    if (seeded) { a.seed = seed; a.seed_dev = seed_dev; a.use_rng = 1; }
-    {
-        DecArgs f = a;
-        f.R = (S > 128 ? 128 : S) * B;
-        REQUIRE(rollout_ms_poly_supports(env, f, false), what);
+    PolyArgs pn{};
+    LayArgs ly{};
+    if (k.ext == EXT_POLYNET) {
+        const eamrl_polynet* p = k.poly;
+        REQUIRE(p != nullptr, what);
+        REQUIRE(p->Wout && p->W1 && p->ctab && p->W2 && p->b2 && p->L, what);
+        REQUIRE(((uintptr_t)p->Wout % 16 == 0) && ((uintptr_t)p->W1 % 16 == 0) && ((uintptr_t)p->ctab % 16 == 0) &&
+                ((uintptr_t)p->W2 % 16 == 0) && ((uintptr_t)p->b2 % 16 == 0) && ((uintptr_t)p->L % 16 == 0), what);
+        REQUIRE(p->P == 256 && p->k >= 1 && p->k <= (1 << 20) && p->s_offset >= 0, what);
+        REQUIRE(ext_shape_ok(env, cache, R, true), what);
+        REQUIRE(((int64_t)p->s_offset + S) * B <= 0x7fffffffLL, what);
+        REQUIRE(a.heads_out == nullptr, what);
+        a.Lp = p->L;                                    // the unfolded logit key: the PolyNet layers sit before project_out
+        pn = PolyArgs{p->Wout, p->W1, p->ctab, p->W2, p->b2, p->k, p->s_offset};
+    } else if (k.ext == EXT_EAS_LAYER) {
+        const eamrl_eas_layer* l = k.layer;
+        REQUIRE(l != nullptr, what);
+        REQUIRE(l->W1 && l->b1 && l->W2 && l->b2, what);
+        REQUIRE(((uintptr_t)l->W1 % 16 == 0) && ((uintptr_t)l->b1 % 16 == 0) && ((uintptr_t)l->W2 % 16 == 0) &&
+                ((uintptr_t)l->b2 % 16 == 0), what);
+        REQUIRE(!l->forced || l->t_forced > 0, what);
+        REQUIRE(env == EAMRL_ENV_TSP || env == EAMRL_ENV_CVRP, what);
+        REQUIRE(a.M <= 112 && S >= 2 && S <= 128, what);
+        REQUIRE(ext_shape_ok(env, cache, R, false), what);                  // E = 128, H = 8, 2 <= M <= 112
+        REQUIRE(!a.heads_out || (uintptr_t)a.heads_out % 16 == 0, what);
+        ly = LayArgs{l->W1, l->b1, l->W2, l->b2, l->forced, l->t_forced};
     }
+    // 5. the seed
+    REQUIRE(!k.seeded || k.mode == EAMRL_SAMPLE, what);
+    if (k.seeded) { a.seed = k.seed; a.seed_dev = k.seed_dev; a.use_rng = 1; }
+    // 6. the kernel (an extension exists in the start-sharing kernel only; step 4 has checked that it takes the shape)
+    const int kernel = k.ext != EXT_NONE ? EAMRL_KERNEL_MS_MFMA : rollout_kernel_for(env, a);
+    // 7. launch
+    if (kernel != EAMRL_KERNEL_MS_MFMA) {
+        if (k.seeded) {     // kernels without in-place noise: the same draws as a tensor in the caller's scratch
+            REQUIRE(k.noise_scratch != nullptr, what);      // [R][t_max][M], needed for this shape
+            a.seed = 0; a.seed_dev = nullptr; a.use_rng = 0;
+            a.noise = k.noise_scratch;
+            rc = launch_exp1_noise(k.seed, k.seed_dev, k.noise_scratch, R, k.t_max, a.M, st);
+            if (rc) return launched(rc, what);
+        }
+        return launched(kernel == EAMRL_KERNEL_RESIDENT ? launch_rollout_resident(env, a, st) : launch_rollout_stream(env, a, st), what);
+    }
+    // the start-sharing kernel: one launch per 128 rows of an instance (only a PolyNet rollout has more than 128)
     const int M = a.M;
     for (int64_t s0 = 0; s0 < S; s0 += 128) {
         const int64_t Sc = S - s0 < 128 ? S - s0 : 128, r0 = s0 * B;
@@ -865,21 +838,80 @@ static int polynet_rollout(const char* what, int env, const eamrl_cache* cache_h
         c.mask = a.mask + r0 * M;
         if (a.visited) c.visited = a.visited + r0 * M;
         c.done = a.done + r0;
-        if (noise) c.noise = noise + r0 * t_max * M;
-        if (given) c.given = given + r0 * t_given;
-        c.action = actions + r0 * t_max;
-        c.logp = logps + r0 * t_max;
-        const PolyArgs pn{poly->Wout, poly->W1, poly->ctab, poly->W2, poly->b2, poly->k, (int)(poly->s_offset + s0)};
-        rc = launch_rollout_ms_poly(env, c, pn, (hipStream_t)stream);
+        if (a.noise) c.noise = a.noise + r0 * k.t_max * M;
+        if (a.given) c.given = a.given + r0 * k.t_given;
+        c.action = k.actions + r0 * k.t_max;
+        c.logp = k.logps + r0 * k.t_max;
+        pn.s_off = (k.poly ? k.poly->s_offset : 0) + (int)s0;
+        rc = launch_rollout_ms(env, c, k.ext == EXT_POLYNET ? &pn : nullptr, k.ext == EXT_EAS_LAYER ? &ly : nullptr, st);
         if (rc) return launched(rc, what);
     }
     return 0;
 }
 
+__attribute__((visibility("default"))) int eamrl_rollout_kernel(int env, const eamrl_cache* cache_host, int64_t R, int t_max,
+                                                               int top_k, double top_p)
+{
+    const char* what = "eamrl_rollout_kernel";
+    REQUIRE(cache_host, what);
+    REQUIRE(env >= EAMRL_ENV_TSP && env <= EAMRL_ENV_PDP, what);
+    REQUIRE(cache_host->B > 0 && cache_host->M > 0 && cache_host->E > 0 && cache_host->H > 0, what);
+    REQUIRE(R > 0 && R % cache_host->B == 0 && R <= 0x7fffffffLL && t_max > 0, what);
+    REQUIRE(top_k >= 0 && top_p >= 0.0 && top_p <= 1.0, what);
+    DecArgs a = shape_args(cache_host, R);
+    a.t_max = t_max; a.top_k = top_k; a.top_p = top_p;
+    return rollout_kernel_for(env, a);
+}
+
+__attribute__((visibility("default"))) int eamrl_exp1_noise(uint64_t seed, const uint64_t* seed_dev, float* noise, int64_t R,
+                                                           int T, int M, void* stream)
+{
+    REQUIRE(noise && R >= 0 && T > 0 && M > 0, "eamrl_exp1_noise");
+    return launched(launch_exp1_noise(seed, seed_dev, noise, R, T, M, (hipStream_t)stream), "eamrl_exp1_noise");
+}
+
+__attribute__((visibility("default"))) int eamrl_rollout_rng_native(int env, const eamrl_cache* cache_host, int64_t R)
+{
+    if (!cache_host || R <= 0 || g_debug[11]) return 0;
+    return rollout_ms_mfma_supports(env, shape_args(cache_host, R)) ? 1 : 0;
+}
+
+// PolyNet rollouts (PolyNetAttention.forward, nn/attention.py:519-556, inside the decode loop of constructive/base.py:236-250)
 __attribute__((visibility("default"))) int eamrl_rollout_polynet_supported(int env, const eamrl_cache* cache_host, int64_t R)
 {
     if (!cache_host || g_debug[11]) return 0;
-    return polynet_shape_ok(env, cache_host, R) ? 1 : 0;
+    return ext_shape_ok(env, cache_host, R, true) ? 1 : 0;
+}
+
+// EAS-Lay (zoo/eas/decoder.py:35-126): the rollout with a per-instance residual layer, and the layer's backward
+__attribute__((visibility("default"))) int eamrl_rollout_eas_layer_supported(int env, const eamrl_cache* cache_host, int64_t R)
+{
+    if (!cache_host || g_debug[11]) return 0;
+    return ext_shape_ok(env, cache_host, R, false) ? 1 : 0;
+}
+
+__attribute__((visibility("default"))) int eamrl_am_rollout(int env, const eamrl_cache* cache_host,
+                                                           const eamrl_state* state_host, int64_t R, int mode,
+                                                           const float* noise, const int64_t* given, int t_given,
+                                                           float tanh_clip, float temperature, int top_k, double top_p,
+                                                           int t_max, int64_t* actions, float* logps, int32_t* steps_out,
+                                                           uint32_t* status, void* stream)
+{
+    const RolloutCall k{mode, noise, given, t_given, false, 0, nullptr, nullptr, tanh_clip, temperature, top_k, top_p, t_max,
+                        actions, logps, steps_out, status, EXT_NONE, nullptr, nullptr};
+    return rollout_call("eamrl_am_rollout", env, cache_host, state_host, R, k, (hipStream_t)stream);
+}
+
+__attribute__((visibility("default"))) int eamrl_am_rollout_seeded(int env, const eamrl_cache* cache_host,
+                                                                  const eamrl_state* state_host, int64_t R, uint64_t seed,
+                                                                  const uint64_t* seed_dev, float* noise_scratch,
+                                                                  float tanh_clip, float temperature,
+                                                                  int t_max, int64_t* actions, float* logps,
+                                                                  int32_t* steps_out, uint32_t* status, void* stream)
+{
+    const RolloutCall k{EAMRL_SAMPLE, nullptr, nullptr, 0, true, seed, seed_dev, noise_scratch, tanh_clip, temperature, 0, 0.0, t_max,
+                        actions, logps, steps_out, status, EXT_NONE, nullptr, nullptr};
+    return rollout_call("eamrl_am_rollout_seeded", env, cache_host, state_host, R, k, (hipStream_t)stream);
 }
 
 __attribute__((visibility("default"))) int eamrl_am_rollout_polynet(int env, const eamrl_cache* cache_host,
@@ -889,8 +921,9 @@ __attribute__((visibility("default"))) int eamrl_am_rollout_polynet(int env, con
                                                                    float temperature, int t_max, int64_t* actions, float* logps,
                                                                    int32_t* steps_out, uint32_t* status, void* stream)
 {
-    return polynet_rollout("eamrl_am_rollout_polynet", env, cache_host, state_host, poly, R, mode, noise, given, t_given, tanh_clip,
-                           temperature, t_max, actions, logps, steps_out, status, false, 0, nullptr, stream);
+    const RolloutCall k{mode, noise, given, t_given, false, 0, nullptr, nullptr, tanh_clip, temperature, 0, 0.0, t_max,
+                        actions, logps, steps_out, status, EXT_POLYNET, poly, nullptr};
+    return rollout_call("eamrl_am_rollout_polynet", env, cache_host, state_host, R, k, (hipStream_t)stream);
 }
 
 __attribute__((visibility("default"))) int eamrl_am_rollout_polynet_seeded(int env, const eamrl_cache* cache_host,
@@ -901,24 +934,9 @@ __attribute__((visibility("default"))) int eamrl_am_rollout_polynet_seeded(int e
                                                                           float* logps, int32_t* steps_out, uint32_t* status,
                                                                           void* stream)
 {
-    return polynet_rollout("eamrl_am_rollout_polynet_seeded", env, cache_host, state_host, poly, R, EAMRL_SAMPLE, nullptr, nullptr,
-                           0, tanh_clip, temperature, t_max, actions, logps, steps_out, status, true, seed, seed_dev, stream);
-}
-
-// EAS-Lay (zoo/eas/decoder.py:35-126): the rollout with a per-instance residual layer, and the layer's backward
-static bool eas_layer_shape_ok(int env, const eamrl_cache* c, int64_t R)
-{
-    if (env != EAMRL_ENV_TSP && env != EAMRL_ENV_CVRP) return false;
-    if (c->B <= 0 || R <= 0 || R % c->B != 0 || R > 0x7fffffffLL) return false;
-    DecArgs a{};
-    a.B = c->B; a.M = c->M; a.E = c->E; a.H = c->H; a.ld = c->ld; a.R = R;
-    return rollout_ms_lay_supports(env, a, true);
-}
-
-__attribute__((visibility("default"))) int eamrl_rollout_eas_layer_supported(int env, const eamrl_cache* cache_host, int64_t R)
-{
-    if (!cache_host || g_debug[11]) return 0;
-    return eas_layer_shape_ok(env, cache_host, R) ? 1 : 0;
+    const RolloutCall k{EAMRL_SAMPLE, nullptr, nullptr, 0, true, seed, seed_dev, nullptr, tanh_clip, temperature, 0, 0.0, t_max,
+                        actions, logps, steps_out, status, EXT_POLYNET, poly, nullptr};
+    return rollout_call("eamrl_am_rollout_polynet_seeded", env, cache_host, state_host, R, k, (hipStream_t)stream);
 }
 
 __attribute__((visibility("default"))) int eamrl_am_rollout_eas_layer(int env, const eamrl_cache* cache_host,
@@ -929,30 +947,9 @@ __attribute__((visibility("default"))) int eamrl_am_rollout_eas_layer(int env, c
                                                                      int t_max, int64_t* actions, float* logps,
                                                                      int32_t* steps_out, uint32_t* status, void* stream)
 {
-    const char* what = "eamrl_am_rollout_eas_layer";
-    REQUIRE(cache_host && state_host && layer, what);
-    REQUIRE(!seeded || mode == EAMRL_SAMPLE, "eamrl_am_rollout_eas_layer (seeded: mode must be EAMRL_SAMPLE)");
-    DecArgs a;
-    int rc = fill_args(what, env, cache_host, state_host, R, mode, noise, given, tanh_clip, temperature, 0, 0.0, status, a, seeded != 0);
-    if (rc) return rc;
-    REQUIRE(layer->W1 && layer->b1 && layer->W2 && layer->b2, what);
-    REQUIRE(((uintptr_t)layer->W1 % 16 == 0) && ((uintptr_t)layer->b1 % 16 == 0) && ((uintptr_t)layer->W2 % 16 == 0) &&
-            ((uintptr_t)layer->b2 % 16 == 0), what);
-    REQUIRE(!layer->forced || layer->t_forced > 0, what);
-    REQUIRE(env == EAMRL_ENV_TSP || env == EAMRL_ENV_CVRP, "eamrl_am_rollout_eas_layer (env: TSP or CVRP)");
-    REQUIRE(a.M <= 112, "eamrl_am_rollout_eas_layer (M <= 112)");
-    REQUIRE(R / a.B >= 2 && R / a.B <= 128, "eamrl_am_rollout_eas_layer (2 <= rows per instance <= 128)");
-    REQUIRE(eas_layer_shape_ok(env, cache_host, R), "eamrl_am_rollout_eas_layer (E = 128, H = 8, 2 <= M <= 112)");
-    REQUIRE(actions && logps && steps_out && a.done && t_max > 0, what);
-    if (env == EAMRL_ENV_CVRP) REQUIRE(a.visited && a.demand, what);
-    if (mode == EAMRL_EVALUATE) REQUIRE(t_given > 0, what);
-    REQUIRE(!a.heads_out || (uintptr_t)a.heads_out % 16 == 0, what);
-    a.fuse_env = 1; a.t_max = t_max; a.t_given = t_given;
-    a.action = actions; a.logp = logps; a.steps_out = steps_out;
-    if (seeded) { a.seed = seed; a.seed_dev = seed_dev; a.use_rng = 1; }
-    REQUIRE(rollout_ms_lay_supports(env, a, false), what);
-    const LayArgs ly{layer->W1, layer->b1, layer->W2, layer->b2, layer->forced, layer->t_forced};
-    return launched(launch_rollout_ms_lay(env, a, ly, (hipStream_t)stream), what);
+    const RolloutCall k{mode, noise, given, t_given, seeded != 0, seed, seed_dev, nullptr, tanh_clip, temperature, 0, 0.0, t_max,
+                        actions, logps, steps_out, status, EXT_EAS_LAYER, nullptr, layer};
+    return rollout_call("eamrl_am_rollout_eas_layer", env, cache_host, state_host, R, k, (hipStream_t)stream);
 }
 
 __attribute__((visibility("default"))) int eamrl_eas_layer_backward(const eamrl_reeval* p, const eamrl_eas_layer* layer, void* stream)

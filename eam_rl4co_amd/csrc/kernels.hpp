@@ -135,17 +135,16 @@ int launch_rollout_stream(int env, const DecArgs& a, hipStream_t st);
 void launch_rollout_pad(int env, const DecArgs& a, hipStream_t st);   // final state of rows that finished early
 int launch_rollout_resident(int env, const DecArgs& a, hipStream_t st);
 bool rollout_resident_supports(int env, const DecArgs& a);
-bool rollout_ms_mfma_supports(int env, const DecArgs& a, bool shape_only = false);
-int launch_rollout_ms_mfma(int env, const DecArgs& a, hipStream_t st);
 // PolyNet case of the start-sharing kernel (rollout_multistart.hip): the operands of eamrl_polynet, by value
 struct PolyArgs { const float* Wout; const float* W1; const float* ctab; const float* W2; const float* b2; int k; int s_off; };
-bool rollout_ms_poly_supports(int env, const DecArgs& a, bool shape_only = false);
-int launch_rollout_ms_poly(int env, const DecArgs& a, const PolyArgs& pn, hipStream_t st);
 // EAS-Lay case of the same kernel: the operands of eamrl_eas_layer that the rollout reads, by value (per-instance weights in
 // fragment order, [B][E * E] and [B][E]); forced [B][t_forced] or NULL = the picks of every instance's last row
 struct LayArgs { const float* W1; const float* b1; const float* W2; const float* b2; const int64_t* forced; int t_forced; };
-bool rollout_ms_lay_supports(int env, const DecArgs& a, bool shape_only = false);
-int launch_rollout_ms_lay(int env, const DecArgs& a, const LayArgs& ly, hipStream_t st);
+// the start-sharing kernel: shape predicates (cache shape, rows, filter; no pointer is read) and the launcher (pn / ly: at most
+// one of them, NULL for the plain kernel)
+bool rollout_ms_mfma_supports(int env, const DecArgs& a);
+bool rollout_ms_ext_supports(int env, const DecArgs& a);        // with an extension (PolyNet, EAS-Lay): TSP or CVRP
+int launch_rollout_ms(int env, const DecArgs& a, const PolyArgs* pn, const LayArgs* ly, hipStream_t st);
 // EAS-Lay backward (eas_layer.hip): dW1 db1 dW2 db2 of eamrl_eas_layer from the rollout's heads and log-probs
 int launch_eas_layer_bwd(const ReevalArgs& a, const eamrl_eas_layer& ly, hipStream_t st);
 int launch_exp1_noise(uint64_t seed, const uint64_t* seed_dev, float* noise, int64_t R, int T, int M, hipStream_t st);

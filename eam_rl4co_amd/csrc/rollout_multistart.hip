@@ -974,87 +974,72 @@ __global__ __launch_bounds__(512, 2) void k_rollout_ms_mfma(DecArgs a, int S, in
     }
 }
 
-template <int RTT, int CC, int ENV>
-int launch_t(const DecArgs& a, int S, hipStream_t st)
+// The one host launcher of k_rollout_ms_mfma.  PA is the kernel's trailing pack: empty (the plain kernel), one PolyArgs or one
+// LayArgs.  Dynamic LDS: the key tiles, for SDVRP also the remaining-demand rows; the plain kernel of every other env asks for
+// 32 KB more, the extensions for nothing more.  g_debug[13] (no split of an instance's query tiles) applies to the plain kernel.
+template <int RTT, int CC, int ENV, typename... PA>
+int launch_t(const DecArgs& a, int S, hipStream_t st, const PA&... pa)
 {
-    const size_t lds = ((size_t)RTT * 32 * 64 + (ENV == EAMRL_ENV_SDVRP ? (size_t)SMAX * 16 * RTT : 0)) * sizeof(float);
-    auto k = k_rollout_ms_mfma<RTT, CC, ENV>;
+    constexpr bool PLAIN = sizeof...(PA) == 0, SD = ENV == EAMRL_ENV_SDVRP;
+    const size_t lds = ((size_t)RTT * 32 * 64 + (SD ? (size_t)SMAX * 16 * RTT : 0)) * sizeof(float);
+    auto k = k_rollout_ms_mfma<RTT, CC, ENV, PA...>;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(lds + (ENV == EAMRL_ENV_SDVRP ? 0 : 32 * 1024))) != hipSuccess)
+                            (int)(lds + (PLAIN && !SD ? 32 * 1024 : 0))) != hipSuccess)
         return EAMRL_E_LAUNCH;
     // one workgroup per CU is resident (register budget): a batch smaller than the chip splits each instance's query tiles
     const int nqt = (S + 15) / 16;
     int nsplit = a.B > 0 ? (int)(256 / a.B) : 1;
     nsplit = nsplit < 1 ? 1 : (nsplit > nqt ? nqt : nsplit);
-    if (g_debug[13]) nsplit = 1;
-    hipLaunchKernelGGL(k, dim3((unsigned)(a.B * nsplit)), dim3(512), lds, st, a, S, nsplit);
+    if (PLAIN && g_debug[13]) nsplit = 1;
+    hipLaunchKernelGGL(k, dim3((unsigned)(a.B * nsplit)), dim3(512), lds, st, a, S, nsplit, pa...);
     return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
 }
 
-template <int ENV>
-int launch_env_t(const DecArgs& a, int S, int C, hipStream_t st)
+// The instantiation for a graph of a.M nodes.
+// Plain kernel: compile-time chunk lengths for the common sizes, TSP-20 / 50 / 100 (C = 5, 13, 25) and the depot envs' 21 / 51 /
+// 101 nodes (C = 6, 13, 26); everything else runs the run-time variant.
+// PolyNet and EAS-Lay (TSP and CVRP): one instantiation per key-tile count.  The glimpse's node chunks are the fixed
+// [4 RTT g, 4 RTT (g + 1)) -- whole k-steps, nothing straddles -- for every M the tile count covers (slots beyond M carry zero
+// weights and values).  The run-time chunk length ceil(M / 4) of the plain kernel, which exists to reproduce the oracle's
+// summation order bit for bit, costs ~50 VGPRs that the weight stream needs (scratch otherwise); PolyNet is pinned to a float64
+// restatement instead, and the heads an EAS-Lay rollout captures are the plain kernel's to rounding, not bit for bit.
+template <int ENV, typename... PA>
+int launch_env_t(const DecArgs& a, int S, hipStream_t st, const PA&... pa)
 {
-    // compile-time chunk lengths for the common sizes: TSP-20 / 50 / 100 (C = 5, 13, 25) and the depot envs' 21 / 51 / 101 nodes
-    // (C = 6, 13, 26); everything else runs the run-time variant
-    constexpr bool T = ENV == EAMRL_ENV_TSP || ENV == EAMRL_ENV_CVRP;       // (the sibling envs: fewer instantiations)
-    if (a.M <= 32) {
-        if (T && C == 5) return launch_t<2, T ? 5 : 6, ENV>(a, S, st);
-        return C == 6 ? launch_t<2, 6, ENV>(a, S, st) : launch_t<2, 0, ENV>(a, S, st);
+    if constexpr (sizeof...(PA) > 0) {
+        if (a.M <= 32) return launch_t<2, 4 * 2, ENV, PA...>(a, S, st, pa...);       // CC = 4 RTT
+        if (a.M <= 64) return launch_t<4, 4 * 4, ENV, PA...>(a, S, st, pa...);
+        return launch_t<7, 4 * 7, ENV, PA...>(a, S, st, pa...);
+    } else {
+        const int C = (a.M + EAMRL_NCHUNK - 1) / EAMRL_NCHUNK;
+        constexpr bool T = ENV == EAMRL_ENV_TSP || ENV == EAMRL_ENV_CVRP;       // (the sibling envs: fewer instantiations)
+        if (a.M <= 32) {
+            if (T && C == 5) return launch_t<2, T ? 5 : 6, ENV>(a, S, st);
+            return C == 6 ? launch_t<2, 6, ENV>(a, S, st) : launch_t<2, 0, ENV>(a, S, st);
+        }
+        if (a.M <= 64) return C == 13 ? launch_t<4, 13, ENV>(a, S, st) : launch_t<4, 0, ENV>(a, S, st);
+        if (T && C == 25) return launch_t<7, T ? 25 : 26, ENV>(a, S, st);
+        return C == 26 ? launch_t<7, 26, ENV>(a, S, st) : launch_t<7, 0, ENV>(a, S, st);
     }
-    if (a.M <= 64) return C == 13 ? launch_t<4, 13, ENV>(a, S, st) : launch_t<4, 0, ENV>(a, S, st);
-    if (T && C == 25) return launch_t<7, T ? 25 : 26, ENV>(a, S, st);
-    return C == 26 ? launch_t<7, 26, ENV>(a, S, st) : launch_t<7, 0, ENV>(a, S, st);
 }
 
-// PolyNet: TSP and CVRP.  One instantiation per key-tile count: the glimpse's node chunks are the fixed [4 RTT g, 4 RTT (g + 1))
-// -- whole k-steps, nothing straddles -- for every M the tile count covers (slots beyond M carry zero weights and values).  The
-// run-time chunk length ceil(M / 4) of the plain kernel, which exists to reproduce the oracle's summation order bit for bit,
-// costs ~50 VGPRs that the weight stream needs (scratch otherwise); PolyNet is pinned to a float64 restatement instead.
-template <int RTT, int ENV>
-int launch_poly_t(const DecArgs& a, const PolyArgs& pn, int S, hipStream_t st)
+// the env switch (the extensions: TSP and CVRP) and, for the depot envs, the final state of the rows that finished early
+template <typename... PA>
+int launch_ms(int env, const DecArgs& a, hipStream_t st, const PA&... pa)
 {
-    const size_t lds = (size_t)RTT * 32 * 64 * sizeof(float);
-    auto k = k_rollout_ms_mfma<RTT, 4 * RTT, ENV, PolyArgs>;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return EAMRL_E_LAUNCH;
-    const int nqt = (S + 15) / 16;
-    int nsplit = a.B > 0 ? (int)(256 / a.B) : 1;
-    nsplit = nsplit < 1 ? 1 : (nsplit > nqt ? nqt : nsplit);
-    hipLaunchKernelGGL(k, dim3((unsigned)(a.B * nsplit)), dim3(512), lds, st, a, S, nsplit, pn);
+    const int S = (int)(a.R / a.B);
+    if (env == EAMRL_ENV_TSP) return launch_env_t<EAMRL_ENV_TSP>(a, S, st, pa...);
+    int rc;
+    if constexpr (sizeof...(PA) > 0)
+        rc = launch_env_t<EAMRL_ENV_CVRP>(a, S, st, pa...);
+    else
+        rc = env == EAMRL_ENV_CVRP ? launch_env_t<EAMRL_ENV_CVRP>(a, S, st)
+           : env == EAMRL_ENV_CVRPTW ? launch_env_t<EAMRL_ENV_CVRPTW>(a, S, st)
+           : env == EAMRL_ENV_PCTSP ? launch_env_t<EAMRL_ENV_PCTSP>(a, S, st)
+           : env == EAMRL_ENV_SDVRP ? launch_env_t<EAMRL_ENV_SDVRP>(a, S, st) : launch_env_t<EAMRL_ENV_OP>(a, S, st);
+    if (rc) return rc;
+    launch_rollout_pad(env, a, st);              // rows that finished early end at the depot (and PCTSP / OP get their step counters)
     return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
-}
-
-template <int ENV>
-int launch_poly_env_t(const DecArgs& a, const PolyArgs& pn, int S, hipStream_t st)
-{
-    if (a.M <= 32) return launch_poly_t<2, ENV>(a, pn, S, st);
-    if (a.M <= 64) return launch_poly_t<4, ENV>(a, pn, S, st);
-    return launch_poly_t<7, ENV>(a, pn, S, st);
-}
-
-// EAS-Lay: TSP and CVRP, one instantiation per key-tile count with PolyNet's fixed node chunks (the same register argument: the
-// run-time chunk length costs ~50 VGPRs next to the weight stream), so the captured heads are the plain kernel's to rounding, not
-// bit for bit.
-template <int RTT, int ENV>
-int launch_lay_t(const DecArgs& a, const LayArgs& ly, int S, hipStream_t st)
-{
-    const size_t lds = (size_t)RTT * 32 * 64 * sizeof(float);
-    auto k = k_rollout_ms_mfma<RTT, 4 * RTT, ENV, LayArgs>;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return EAMRL_E_LAUNCH;
-    const int nqt = (S + 15) / 16;
-    int nsplit = a.B > 0 ? (int)(256 / a.B) : 1;
-    nsplit = nsplit < 1 ? 1 : (nsplit > nqt ? nqt : nsplit);
-    hipLaunchKernelGGL(k, dim3((unsigned)(a.B * nsplit)), dim3(512), lds, st, a, S, nsplit, ly);
-    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
-}
-
-template <int ENV>
-int launch_lay_env_t(const DecArgs& a, const LayArgs& ly, int S, hipStream_t st)
-{
-    if (a.M <= 32) return launch_lay_t<2, ENV>(a, ly, S, st);
-    if (a.M <= 64) return launch_lay_t<4, ENV>(a, ly, S, st);
-    return launch_lay_t<7, ENV>(a, ly, S, st);
 }
 
 }  // namespace
@@ -1071,75 +1056,31 @@ extern "C" __attribute__((visibility("default"))) int eamrl_debug_read_ms_stamps
 }
 #endif
 
-// shape_only: the question eamrl_rollout_rng_native asks before the state exists (cache shape and row count alone)
-bool rollout_ms_mfma_supports(int env, const DecArgs& a, bool shape_only)
+// What the start-sharing kernel takes, from the cache shape, the row count and the filter settings alone (the pointers a rollout
+// needs are the caller's to require: rollout_call in abi.hip).
+bool rollout_ms_mfma_supports(int env, const DecArgs& a)
 {
     const bool sd = env == EAMRL_ENV_SDVRP;
     const bool depot_env = env == EAMRL_ENV_CVRP || env == EAMRL_ENV_CVRPTW || env == EAMRL_ENV_PCTSP || env == EAMRL_ENV_OP;
-    if (sd) {
-        if (g_debug[14] || a.E != ME || a.H != MH || a.M < 2 || a.M > 112 || a.ld % 4 != 0 || a.ld >= (1 << 24)) return false;
-        if (!shape_only && (!a.dyn || !a.rem || !a.used || !a.vcap)) return false;
-        if (a.R % a.B != 0 || a.R >= (1ll << 31)) return false;
-        const int64_t S = a.R / a.B;
-        return S >= 2 && S <= SMAX && a.top_k == 0 && !(a.top_p > 0.0 && a.top_p < 1.0);
-    }
-    if ((env != EAMRL_ENV_TSP && !depot_env) || a.E != ME || a.H != MH || a.M < 2 || a.M > 112 || a.ld % 4 != 0 || a.ld >= (1 << 24)) return false;
-    if (depot_env && (g_debug[14] || (!shape_only && (!a.visited || !a.used || !a.vcap || !a.demand)))) return false;
-    if (!shape_only && (env == EAMRL_ENV_OP || env == EAMRL_ENV_CVRPTW) && !a.locs) return false;
-    if (!shape_only && env == EAMRL_ENV_CVRPTW && (!a.time || !a.tw || !a.dur)) return false;
-    if (!shape_only && (env == EAMRL_ENV_PCTSP || env == EAMRL_ENV_OP) && !a.istep) return false;
-    if (a.R % a.B != 0 || a.R >= (1ll << 31)) return false;    // mul32w below
+    if ((env != EAMRL_ENV_TSP && !depot_env && !sd) || ((depot_env || sd) && g_debug[14])) return false;
+    if (a.E != ME || a.H != MH || a.M < 2 || a.M > 112 || a.ld % 4 != 0 || a.ld >= (1 << 24)) return false;
+    if (a.R % a.B != 0 || a.R >= (1ll << 31)) return false;    // mul32w in the kernel
     const int64_t S = a.R / a.B;
     return S >= 2 && S <= SMAX && a.top_k == 0 && !(a.top_p > 0.0 && a.top_p < 1.0);
 }
 
-int launch_rollout_ms_mfma(int env, const DecArgs& a, hipStream_t st)
+// the start-sharing kernel with an extension (PolyNet, EAS-Lay): TSP or CVRP
+bool rollout_ms_ext_supports(int env, const DecArgs& a)
 {
-    const int S = (int)(a.R / a.B);
-    const int C = (a.M + EAMRL_NCHUNK - 1) / EAMRL_NCHUNK;
-    if (env == EAMRL_ENV_TSP) return launch_env_t<EAMRL_ENV_TSP>(a, S, C, st);
-    const int rc = env == EAMRL_ENV_CVRP ? launch_env_t<EAMRL_ENV_CVRP>(a, S, C, st)
-                 : env == EAMRL_ENV_CVRPTW ? launch_env_t<EAMRL_ENV_CVRPTW>(a, S, C, st)
-                 : env == EAMRL_ENV_PCTSP ? launch_env_t<EAMRL_ENV_PCTSP>(a, S, C, st)
-                 : env == EAMRL_ENV_SDVRP ? launch_env_t<EAMRL_ENV_SDVRP>(a, S, C, st) : launch_env_t<EAMRL_ENV_OP>(a, S, C, st);
-    if (rc) return rc;
-    launch_rollout_pad(env, a, st);              // rows that finished early end at the depot (and PCTSP / OP get their step counters)
-    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
+    return (env == EAMRL_ENV_TSP || env == EAMRL_ENV_CVRP) && rollout_ms_mfma_supports(env, a);
 }
 
-// PolyNet rollouts: what the start-sharing kernel takes at all, TSP and CVRP only, no filters, no glimpse capture
-bool rollout_ms_poly_supports(int env, const DecArgs& a, bool shape_only)
+// One launch for the S <= 128 starts of `a`: the plain kernel, or with pn its PolyNet case (a.Lp = the unfolded logit key,
+// pn->s_off = the first start's index in the whole rollout), or with ly its EAS-Lay case.
+int launch_rollout_ms(int env, const DecArgs& a, const PolyArgs* pn, const LayArgs* ly, hipStream_t st)
 {
-    if (env != EAMRL_ENV_TSP && env != EAMRL_ENV_CVRP) return false;
-    return rollout_ms_mfma_supports(env, a, shape_only);
-}
-
-// one launch for the S <= 128 starts of `a` (a.Lp = the unfolded logit key); pn.s_off = the first start's index in the whole rollout
-int launch_rollout_ms_poly(int env, const DecArgs& a, const PolyArgs& pn, hipStream_t st)
-{
-    const int S = (int)(a.R / a.B);
-    if (env == EAMRL_ENV_TSP) return launch_poly_env_t<EAMRL_ENV_TSP>(a, pn, S, st);
-    const int rc = launch_poly_env_t<EAMRL_ENV_CVRP>(a, pn, S, st);
-    if (rc) return rc;
-    launch_rollout_pad(env, a, st);
-    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
-}
-
-// EAS-Lay rollouts: what the start-sharing kernel takes at all, TSP and CVRP only, no filters
-bool rollout_ms_lay_supports(int env, const DecArgs& a, bool shape_only)
-{
-    if (env != EAMRL_ENV_TSP && env != EAMRL_ENV_CVRP) return false;
-    return rollout_ms_mfma_supports(env, a, shape_only);
-}
-
-int launch_rollout_ms_lay(int env, const DecArgs& a, const LayArgs& ly, hipStream_t st)
-{
-    const int S = (int)(a.R / a.B);
-    if (env == EAMRL_ENV_TSP) return launch_lay_env_t<EAMRL_ENV_TSP>(a, ly, S, st);
-    const int rc = launch_lay_env_t<EAMRL_ENV_CVRP>(a, ly, S, st);
-    if (rc) return rc;
-    launch_rollout_pad(env, a, st);
-    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
+    if (!pn && !ly) return launch_ms(env, a, st);
+    return pn ? launch_ms(env, a, st, *pn) : launch_ms(env, a, st, *ly);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

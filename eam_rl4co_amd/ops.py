@@ -1586,13 +1586,18 @@ def decode_step(st: RolloutState, cache: DecodeCache, mode="greedy", noise=None,
     return action, logp, lps, lgs, status
 
 
+def _seed64(seed):
+    """A Python int seed as the uint64 the library takes (the low 64 bits)."""
+    return C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
 def exp1_noise(seed: int, R: int, T: int, M: int, device="cuda", seed_dev=None):
     """[R, T, M] Exp(1) draws of the library's counter-based generator (eamrl_exp1_noise): what a seeded rollout uses.
     seed_dev: optional int64 device tensor [1] XOR-ed into the seed on the device."""
     lib = _lib.load()
     out = torch.empty(R, T, M, dtype=torch.float32, device=device)
     _need_gpu(out, "noise")
-    _lib.check(lib.eamrl_exp1_noise(C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _ptr(seed_dev), _ptr(out), R, T, M,
+    _lib.check(lib.eamrl_exp1_noise(_seed64(seed), _ptr(seed_dev), _ptr(out), R, T, M,
                                     _stream(out)), "eamrl_exp1_noise")
     return out
 
@@ -1715,68 +1720,86 @@ def rollout(st: RolloutState, cache: DecodeCache, mode="greedy", noise=None, giv
     Sampling takes its Exp(1) noise from `noise` [R, T, M] or, with `seed` (XOR the device word `seed_dev`), from the counter-based
     generator -- in place where the kernel supports it (TSP multistart), else through a scratch tensor of the same draws.
     return_flags: info is int32[4] = (steps, status, 0, 0), the last two free for the caller's validity counters."""
-    lib = _lib.load()
     _validate_state(st, cache)
-    R, M, dev = st.R, st.M, st.mask.device
+    R, M = st.R, st.M
     if t_max is None:
         t_max = env_spec.max_steps(st.env_name, M)
     if mode == "sampling" and noise is None and seed is None:
         raise ValueError("rollout: sampling needs `noise` or `seed`")
-    if poly is not None:
-        if top_k or (0.0 < top_p < 1.0):
-            raise NotImplementedError("PolyNet rollout: top-k / top-p filtering is not built")
-        return _rollout_polynet(st, cache, poly, mode, noise, given, clip, temp, int(t_max), seed, seed_dev, return_flags)
-    if eas_layer is not None:
-        if top_k or (0.0 < top_p < 1.0):
-            raise NotImplementedError("EAS-Lay rollout: top-k / top-p filtering is not built")
-        return _rollout_eas_layer(st, cache, eas_layer, mode, noise, given, clip, temp, int(t_max), seed, seed_dev, return_flags,
-                                  want_heads)
-    if mode == "sampling" and noise is None:
-        if top_k or (0.0 < top_p < 1.0):
-            # the kernels that filter (register-resident FILT variant, streaming) read their noise from a tensor
-            noise = exp1_noise(seed, R, int(t_max), M, dev, seed_dev)
-        else:
-            actions, logps, info = _rollout_outputs(R, int(t_max), dev)
-            cs = cache.struct()
-            _capture_heads(st, cache, cs, R, t_max, want_heads)
-            ss = st.struct()
-            st.heads_out = None
-            native = lib.eamrl_rollout_rng_native(ENVS[st.env_name], C.byref(cs), R)
-            scratch = None if native else torch.empty(R, t_max, M, dtype=torch.float32, device=dev)
-            _lib.check(lib.eamrl_am_rollout_seeded(ENVS[st.env_name], C.byref(cs), C.byref(ss), R,
-                                                   C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _ptr(seed_dev), _ptr(scratch),
-                                                   float(clip),
-                                                   float(temp), int(t_max), _ptr(actions), _ptr(logps),
-                                                   C.c_void_p(info.data_ptr()), C.c_void_p(info.data_ptr() + 4),
-                                                   _stream(st.mask)), "eamrl_am_rollout_seeded")
-            return actions, logps, (info if return_flags else info[:2])
+    filtering = bool(top_k or (0.0 < top_p < 1.0))
+    ext = cs = None
+    if poly is not None or eas_layer is not None:
+        if filtering:
+            raise NotImplementedError(f"{'PolyNet' if poly is not None else 'EAS-Lay'} rollout: top-k / top-p filtering is not built")
+        cs = cache.struct()         # (the extension's shape is asked of the library before anything is allocated)
+        ext = _polynet_struct(st, cache, cs, poly) if poly is not None else _eas_layer_rollout_struct(st, cache, cs, eas_layer)
+    elif mode == "sampling" and noise is None and filtering:
+        # the kernels that filter (register-resident FILT variant, streaming) read their noise from a tensor
+        noise = exp1_noise(seed, R, int(t_max), M, st.mask.device, seed_dev)
+    noise, given, t_max, t_given = _rollout_inputs(noise, given, t_max, st.env_name, R, M)
+    return _rollout_launch(st, cache, cs, ext, mode, noise, given, t_given, clip, temp, t_max, top_k, top_p, seed, seed_dev,
+                           return_flags, want_heads and not filtering)
+
+
+def _rollout_inputs(noise, given, t_max, env_name, R, M):
+    """(noise, given, t_max, env, R, M) -> (noise, given, t_max, t_given) of a whole-rollout call: a noise tensor [R, T, M] sets
+    t_max = T; given actions [R, T'] set t_given = T' and, without noise on a depot env, bound t_max by it (a TSP tour has its
+    fixed length either way)."""
     t_given = 0
     if noise is not None:
         _chk(noise, "noise", torch.float32)
-        if noise.shape[0] != R or noise.shape[2] != M or noise.shape[1] < t_max:
-            if noise.shape[0] != R or noise.shape[2] != M:
-                raise ValueError("noise must be [R, T, M]")
-            t_max = noise.shape[1]
-        elif noise.shape[1] != t_max:
-            t_max = noise.shape[1]
+        if noise.dim() != 3 or noise.shape[0] != R or noise.shape[2] != M:
+            raise ValueError("noise must be [R, T, M]")
+        t_max = noise.shape[1]
     if given is not None:
         _chk(given, "given actions", torch.int64)
         if given.dim() != 2 or given.shape[0] != R:
             raise ValueError("given actions must be [R, T]")
         t_given = given.shape[1]
-        if noise is None:
-            t_max = min(t_max, t_given) if st.env_name != "tsp" else t_max
-    actions, logps, info = _rollout_outputs(R, int(t_max), dev)          # info: [steps, status, -, -]
-    cs = cache.struct()
-    _capture_heads(st, cache, cs, R, t_max, want_heads and not (top_k or (0.0 < top_p < 1.0)))
+        if noise is None and env_name != "tsp":
+            t_max = min(t_max, t_given)
+    return noise, given, int(t_max), t_given
+
+
+def _rollout_launch(st, cache, cs, ext, mode, noise, given, t_given, clip, temp, t_max, top_k, top_p, seed, seed_dev, return_flags,
+                    want_heads):
+    """The one launch path of `rollout`: outputs, the optional capture of the glimpse outputs, the state struct and the C call --
+    eamrl_am_rollout or, for sampling without a noise tensor, eamrl_am_rollout_seeded; with ext = an eamrl_polynet / eamrl_eas_layer
+    struct their PolyNet / EAS-Lay counterparts.  cs: the cache struct if the caller has built it already, else None."""
+    lib = _lib.load()
+    R = st.R
+    actions, logps, info = _rollout_outputs(R, t_max, st.mask.device)          # info: [steps, status, -, -]
+    if cs is None:
+        cs = cache.struct()
+    poly = ext if isinstance(ext, _lib.PolyNet) else None
+    if poly is not None:
+        st.heads = st.heads_out = None              # (the PolyNet case does not capture)
+    else:
+        _capture_heads(st, cache, cs, R, t_max, want_heads)
+        if ext is not None and want_heads and st.heads is None:
+            raise RuntimeError("EAS-Lay rollout: the buffer for the steps' glimpse outputs could not be had (see the log); the "
+                               "layer's backward has no path without it")
     ss = st.struct()
     st.heads_out = None
-    steps_ptr = C.c_void_p(info.data_ptr())
-    status_ptr = C.c_void_p(info.data_ptr() + 4)
-    _lib.check(lib.eamrl_am_rollout(ENVS[st.env_name], C.byref(cs), C.byref(ss), R, MODES[mode], _ptr(noise),
-                                    _ptr(given), t_given, float(clip), float(temp), int(top_k), float(top_p), int(t_max),
-                                    _ptr(actions),
-                                    _ptr(logps), steps_ptr, status_ptr, _stream(st.mask)), "eamrl_am_rollout")
+    seeded = mode == "sampling" and noise is None
+    seed64 = _seed64(seed if seeded else 0)
+    head = (ENVS[st.env_name], C.byref(cs), C.byref(ss)) + (() if ext is None else (C.byref(ext),))
+    tensors = (R, MODES[mode], _ptr(noise), _ptr(given), t_given)
+    tail = (float(clip), float(temp))
+    outs = (t_max, _ptr(actions), _ptr(logps), C.c_void_p(info.data_ptr()), C.c_void_p(info.data_ptr() + 4),
+            _stream(st.mask))
+    if ext is not None and poly is None:
+        name, args = "eamrl_am_rollout_eas_layer", head + tensors + (int(seeded), seed64, _ptr(seed_dev if seeded else None)) + tail + outs
+    elif poly is not None:
+        name, args = (("eamrl_am_rollout_polynet_seeded", head + (R, seed64, _ptr(seed_dev)) + tail + outs) if seeded else
+                      ("eamrl_am_rollout_polynet", head + tensors + tail + outs))
+    elif seeded:
+        native = lib.eamrl_rollout_rng_native(ENVS[st.env_name], C.byref(cs), R)
+        scratch = None if native else torch.empty(R, t_max, st.M, dtype=torch.float32, device=st.mask.device)
+        name, args = "eamrl_am_rollout_seeded", head + (R, seed64, _ptr(seed_dev), _ptr(scratch)) + tail + outs
+    else:
+        name, args = "eamrl_am_rollout", head + tensors + tail + (int(top_k), float(top_p)) + outs
+    _lib.check(getattr(lib, name)(*args), name)
     return actions, logps, (info if return_flags else info[:2])
 
 
@@ -1812,17 +1835,12 @@ def polynet_operands(Wout, W1, b1, W2, b2, binary_vectors):
 
 def rollout_polynet_supported(env_name, cache, R) -> bool:
     """Whether `rollout(..., poly=)` serves this env / cache shape / row count (eamrl_rollout_polynet_supported; host only)."""
-    if env_name not in ("tsp", "cvrp"):
-        return False
     cs = cache if isinstance(cache, _lib.Cache) else cache.struct()
-    return bool(_lib.load().eamrl_rollout_polynet_supported(ENVS[env_name], C.byref(cs), int(R)))
+    return bool(_lib.load().eamrl_rollout_polynet_supported(ENVS.get(env_name, -1), C.byref(cs), int(R)))
 
 
-def _rollout_polynet(st, cache, poly, mode, noise, given, clip, temp, t_max, seed, seed_dev, return_flags):
-    lib = _lib.load()
-    R, M, dev = st.R, st.M, st.mask.device
-    if cache.planes:
-        raise NotImplementedError("PolyNet rollout: graphs above 112 nodes are not built (plane-major cache)")
+def _polynet_struct(st, cache, cs, poly):
+    """eamrl_polynet of `rollout(..., poly=)`: the operands validated against the cache, the shape against the library."""
     for name in ("Wout", "W1", "ctab", "W2", "b2"):
         _chk(poly[name], f"poly[{name!r}]", torch.float32)
     E, k, P = cache.E, int(poly["k"]), int(poly["P"])
@@ -1831,42 +1849,14 @@ def _rollout_polynet(st, cache, poly, mode, noise, given, clip, temp, t_max, see
     if (poly["Wout"].numel(), poly["W1"].numel(), poly["W2"].numel(), poly["b2"].numel()) != (E * E, P * E, E * P, E) \
             or tuple(poly["ctab"].shape) != (k, P):
         raise ValueError("PolyNet rollout: operand shapes do not match the cache (ops.polynet_operands)")
-    cs = cache.struct()
-    if not lib.eamrl_rollout_polynet_supported(ENVS.get(st.env_name, -1), C.byref(cs), R):
-        raise NotImplementedError(f"PolyNet rollout: env {st.env_name!r} with {M} nodes and {R // cache.B} rows per instance is not "
-                                  "built: TSP / CVRP, at most 112 nodes, at least two rows per instance, embed_dim 128, 8 heads")
-    t_given = 0
-    if noise is not None:
-        _chk(noise, "noise", torch.float32)
-        if noise.dim() != 3 or noise.shape[0] != R or noise.shape[2] != M:
-            raise ValueError("noise must be [R, T, M]")
-        t_max = noise.shape[1]
-    if given is not None:
-        _chk(given, "given actions", torch.int64)
-        if given.dim() != 2 or given.shape[0] != R:
-            raise ValueError("given actions must be [R, T]")
-        t_given = given.shape[1]
-        if noise is None and st.env_name != "tsp":
-            t_max = min(t_max, t_given)
-    actions, logps, info = _rollout_outputs(R, int(t_max), dev)
-    st.heads = st.heads_out = None
-    ss = st.struct()
+    if not _lib.load().eamrl_rollout_polynet_supported(ENVS.get(st.env_name, -1), C.byref(cs), st.R):
+        raise NotImplementedError(f"PolyNet rollout: env {st.env_name!r} with {st.M} nodes and {st.R // cache.B} rows per instance is "
+                                  "not built: TSP / CVRP, at most 112 nodes, at least two rows per instance, embed_dim 128, 8 heads")
     ps = _lib.PolyNet()
     ps.Wout, ps.W1, ps.ctab, ps.W2, ps.b2 = (poly[n].data_ptr() for n in ("Wout", "W1", "ctab", "W2", "b2"))
     ps.L = cache.buf.data_ptr() + cache.slots["L"] * cache.E * 4
     ps.k, ps.P, ps.s_offset = k, P, 0
-    steps_ptr, status_ptr = C.c_void_p(info.data_ptr()), C.c_void_p(info.data_ptr() + 4)
-    if mode == "sampling" and noise is None:
-        _lib.check(lib.eamrl_am_rollout_polynet_seeded(ENVS[st.env_name], C.byref(cs), C.byref(ss), C.byref(ps), R,
-                                                       C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _ptr(seed_dev), float(clip),
-                                                       float(temp), int(t_max), _ptr(actions), _ptr(logps), steps_ptr, status_ptr,
-                                                       _stream(st.mask)), "eamrl_am_rollout_polynet_seeded")
-    else:
-        _lib.check(lib.eamrl_am_rollout_polynet(ENVS[st.env_name], C.byref(cs), C.byref(ss), C.byref(ps), R, MODES[mode],
-                                                _ptr(noise), _ptr(given), t_given, float(clip), float(temp), int(t_max),
-                                                _ptr(actions), _ptr(logps), steps_ptr, status_ptr, _stream(st.mask)),
-                   "eamrl_am_rollout_polynet")
-    return actions, logps, (info if return_flags else info[:2])
+    return ps
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -1909,10 +1899,8 @@ def eas_layer_operands(W1, b1, W2, b2, forced=None):
 
 def rollout_eas_layer_supported(env_name, cache, R) -> bool:
     """Whether `rollout(..., eas_layer=)` serves this env / cache shape / row count (eamrl_rollout_eas_layer_supported; host only)."""
-    if env_name not in ("tsp", "cvrp"):
-        return False
     cs = cache if isinstance(cache, _lib.Cache) else cache.struct()
-    return bool(_lib.load().eamrl_rollout_eas_layer_supported(ENVS[env_name], C.byref(cs), int(R)))
+    return bool(_lib.load().eamrl_rollout_eas_layer_supported(ENVS.get(env_name, -1), C.byref(cs), int(R)))
 
 
 def _eas_layer_struct(layer, B, E):
@@ -1925,19 +1913,11 @@ def _eas_layer_struct(layer, B, E):
     return ls
 
 
-def _rollout_eas_layer(st, cache, layer, mode, noise, given, clip, temp, t_max, seed, seed_dev, return_flags, want_heads):
-    lib = _lib.load()
-    R, M, dev = st.R, st.M, st.mask.device
-    if st.env_name not in ("tsp", "cvrp"):
-        raise NotImplementedError(f"EAS-Lay rollout: env {st.env_name!r} is not built (TSP and CVRP are)")
-    if cache.planes or M > KEY_CHUNK:
-        raise NotImplementedError(f"EAS-Lay rollout: graphs above {KEY_CHUNK} nodes are not built ({M} nodes)")
-    S = R // cache.B
-    if S < 2 or S > 128:
-        raise NotImplementedError(f"EAS-Lay rollout: 2 .. 128 rows per instance are built, not {S}")
-    cs = cache.struct()
-    if not lib.eamrl_rollout_eas_layer_supported(ENVS[st.env_name], C.byref(cs), R):
-        raise NotImplementedError("EAS-Lay rollout: this decoder shape is not built (embed_dim 128, 8 heads, 2 .. 112 nodes)")
+def _eas_layer_rollout_struct(st, cache, cs, layer):
+    """eamrl_eas_layer of `rollout(..., eas_layer=)`: the shape checked against the library, the layer and `forced` against the cache."""
+    if not _lib.load().eamrl_rollout_eas_layer_supported(ENVS.get(st.env_name, -1), C.byref(cs), st.R):
+        raise NotImplementedError(f"EAS-Lay rollout: env {st.env_name!r} with {st.M} nodes and {st.R // cache.B} rows per instance is "
+                                  f"not built: TSP / CVRP, 2 .. {KEY_CHUNK} nodes, 2 .. 128 rows per instance, embed_dim 128, 8 heads")
     ls = _eas_layer_struct(layer, cache.B, cache.E)
     forced = layer.get("forced")
     if forced is not None:
@@ -1945,34 +1925,7 @@ def _rollout_eas_layer(st, cache, layer, mode, noise, given, clip, temp, t_max, 
         if forced.dim() != 2 or forced.shape[0] != cache.B or forced.shape[1] < 1:
             raise ValueError("EAS-Lay: forced must be [B, t >= 1] int64")
         ls.forced, ls.t_forced = forced.data_ptr(), forced.shape[1]
-    t_given = 0
-    if noise is not None:
-        _chk(noise, "noise", torch.float32)
-        if noise.dim() != 3 or noise.shape[0] != R or noise.shape[2] != M:
-            raise ValueError("noise must be [R, T, M]")
-        t_max = noise.shape[1]
-    if given is not None:
-        _chk(given, "given actions", torch.int64)
-        if given.dim() != 2 or given.shape[0] != R:
-            raise ValueError("given actions must be [R, T]")
-        t_given = given.shape[1]
-        if noise is None and st.env_name != "tsp":
-            t_max = min(t_max, t_given)
-    actions, logps, info = _rollout_outputs(R, int(t_max), dev)
-    _capture_heads(st, cache, cs, R, t_max, want_heads)
-    if want_heads and st.heads is None:
-        raise RuntimeError("EAS-Lay rollout: the buffer for the steps' glimpse outputs could not be had (see the log); the layer's "
-                           "backward has no path without it")
-    ss = st.struct()
-    st.heads_out = None
-    seeded = mode == "sampling" and noise is None
-    _lib.check(lib.eamrl_am_rollout_eas_layer(ENVS[st.env_name], C.byref(cs), C.byref(ss), C.byref(ls), R, MODES[mode], _ptr(noise),
-                                              _ptr(given), t_given, int(seeded),
-                                              C.c_uint64((int(seed) if seeded else 0) & 0xFFFFFFFFFFFFFFFF),
-                                              _ptr(seed_dev if seeded else None), float(clip), float(temp), int(t_max), _ptr(actions),
-                                              _ptr(logps), C.c_void_p(info.data_ptr()), C.c_void_p(info.data_ptr() + 4),
-                                              _stream(st.mask)), "eamrl_am_rollout_eas_layer")
-    return actions, logps, (info if return_flags else info[:2])
+    return ls
 
 
 def raise_on_status(status: int):

@@ -191,25 +191,33 @@ class EAS:
 
     # ---- one iteration -----------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def _rollout(self, s: _State):
-        """Multistart sampling rollout on the adapted cache: what policy._enqueue does for one, on a given cache.
+    def _multistart_rollout(self, s: _State, extra_start=None, **rollout_kw):
+        """Multistart sampling rollout on the search's cache: what policy._enqueue does for one, on a given cache.  extra_start
+        [Ba]: one more row per instance behind the S multistart rows, starting there; rollout_kw goes to ops.rollout.
         -> actions [R, T] (start column included), logp [R, T], heads [R, >= T - 1, E] or None, reward [R]"""
         from .policy import _env_step_, _max_decode_steps, state_from_td
 
         pol, env = self.policy, self.env
-        st = state_from_td(pol.env_name, s.td, s.S)
-        start = env.select_start_nodes(s.td, num_starts=s.S).to(torch.int64).contiguous()
+        st = state_from_td(pol.env_name, s.td, s.S + (0 if extra_start is None else 1))
+        start = env.select_start_nodes(s.td, num_starts=s.S).to(torch.int64)
+        if extra_start is not None:
+            start = torch.cat((start, extra_start))
+        start = start.contiguous()
         _env_step_(st, start)
         t_max = int(max(1, _max_decode_steps(pol.env_name, s.M, 1)))
         seed = int(torch.randint(0, 2 ** 62, (1,), generator=s.gen).item())
-        acts, lps, info = ops.rollout(st, s.cache, "sampling", clip=pol.tanh_clipping, temp=pol.temperature, t_max=t_max,
-                                      seed=seed, want_heads=True)
+        acts, lps, info = ops.rollout(st, s.cache, "sampling", clip=pol.tanh_clipping, temp=pol.temperature, t_max=t_max, seed=seed,
+                                      want_heads=True, **rollout_kw)
         T, status = info.tolist()
         ops.raise_on_status(status)
         actions = torch.cat((start[:, None], acts[:, :T]), 1).contiguous()
         logp = torch.cat((torch.zeros_like(lps[:, :1]), lps[:, :T]), 1).contiguous()
         reward = env.get_reward(s.td, actions, check_solution=False)
-        return actions, logp, getattr(st, "heads", None), reward
+        return actions, logp, st.heads, reward
+
+    def _rollout(self, s: _State):
+        """The rollout of an iteration on the adapted cache."""
+        return self._multistart_rollout(s)
 
     def _plan(self, s: _State, actions, S: int, rollout_logp=None, rollout_heads=None):
         """A re-evaluation plan that reads the adapted cache in place."""
@@ -271,34 +279,14 @@ class EAS:
             d["forced"] = forced
         return d
 
-    @torch.no_grad()
     def _rollout_layer(self, s: _State):
         """One sampling rollout of S (+ 1 with an incumbent) rows per instance through the layer; the last row follows the incumbent.
-        -> actions [R, T] (start column included), logp [R, T], heads [R, >= T - 1, E] (pre-layer), reward [R], rows per instance"""
-        from .policy import _env_step_, _max_decode_steps, state_from_td
-
-        pol, env = self.policy, self.env
-        inc = s.best is not None
-        S1 = s.S + (1 if inc else 0)
-        st = state_from_td(pol.env_name, s.td, S1)
-        start = env.select_start_nodes(s.td, num_starts=s.S).to(torch.int64)
-        forced = None
-        if inc:
-            tour = s.best.repeat(s.n_aug, 1)                        # rows (a b) <- best[b]
-            start = torch.cat((start, tour[:, 0]))
-            forced = tour[:, 1:].contiguous()
-        start = start.contiguous()
-        _env_step_(st, start)
-        t_max = int(max(1, _max_decode_steps(pol.env_name, s.M, 1)))
-        seed = int(torch.randint(0, 2 ** 62, (1,), generator=s.gen).item())
-        acts, lps, info = ops.rollout(st, s.cache, "sampling", clip=pol.tanh_clipping, temp=pol.temperature, t_max=t_max, seed=seed,
-                                      want_heads=True, eas_layer=self._layer_operands(s, forced))
-        T, status = info.tolist()
-        ops.raise_on_status(status)
-        actions = torch.cat((start[:, None], acts[:, :T]), 1).contiguous()
-        logp = torch.cat((torch.zeros_like(lps[:, :1]), lps[:, :T]), 1).contiguous()
-        reward = env.get_reward(s.td, actions, check_solution=False)
-        return actions, logp, st.heads, reward, S1
+        -> `_multistart_rollout`'s tuple (heads: pre-layer) and the rows per instance"""
+        if s.best is None:
+            return self._multistart_rollout(s, eas_layer=self._layer_operands(s)) + (s.S,)
+        tour = s.best.repeat(s.n_aug, 1)                            # rows (a b) <- best[b]
+        forced = tour[:, 1:].contiguous()
+        return self._multistart_rollout(s, tour[:, 0], eas_layer=self._layer_operands(s, forced)) + (s.S + 1,)
 
     def _iteration_layer(self, s: _State, rollout=None) -> dict:
         actions, logp, heads, reward, S1 = rollout if rollout is not None else self._rollout_layer(s)
