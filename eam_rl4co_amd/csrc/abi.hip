@@ -824,8 +824,11 @@ static int rollout_call(const char* what, int env, const eamrl_cache* cache, con
         }
         return launched(kernel == EAMRL_KERNEL_RESIDENT ? launch_rollout_resident(env, a, st) : launch_rollout_stream(env, a, st), what);
     }
-    // the start-sharing kernel: one launch per 128 rows of an instance (only a PolyNet rollout has more than 128)
+    // the start-sharing kernel: one launch per 128 rows of an instance (only a PolyNet rollout has more than 128).  The launches
+    // of a split rollout share steps_out, which is final after the last one only: the rows that finished early are padded once,
+    // over all R rows, behind it (a pad per launch would leave a row at its customer that finished at its own launch's count)
     const int M = a.M;
+    const bool split = S > 128;
     for (int64_t s0 = 0; s0 < S; s0 += 128) {
         const int64_t Sc = S - s0 < 128 ? S - s0 : 128, r0 = s0 * B;
         DecArgs c = a;
@@ -843,8 +846,12 @@ static int rollout_call(const char* what, int env, const eamrl_cache* cache, con
         c.action = k.actions + r0 * k.t_max;
         c.logp = k.logps + r0 * k.t_max;
         pn.s_off = (k.poly ? k.poly->s_offset : 0) + (int)s0;
-        rc = launch_rollout_ms(env, c, k.ext == EXT_POLYNET ? &pn : nullptr, k.ext == EXT_EAS_LAYER ? &ly : nullptr, st);
+        rc = launch_rollout_ms(env, c, k.ext == EXT_POLYNET ? &pn : nullptr, k.ext == EXT_EAS_LAYER ? &ly : nullptr, !split, st);
         if (rc) return launched(rc, what);
+    }
+    if (split) {
+        launch_rollout_pad(env, a, st);
+        if (hipGetLastError() != hipSuccess) return launched(EAMRL_E_LAUNCH, what);
     }
     return 0;
 }

@@ -141,10 +141,11 @@ struct PolyArgs { const float* Wout; const float* W1; const float* ctab; const f
 // fragment order, [B][E * E] and [B][E]); forced [B][t_forced] or NULL = the picks of every instance's last row
 struct LayArgs { const float* W1; const float* b1; const float* W2; const float* b2; const int64_t* forced; int t_forced; };
 // the start-sharing kernel: shape predicates (cache shape, rows, filter; no pointer is read) and the launcher (pn / ly: at most
-// one of them, NULL for the plain kernel)
+// one of them, NULL for the plain kernel; pad: launch_rollout_pad follows the launch -- false for one launch of several that
+// share a steps_out, whose caller pads all rows once, after the last)
 bool rollout_ms_mfma_supports(int env, const DecArgs& a);
 bool rollout_ms_ext_supports(int env, const DecArgs& a);        // with an extension (PolyNet, EAS-Lay): TSP or CVRP
-int launch_rollout_ms(int env, const DecArgs& a, const PolyArgs* pn, const LayArgs* ly, hipStream_t st);
+int launch_rollout_ms(int env, const DecArgs& a, const PolyArgs* pn, const LayArgs* ly, bool pad, hipStream_t st);
 // EAS-Lay backward (eas_layer.hip): dW1 db1 dW2 db2 of eamrl_eas_layer from the rollout's heads and log-probs
 int launch_eas_layer_bwd(const ReevalArgs& a, const eamrl_eas_layer& ly, hipStream_t st);
 int launch_exp1_noise(uint64_t seed, const uint64_t* seed_dev, float* noise, int64_t R, int T, int M, hipStream_t st);

@@ -1023,9 +1023,9 @@ int launch_env_t(const DecArgs& a, int S, hipStream_t st, const PA&... pa)
     }
 }
 
-// the env switch (the extensions: TSP and CVRP) and, for the depot envs, the final state of the rows that finished early
+// the env switch (the extensions: TSP and CVRP) and, for the depot envs with `pad`, the final state of the rows that finished early
 template <typename... PA>
-int launch_ms(int env, const DecArgs& a, hipStream_t st, const PA&... pa)
+int launch_ms(int env, const DecArgs& a, bool pad, hipStream_t st, const PA&... pa)
 {
     const int S = (int)(a.R / a.B);
     if (env == EAMRL_ENV_TSP) return launch_env_t<EAMRL_ENV_TSP>(a, S, st, pa...);
@@ -1037,7 +1037,7 @@ int launch_ms(int env, const DecArgs& a, hipStream_t st, const PA&... pa)
            : env == EAMRL_ENV_CVRPTW ? launch_env_t<EAMRL_ENV_CVRPTW>(a, S, st)
            : env == EAMRL_ENV_PCTSP ? launch_env_t<EAMRL_ENV_PCTSP>(a, S, st)
            : env == EAMRL_ENV_SDVRP ? launch_env_t<EAMRL_ENV_SDVRP>(a, S, st) : launch_env_t<EAMRL_ENV_OP>(a, S, st);
-    if (rc) return rc;
+    if (rc || !pad) return rc;
     launch_rollout_pad(env, a, st);              // rows that finished early end at the depot (and PCTSP / OP get their step counters)
     return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
 }
@@ -1076,11 +1076,11 @@ bool rollout_ms_ext_supports(int env, const DecArgs& a)
 }
 
 // One launch for the S <= 128 starts of `a`: the plain kernel, or with pn its PolyNet case (a.Lp = the unfolded logit key,
-// pn->s_off = the first start's index in the whole rollout), or with ly its EAS-Lay case.
-int launch_rollout_ms(int env, const DecArgs& a, const PolyArgs* pn, const LayArgs* ly, hipStream_t st)
+// pn->s_off = the first start's index in the whole rollout), or with ly its EAS-Lay case.  pad: kernels.hpp.
+int launch_rollout_ms(int env, const DecArgs& a, const PolyArgs* pn, const LayArgs* ly, bool pad, hipStream_t st)
 {
-    if (!pn && !ly) return launch_ms(env, a, st);
-    return pn ? launch_ms(env, a, st, *pn) : launch_ms(env, a, st, *ly);
+    if (!pn && !ly) return launch_ms(env, a, pad, st);
+    return pn ? launch_ms(env, a, pad, st, *pn) : launch_ms(env, a, pad, st, *ly);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -1483,14 +1483,14 @@ class DecodeCache:
     def graph_context(self):
         return self.gctx if self.gctx is not None else 0
 
+    def slot_ptr(self, name):
+        """Address of the rows `name` (node 0 of instance 0; row stride ld floats) in either layout."""
+        return self.buf.data_ptr() + self.slots[name] * (self.B * self.M * self.E * 4 if self.planes else self.E * 4)
+
     def struct(self):
         c = _lib.Cache()
-        base, step = self.buf.data_ptr(), (self.B * self.M * self.E * 4 if self.planes else self.E * 4)
-        c.K = C.c_void_p(base + self.slots["K"] * step)
-        c.V = C.c_void_p(base + self.slots["V"] * step)
-        c.Lp = C.c_void_p(base + self.slots["Lp"] * step)
-        c.Pa = C.c_void_p(base + self.slots["Pa"] * step)
-        c.Pb = C.c_void_p(base + self.slots["Pb"] * step) if "Pb" in self.slots else None
+        c.K, c.V, c.Lp, c.Pa = (C.c_void_p(self.slot_ptr(n)) for n in ("K", "V", "Lp", "Pa"))
+        c.Pb = C.c_void_p(self.slot_ptr("Pb")) if "Pb" in self.slots else None
         c.cvec, c.gctx = _ptr(self.cvec), _ptr(self.gctx)
         c.ld, c.B, c.M, c.E, c.H = self.ld, self.B, self.M, self.E, self.H
         c.dyn = _ptr(self.dyn)
@@ -1854,7 +1854,7 @@ def _polynet_struct(st, cache, cs, poly):
                                   "not built: TSP / CVRP, at most 112 nodes, at least two rows per instance, embed_dim 128, 8 heads")
     ps = _lib.PolyNet()
     ps.Wout, ps.W1, ps.ctab, ps.W2, ps.b2 = (poly[n].data_ptr() for n in ("Wout", "W1", "ctab", "W2", "b2"))
-    ps.L = cache.buf.data_ptr() + cache.slots["L"] * cache.E * 4
+    ps.L = cache.slot_ptr("L")
     ps.k, ps.P, ps.s_offset = k, P, 0
     return ps
 

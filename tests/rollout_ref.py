@@ -20,6 +20,14 @@ after it is computed in the dtype of the cache: float64 is the reference, the fl
 `operands_of` turns a rollout's actions into the operands of reeval_ref.reeval; `run` adds the full log-prob vectors; `keys64`
 is the selection key; `rollout` is the decode loop on the restatement itself (the stand-in for a kernel on the CPU).
 `mutant` selects a deliberately wrong one-line variant (tests/test_host_rollout_ref.py shows that the case table sees each).
+
+The PolyNet pointer (`poly`, an argument of `run` and `rollout`, or the entry "poly" of the cache dict): the logits are formed
+from reeval_ref's heads as include/eamrl.h (eamrl_polynet) and the reference's nn/attention.py:519-556 define them,
+    g = heads Wout^T;  h = relu(W1[:, :E] g + W1[:, E:] z_j + b1);  y = g + (W2 h + b2);  u[n] = y . L[n] / sqrt(E)
+with L the UNFOLDED logit key (the entry "L" of the cache dict; the fold Lp = L Wout does not cover y) and z_j row
+j = (s_first + r // B) % k of the strategy table.  poly: dict of Wout [E, E], W1 [P, E + dz], b1 [P], W2 [E, P], b2 [E],
+Z [k, dz] (float32 tensors; everything after them is computed in the dtype of the run) and s_first (absent: 0).  Its own one-line
+mutants are POLY_MUTANTS (tests/test_host_polynet_arith.py shows that tests/polynet_cases.py sees each).
 One of reeval_ref's does not carry over: `rem_of_previous_step` changes nothing that a rollout can show.  A delivery either
 empties its node, which is masked from then on, or fills the vehicle, after which the depot is the only feasible node and the
 step after that starts from the depot with the same remaining demands; so the stale row only ever belongs to an infeasible node
@@ -41,6 +49,9 @@ OPERAND_MUTANTS = ("rem_of_previous_step", "rem_of_reset", "state_column_dropped
 LOGIT_MUTANTS = ("temperature_before_clip", "mask_before_clip")
 SELECT_MUTANTS = ("sampling_minus_noise", "tie_to_higher_index")
 MUTANTS = REEVAL_MUTANTS + OPERAND_MUTANTS + LOGIT_MUTANTS + SELECT_MUTANTS
+POLY_MUTANTS = ("strategy_of_r_mod_k", "s_first_ignored", "relu_dropped", "residual_g_dropped", "b2_dropped", "ctab_of_strategy_0",
+                "folded_Lp_for_L", "padded_slots_not_zero")                 # of the PolyNet pointer (run(..., poly=))
+LAUNCH_ROWS = 128           # rows of an instance per launch of the kernel: what `s_first_ignored` restarts the strategies at
 N_STATE_COLS = {"tsp": 1, "cvrp": 1, "sdvrp": 1, "pctsp": 1, "spctsp": 1, "op": 1, "cvrptw": 2, "pdp": 0}    # rows of cvec
 
 
@@ -88,6 +99,7 @@ def _assemble(cache, per_step, actions, S, tstart, clip, temp):
     """reeval_ref's operand dict from the per-step operands (a list over t) and the cache tensors."""
     st = lambda k: np.stack([p[k] for p in per_step], 1)              # [R, T, ...]
     op = {k: cache.get(k) for k in ("K", "V", "Lp", "Pa", "Pb", "gctx", "Cvec", "dyn")}
+    op.update({k: cache[k] for k in ("L", "poly") if cache.get(k) is not None})         # the PolyNet pointer's, where there is one
     op.update(mask=torch.from_numpy(st("mask")), idxA=torch.from_numpy(st("idxA")), actions=torch.from_numpy(np.asarray(actions, np.int64)),
               idxB=torch.from_numpy(st("idxB")) if per_step[0]["idxB"] is not None else None,
               sc=torch.from_numpy(np.stack([p["sc"] for p in per_step], 2)) if op["Cvec"] is not None else None,
@@ -116,13 +128,53 @@ def operands_of(cache, batch, actions, S, tstart=0, clip=10.0, temp=1.0, mutant=
     return op
 
 
-def run(op, dtype=torch.float64, mutant=None, chunk=64, rowwise=False):
+def polynet_y(heads, poly, B, mutant=None):
+    """y [R, T, E] of the PolyNet pointer from the glimpse outputs heads [R, T, E] (row r: strategy (s_first + r // B) % k), in
+    the dtype of `heads`; also the hidden pre-activations [R, T, P]."""
+    w = {n: poly[n].to(heads.dtype) for n in ("Wout", "W1", "b1", "W2", "b2", "Z")}
+    R = heads.shape[0]
+    k, s_first = w["Z"].shape[0], int(poly.get("s_first", 0))
+    s = torch.arange(R) // B
+    j = (s_first + s) % k
+    if mutant == "strategy_of_r_mod_k":
+        j = (s_first + torch.arange(R)) % k
+    elif mutant == "s_first_ignored":           # every launch of LAUNCH_ROWS rows per instance starts at strategy 0 again
+        j = (s % LAUNCH_ROWS) % k
+    elif mutant == "ctab_of_strategy_0":
+        j = torch.zeros_like(j)
+    g = heads @ w["Wout"].T
+    ctab = w["Z"] @ w["W1"][:, E:].T + w["b1"]                                  # [k, P]
+    pre = g @ w["W1"][:, :E].T + ctab[j][:, None, :]
+    h = pre if mutant == "relu_dropped" else torch.relu(pre)
+    res = h @ w["W2"].T
+    if mutant != "b2_dropped":
+        res = res + w["b2"]
+    return (res if mutant == "residual_g_dropped" else g + res), pre
+
+
+def _padded_to_key_tiles(part):
+    """`padded_slots_not_zero`: the glimpse runs over 16 ceil(M / 16) slots, the slots beyond M holding the last node's key,
+    value and feasibility."""
+    M = part["K"].shape[1]
+    pad = -M % 16
+    out = dict(part)
+    for k in ("K", "V", "Lp", "Pa", "Pb"):
+        if part.get(k) is not None:
+            out[k] = torch.cat([part[k], part[k][:, -1:].expand(-1, pad, -1)], 1)
+    out["mask"] = torch.cat([part["mask"], part["mask"][..., -1:].expand(-1, -1, pad)], -1)
+    return out
+
+
+def run(op, dtype=torch.float64, mutant=None, chunk=64, rowwise=False, poly=None):
     """reeval_ref.reeval on `op` in `dtype`, T-chunk by T-chunk (the steps are independent; SDVRP's per-step keys are large),
     plus `logp_all` [R, T, M]: the full log-prob vector of every step, -inf at the infeasible nodes.
     rowwise: u[n] is recomputed from the heads as one sum over the 128 products of node n alone, so that nodes with bit-identical
     rows get bit-identical logits whatever their position -- a property a matrix product of a BLAS does not have at the edge
-    columns, and one that `rollout`, standing in for a kernel, needs for its ties."""
-    assert mutant is None or mutant in MUTANTS
+    columns, and one that `rollout`, standing in for a kernel, needs for its ties.
+    poly (or op["poly"]): the PolyNet pointer (module text): u comes from y and op["L"]; the result gains `pre` [R, T, P]."""
+    poly = op.get("poly") if poly is None else poly
+    assert mutant is None or mutant in MUTANTS or (poly is not None and mutant in POLY_MUTANTS)
+    assert poly is None or (op.get("L") is not None and op.get("dyn") is None)
     T = op["actions"].shape[1]
     per_t = ("mask", "idxA", "idxB", "actions", "rem")
     outs = []
@@ -135,18 +187,23 @@ def run(op, dtype=torch.float64, mutant=None, chunk=64, rowwise=False):
             part["sc"] = op["sc"][:, :, t0:t0 + chunk]
         part["tstart"] = max(op["tstart"] - t0, 0)
         part = rr.cast(part, dtype)
-        r = rr.reeval(part, mutant if mutant in REEVAL_MUTANTS else None)
-        if rowwise:
-            R = part["actions"].shape[0]
-            inst = torch.arange(R) // op["S"] if mutant == "instance_r_div_S" else torch.arange(R) % part["K"].shape[0]
+        glimpse = _padded_to_key_tiles(part) if mutant == "padded_slots_not_zero" and part["K"].shape[1] % 16 else part
+        r = rr.reeval(glimpse, mutant if mutant in REEVAL_MUTANTS else None)
+        R, nB = part["actions"].shape[0], part["K"].shape[0]
+        inst = torch.arange(R) // op["S"] if mutant == "instance_r_div_S" else torch.arange(R) % nB
+        if poly is not None:
+            y, r["pre"] = polynet_y(r["heads"], poly, nB, mutant)
+            Lr = part["Lp" if mutant == "folded_Lp_for_L" else "L"][inst]
+            r["u"] = ((y[:, :, None, :] * Lr[:, None]).sum(-1) if rowwise else torch.einsum("rte,rne->rtn", y, Lr)) / math.sqrt(E)
+        elif rowwise:
             Lr = part["Lp"][inst][:, None]
             if part.get("dyn") is not None:
                 Lr = Lr + part["rem"][..., None] * part["dyn"][2]
             r["u"] = (r["heads"][:, :, None, :] * Lr).sum(-1) / math.sqrt(E)
         r["logp_all"] = logprob_rows(r["u"], part["mask"], op["clip"], op["temp"], mutant)
-        if mutant in LOGIT_MUTANTS or rowwise:
+        if mutant in LOGIT_MUTANTS or rowwise or poly is not None:
             r["logp"] = r["logp_all"].gather(-1, part["actions"][..., None]).squeeze(-1)
-        outs.append({k: r[k] for k in ("logp", "lse", "u", "logp_all", "heads")})
+        outs.append({k: r[k] for k in ("logp", "lse", "u", "logp_all", "heads") + (("pre",) if poly is not None else ())})
     return {k: torch.cat([o[k] for o in outs], 1) for k in outs[0]}
 
 
@@ -182,18 +239,19 @@ def select(key, mutant=None):
     return torch.argmax(key, dim=-1)
 
 
-def rollout(cache, batch, S, mode, noise=None, dtype=torch.float64, clip=10.0, temp=1.0, t_max=None, mutant=None):
+def rollout(cache, batch, S, mode, noise=None, dtype=torch.float64, clip=10.0, temp=1.0, t_max=None, mutant=None, poly=None):
     """The decode loop on the restatement: every row selects by `keys64` until all rows are done (rows that are done keep
-    selecting: their mask allows the depot only) or t_max steps are taken.  -> (actions [R, T] int64, logps [R, T] in `dtype`)."""
+    selecting: their mask allows the depot only) or t_max steps are taken.  -> (actions [R, T] int64, logps [R, T] in `dtype`).
+    poly: the PolyNet pointer, where the cache dict does not carry it."""
     env = str(batch["env"])
     states = step_ref.reset_rows(batch, S)
     prev = states
     acts, lps = [], []
     t = 0
     while not all(s["done"] for s in states) and (t_max is None or t < t_max):
-        p = step_operands(env, states, prev, mutant)
+        p = step_operands(env, states, prev, mutant if mutant in MUTANTS else None)
         op = _assemble(cache, [p], np.zeros((len(states), 1), np.int64), S, 0, clip, temp)
-        r = run(op, dtype, mutant, rowwise=True)
+        r = run(op, dtype, mutant, rowwise=True, poly=poly)
         key = keys64(r, mode, None if noise is None else noise[:, t:t + 1], mutant)[:, 0]
         a = select(key, mutant)
         acts.append(a)

@@ -67,12 +67,12 @@ def row_slots(env_name):
     return [f for f in env_spec.spec(env_name).fields if f.per_row]
 
 
-def upload(case, states):
+def upload(case, states, B=3):
     """ops.RolloutState holding the step_ref states (row r: instance r % B), per-instance tensors included."""
     from eam_rl4co_amd import ops
 
     env = env_spec.spec(case["env"]).name
-    R, M, B = len(states), case["M"], 3
+    R, M = len(states), case["M"]
     st = ops.RolloutState(env, R, M, DEV)
     st.mask = t(np.stack([s["mask"] for s in states]))
     st.done = t(np.array([s["done"] for s in states]))
