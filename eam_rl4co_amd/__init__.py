@@ -6,6 +6,7 @@ from .policy import (AttentionModelDecoder, AttentionModelEncoder, AttentionMode
                      GraphHeterogeneousAttentionEncoder, HeterogeneousAttentionModelPolicy, PolyNetDecoder, PolyNetPolicy,
                      SymNCOPolicy,
                      load_reference_checkpoint, random_policy, rollout)
+from .ptrnet import PointerNetworkPolicy  # noqa: F401
 from .attention import PointerAttention, PolyNetAttention, scaled_dot_product_attention  # noqa: F401
 from .evolution import EA, EACvrpDraws, EAPrizeDraws, EADraws, evolution_worker, generate_batch_population  # noqa: F401
 from .search import EAS, EASEmb, EASLay, eas_loss_coefficients  # noqa: F401

@@ -71,6 +71,17 @@ class State(C.Structure):
                 ("time", _vp), ("tw", _vp), ("dur", _vp), ("heads_out", _vp), ("to_deliver", _vp)]
 
 
+class PtrNet(C.Structure):
+    """struct eamrl_ptrnet"""
+    _fields_ = ([(n, _vp) for n in ("locs", "embedding", "enc_w_ih", "enc_w_hh", "enc_b_ih", "enc_b_hh", "dec_in0", "dec_w_ih",
+                                    "dec_w_hh", "dec_b_ih", "dec_b_hh", "g_v", "g_wq", "g_bq", "p_v", "p_wq", "p_bq", "ctx", "h", "c",
+                                    "e_g", "e_p", "ws")]
+                + [("B", _i64), ("N", C.c_int32), ("E", C.c_int32), ("H", C.c_int32), ("clip", _f32)])
+
+
+PTRNET_WS_FLOATS = 3584      # EAMRL_PTRNET_WS_FLOATS
+
+
 class EasLayer(C.Structure):
     """struct eamrl_eas_layer"""
     _fields_ = [("W1", _vp), ("b1", _vp), ("W2", _vp), ("b2", _vp), ("forced", _vp), ("t_forced", C.c_int32),
@@ -174,6 +185,9 @@ PROTOTYPES = {
                                _vp, C.c_size_t, _vp],
     "eamrl_ea_cvrp_run_large": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, C.c_double, C.c_double, C.c_double, _i32,
                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp],
+    "eamrl_ptrnet_encode": [C.POINTER(PtrNet), _vp],
+    "eamrl_ptrnet_rollout": [C.POINTER(PtrNet), _i32, _vp, _vp, _vp, _vp, _vp],
+    "eamrl_ptrnet_rollout_seeded": [C.POINTER(PtrNet), C.c_uint64, _vp, _vp, _vp],
     "eamrl_math_probe": [_i32, _vp, _vp, _i64, _vp],
     "eamrl_wave_probe": [_i32, _vp, _vp, _vp, _vp, _i64, _vp],
 }

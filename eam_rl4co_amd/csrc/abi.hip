@@ -1216,4 +1216,51 @@ __attribute__((visibility("default"))) int eamrl_ea_prize_run(int env, const flo
                                     mut_rand, mut_u, (hipStream_t)stream), "eamrl_ea_prize_run");
 }
 
+// Pointer Network: the shared checks of the three entry points (nothing is launched before they pass)
+static int ptrnet_check(const eamrl_ptrnet* p, const char* what)
+{
+    REQUIRE(p, what);
+    REQUIRE(p->N >= 2 && p->N <= 128, what);
+    REQUIRE(p->E == 128 && p->H == 128, what);
+    REQUIRE(p->B >= 0, what);
+    REQUIRE(p->locs && p->embedding && p->ws && p->h && p->c, what);
+    return 0;
+}
+
+__attribute__((visibility("default"))) int eamrl_ptrnet_encode(const eamrl_ptrnet* p, void* stream)
+{
+    if (int rc = ptrnet_check(p, "eamrl_ptrnet_encode")) return rc;
+    REQUIRE(p->enc_w_ih && p->enc_w_hh && p->enc_b_ih && p->enc_b_hh && p->ctx, "eamrl_ptrnet_encode");
+    return launched(launch_ptrnet_encode(*p, (hipStream_t)stream), "eamrl_ptrnet_encode");
+}
+
+static int ptrnet_rollout_check(const eamrl_ptrnet* p, const int64_t* actions, const float* logp, const char* what)
+{
+    if (int rc = ptrnet_check(p, what)) return rc;
+    REQUIRE(p->dec_in0 && p->dec_w_ih && p->dec_w_hh && p->dec_b_ih && p->dec_b_hh, what);
+    REQUIRE(p->g_v && p->g_wq && p->g_bq && p->p_v && p->p_wq && p->p_bq && p->e_g && p->e_p, what);
+    REQUIRE(p->clip > 0.0f, what);
+    REQUIRE(actions && logp, what);
+    return 0;
+}
+
+__attribute__((visibility("default"))) int eamrl_ptrnet_rollout(const eamrl_ptrnet* p, int mode, const float* noise,
+                                                               const int64_t* given, int64_t* actions, float* logp, void* stream)
+{
+    if (int rc = ptrnet_rollout_check(p, actions, logp, "eamrl_ptrnet_rollout")) return rc;
+    REQUIRE(mode == EAMRL_GREEDY || mode == EAMRL_SAMPLE || mode == EAMRL_EVALUATE, "eamrl_ptrnet_rollout");
+    REQUIRE(mode != EAMRL_SAMPLE || noise, "eamrl_ptrnet_rollout");
+    REQUIRE(mode != EAMRL_EVALUATE || given, "eamrl_ptrnet_rollout");
+    return launched(launch_ptrnet_rollout(*p, mode, noise, given, 0, 0, actions, logp, (hipStream_t)stream),
+                    "eamrl_ptrnet_rollout");
+}
+
+__attribute__((visibility("default"))) int eamrl_ptrnet_rollout_seeded(const eamrl_ptrnet* p, uint64_t seed, int64_t* actions,
+                                                                      float* logp, void* stream)
+{
+    if (int rc = ptrnet_rollout_check(p, actions, logp, "eamrl_ptrnet_rollout_seeded")) return rc;
+    return launched(launch_ptrnet_rollout(*p, EAMRL_SAMPLE, nullptr, nullptr, 1, seed, actions, logp, (hipStream_t)stream),
+                    "eamrl_ptrnet_rollout_seeded");
+}
+
 }  // extern "C"

@@ -173,5 +173,9 @@ int launch_ea_cvrp_large(const float* locs, const float* demand, const float* vc
 // TSP 2-opt local search, all sweeps in one launch (local_search.hip)
 int launch_tsp_two_opt(const float* locs, const float* distances, const int64_t* actions_in, int64_t* actions_out,
                        int32_t* iters, int32_t* status, int64_t B, int N, int max_iterations, hipStream_t st);
+// Pointer Network (ptrnet.hip): the encoder recurrence and the whole decode loop, one launch each (plus the weight fold)
+int launch_ptrnet_encode(const eamrl_ptrnet& p, hipStream_t st);
+int launch_ptrnet_rollout(const eamrl_ptrnet& p, int mode, const float* noise, const int64_t* given, int use_rng, uint64_t seed,
+                          int64_t* actions, float* logp, hipStream_t st);
 
 }  // namespace eamrl

@@ -1934,3 +1934,90 @@ def raise_on_status(status: int):
         raise AssertionError("Logits contain NaNs")                       # nn/attention.py:303-304
     if status & ST_INFEASIBLE:
         raise AssertionError("infeasible action selected")               # utils/decoding.py:397-399
+
+
+# ------------------------------------------------------------------------------------------------------
+# Pointer Network (csrc/ptrnet.hip)
+# ------------------------------------------------------------------------------------------------------
+PTRNET_WEIGHTS = {     # eamrl_ptrnet field -> (state-dict key, shape)
+    "embedding": ("embedding", (2, 128)), "dec_in0": ("decoder_in_0", (128,)),
+    "enc_w_ih": ("encoder.lstm.weight_ih_l0", (512, 128)), "enc_w_hh": ("encoder.lstm.weight_hh_l0", (512, 128)),
+    "enc_b_ih": ("encoder.lstm.bias_ih_l0", (512,)), "enc_b_hh": ("encoder.lstm.bias_hh_l0", (512,)),
+    "dec_w_ih": ("decoder.lstm.weight_ih", (512, 128)), "dec_w_hh": ("decoder.lstm.weight_hh", (512, 128)),
+    "dec_b_ih": ("decoder.lstm.bias_ih", (512,)), "dec_b_hh": ("decoder.lstm.bias_hh", (512,)),
+    "g_v": ("decoder.glimpse.v", (128,)), "g_wq": ("decoder.glimpse.project_query.weight", (128, 128)),
+    "g_bq": ("decoder.glimpse.project_query.bias", (128,)),
+    "p_v": ("decoder.pointer.v", (128,)), "p_wq": ("decoder.pointer.project_query.weight", (128, 128)),
+    "p_bq": ("decoder.pointer.project_query.bias", (128,)),
+}
+PTRNET_MAX_NODES = 128
+
+
+def _ptrnet_struct(locs, weights, clip):
+    """(struct, keep-alive list): eamrl_ptrnet over `locs` [B, N, 2] and `weights` (state-dict key -> fp32 device tensor)."""
+    _chk(locs, "locs", torch.float32)
+    if locs.dim() != 3 or locs.shape[2] != 2:
+        raise ValueError(f"ptrnet: locs must be [B, N, 2], got {tuple(locs.shape)}")
+    B, N, _ = locs.shape
+    if not 2 <= N <= PTRNET_MAX_NODES:
+        raise NotImplementedError(f"ptrnet: graphs of 2..{PTRNET_MAX_NODES} nodes are built, got {N}")
+    s = _lib.PtrNet()
+    keep = [locs]
+    s.locs = _ptr(locs)
+    for field, (key, shape) in PTRNET_WEIGHTS.items():
+        t = _chk(weights[key], key, torch.float32, shape)
+        keep.append(t)
+        setattr(s, field, _ptr(t))
+    s.B, s.N, s.E, s.H, s.clip = B, N, 128, 128, float(clip)
+    return s, keep
+
+
+def ptrnet_encode(locs, weights, ws=None):
+    """The Pointer Network encoder (eamrl_ptrnet_encode): nn.LSTM over the nodes 0..N-1 of x_n = locs_n @ embedding from the
+    zero state, all N steps in one launch.  -> ctx [B, N, 128], h [B, 128], c [B, 128], ws (the scratch the rollout call
+    takes again)."""
+    lib = _lib.load()
+    s, keep = _ptrnet_struct(locs, weights, 1.0)
+    B, N, _ = locs.shape
+    dev = locs.device
+    ctx = torch.empty(B, N, 128, device=dev, dtype=torch.float32)
+    h = torch.empty(B, 128, device=dev, dtype=torch.float32)
+    c = torch.empty(B, 128, device=dev, dtype=torch.float32)
+    ws = torch.empty(_lib.PTRNET_WS_FLOATS, device=dev, dtype=torch.float32) if ws is None else ws
+    s.ctx, s.h, s.c, s.ws = _ptr(ctx), _ptr(h), _ptr(c), _ptr(ws)
+    _lib.check(lib.eamrl_ptrnet_encode(C.byref(s), _stream(locs)), "eamrl_ptrnet_encode")
+    return ctx, h, c, ws
+
+
+def ptrnet_rollout(locs, weights, h, c, e_g, e_p, clip=10.0, mode="greedy", noise=None, given=None, seed=None, ws=None):
+    """The Pointer Network decode loop (eamrl_ptrnet_rollout[_seeded]), all N steps in one launch.  h, c: the encoder's final
+    state; e_g, e_p [B, N, 128]: project_ref of the glimpse / the pointer applied to ctx.  mode "sampling" takes noise
+    [B, N, N] (Exp(1) draws, [instance][step][node]) or a seed (the draws of exp1_noise(seed, B, N, N)); "evaluate" takes
+    given [B, N].  -> actions [B, N] int64, logp [B, N] (the chosen node's log-probability per step)."""
+    lib = _lib.load()
+    s, keep = _ptrnet_struct(locs, weights, clip)
+    B, N, _ = locs.shape
+    dev = locs.device
+    _chk(h, "h", torch.float32, (B, 128)), _chk(c, "c", torch.float32, (B, 128))
+    _chk(e_g, "e_g", torch.float32, (B, N, 128)), _chk(e_p, "e_p", torch.float32, (B, N, 128))
+    m = MODES[mode]
+    if m == SAMPLE and (noise is None) == (seed is None):
+        raise ValueError("ptrnet_rollout(mode='sampling') takes exactly one of noise= and seed=")
+    if m == SAMPLE and noise is not None:
+        _chk(noise, "noise", torch.float32, (B, N, N))
+    if m == EVALUATE:
+        if given is None:
+            raise ValueError("ptrnet_rollout(mode='evaluate') needs given=")
+        _chk(given, "given", torch.int64, (B, N))
+    ws = torch.empty(_lib.PTRNET_WS_FLOATS, device=dev, dtype=torch.float32) if ws is None else ws
+    actions = torch.empty(B, N, device=dev, dtype=torch.int64)
+    logp = torch.empty(B, N, device=dev, dtype=torch.float32)
+    s.h, s.c, s.e_g, s.e_p, s.ws = _ptr(h), _ptr(c), _ptr(e_g), _ptr(e_p), _ptr(ws)
+    if m == SAMPLE and noise is None:
+        _lib.check(lib.eamrl_ptrnet_rollout_seeded(C.byref(s), _seed64(seed), _ptr(actions), _ptr(logp), _stream(locs)),
+                   "eamrl_ptrnet_rollout_seeded")
+    else:
+        _lib.check(lib.eamrl_ptrnet_rollout(C.byref(s), m, _ptr(noise) if m == SAMPLE else None,
+                                            _ptr(given) if m == EVALUATE else None, _ptr(actions), _ptr(logp), _stream(locs)),
+                   "eamrl_ptrnet_rollout")
+    return actions, logp

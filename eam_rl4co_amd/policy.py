@@ -1619,6 +1619,8 @@ class GraphedRollout:
             raise NotImplementedError("GraphedRollout: step-wise / select_best / beam-search rollouts are not capturable")
         if isinstance(policy, PolyNetPolicy):
             raise NotImplementedError("GraphedRollout: capture of a PolyNet rollout has not been built or tested")
+        if getattr(policy, "is_ptrnet", False):
+            raise NotImplementedError("GraphedRollout: capture of a Pointer Network rollout has not been built or tested")
         self.policy, self.env = policy, env
         self.kw = dict(phase=phase, calc_reward=True, return_actions=True, return_entropy=False, return_hidden=False,
                        return_init_embeds=False, return_sum_log_likelihood=True, actions=None, max_steps=1_000_000)

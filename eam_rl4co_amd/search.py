@@ -111,6 +111,9 @@ class EAS:
         from .train import _NATIVE_ENVS
 
         assert use_eas_embedding or use_eas_layer, "At least one of `use_eas_embedding` or `use_eas_layer` must be True."
+        if getattr(policy, "is_ptrnet", False):
+            raise NotImplementedError("EAS: the Pointer Network policy has no cached embeddings or pointer layer to adapt; EAS is "
+                                      "not built for it")
         if use_eas_layer:
             if not all(p.is_cuda for p in policy.parameters()):
                 raise NotImplementedError("EAS-Lay: the per-instance layer runs inside the GPU rollout kernel and has no CPU path; "

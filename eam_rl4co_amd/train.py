@@ -1145,6 +1145,8 @@ def eam_am_loss(policy, env, td, ea, baseline, extra=None, improve: bool = True,
     it makes the effective baseline of a step with `extra` the batch mean of the stored values.
     baseline: a `baselines.REINFORCEBaseline` (e.g. get_reinforce_baseline("rollout") after setup) or a name.
     Returns dict(loss, reinforce_loss, bl_loss, bl_val, reward, log_likelihood, actions[, improved_*][, entropy])."""
+    if getattr(policy, "is_ptrnet", False):
+        raise NotImplementedError("eam_am_loss: the Pointer Network policy is not built into the EAM step; use reinforce_loss")
     bl, scaler = _resolve_baseline(baseline), _resolve_scaler(reward_scale)
     with shared_decoder_tensors(policy):        # one differentiable encoder pass for the sampled and the improved tours
         return _eam_am_loss(policy, env, td, ea, bl, scaler, extra, improve, draws, generator, return_entropy)
@@ -1479,6 +1481,9 @@ class PPOStep:
         from .critic import create_critic_from_actor
         from .dist import FlatGradBuffer, broadcast_module_state
 
+        if getattr(policy, "is_ptrnet", False):
+            raise NotImplementedError("PPOStep: the Pointer Network policy is not built into PPO (no critic from its encoder, no "
+                                      "entropy); train it with reinforce_loss / PolicyGradientStep")
         if getattr(policy.decoder, "is_polynet", False):
             raise NotImplementedError("PPOStep: a PolyNet policy has no re-evaluation with given actions (actions=) on this path")
         if critic is None:

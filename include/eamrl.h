@@ -932,6 +932,40 @@ int eamrl_math_probe(int fn, const uint32_t* x, uint32_t* y, int64_t n, void* st
 int eamrl_wave_probe(int fn, const uint32_t* v, const int32_t* idx, uint32_t* out_v, int32_t* out_i, int64_t nwaves,
                      void* stream);
 
+/* ---- Pointer Network (rl4co/models/zoo/ptrnet; TSP, E = H = 128, 2 <= N <= 128; csrc/ptrnet.hip) ---------------------------
+ * One struct for both entry points.  LSTM weights as torch stores them: w_ih, w_hh [512][128] (gate order i f g o), b_ih, b_hh
+ * [512].  An attention: v [128], wq [128][128] + bq [128] (project_query).  The ref projections e_g, e_p [B][N][128]
+ * (project_ref of ctx, bias included) are the caller's (two eamrl_linear calls on ctx).  ws: EAMRL_PTRNET_WS_FLOATS floats of
+ * device scratch (the folded input parts of the two LSTMs), shared by the two calls of one rollout.
+ * eamrl_ptrnet_encode: locs, embedding, enc_* -> ctx [B][N][128] (the hidden state after node n, node order 0 .. N - 1 from the
+ *   zero state) and the final h, c [B][128].  One launch for the recurrence (plus the weight fold).
+ * eamrl_ptrnet_rollout: h, c, e_g, e_p, dec_*, g_*, p_*, locs, embedding, clip -> actions [B][N] int64, logp [B][N] (the chosen
+ *   node's log-probability per step).  mode EAMRL_GREEDY (first maximum) / EAMRL_SAMPLE (argmax of p / noise, noise [B][N][N]
+ *   Exp(1) draws indexed [instance][step][node]) / EAMRL_EVALUATE (given [B][N]; an entry outside 0 .. N - 1 is clamped, a
+ *   visited node gives -inf).  One launch for the whole decode loop (plus the weight fold), no host synchronisation.
+ * eamrl_ptrnet_rollout_seeded: EAMRL_SAMPLE with the draws eamrl_exp1_noise(seed, NULL, noise, B, N, N) writes, bit for bit.
+ * All: -1 (eamrl_last_error names the function) on NULL struct / pointers, N outside 2 .. 128, E or H != 128, clip <= 0. */
+#define EAMRL_PTRNET_WS_FLOATS 3584
+typedef struct eamrl_ptrnet {
+    const float* locs;
+    const float* embedding;
+    const float* enc_w_ih; const float* enc_w_hh; const float* enc_b_ih; const float* enc_b_hh;
+    const float* dec_in0;
+    const float* dec_w_ih; const float* dec_w_hh; const float* dec_b_ih; const float* dec_b_hh;
+    const float* g_v; const float* g_wq; const float* g_bq;
+    const float* p_v; const float* p_wq; const float* p_bq;
+    float* ctx; float* h; float* c;
+    const float* e_g; const float* e_p;
+    float* ws;
+    int64_t B;
+    int32_t N, E, H;
+    float clip;
+} eamrl_ptrnet;
+int eamrl_ptrnet_encode(const eamrl_ptrnet* p, void* stream);
+int eamrl_ptrnet_rollout(const eamrl_ptrnet* p, int mode, const float* noise, const int64_t* given, int64_t* actions, float* logp,
+                         void* stream);
+int eamrl_ptrnet_rollout_seeded(const eamrl_ptrnet* p, uint64_t seed, int64_t* actions, float* logp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
