@@ -12,21 +12,19 @@
 // "any / all" reductions are wave ballots, and the tour length uses the canonical lane tree.
 // The step, mask and replay kernels walk the rows in this layout; the comparisons and transitions they apply (capacity
 // epsilon, window, prize, arrival limit, split delivery, end of a tour, the leg) are the functions of env_rule.hpp.
-// The k_check_* kernels restate check_solution_validity, whose own tolerances stay here.
-#include "kernels.hpp"
-#include "env_rule.hpp"
+// What a wavefront computes about a row lives in tour_row.hpp, once each: the row it owns (wave_row), the chunked lane-tree
+// sum, the closed tour length, the seen-bitmap (SeenBits), the in-order log-prob sum and the CVRP load replay, and the launch
+// (launch_rows).  The reward and k_check_* kernels are thin bodies over those; the k_check_* kernels restate
+// check_solution_validity, whose own rules and tolerances stay here.
+#include "tour_row.hpp"
 
 namespace eamrl {
-
-constexpr int EB = 256;          // threads per block
-constexpr int ROWS_PER_BLOCK = EB / 64;
 
 __global__ __launch_bounds__(EB) void k_tsp_step(uint8_t* mask, int64_t* first, int64_t* cur, int64_t* istep,
                                                  const int64_t* action, uint8_t* done, int64_t R, int N)
 {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
-    if (r >= R) return;
+    const auto [lane, wv, r, live] = wave_row(R);
+    if (!live) return;
     const int64_t a = action[r];
     uint8_t* m = mask + r * N;
     int any = 0;
@@ -92,9 +90,8 @@ __global__ __launch_bounds__(EB) void k_cvrp_step_mask(uint8_t* visited, float* 
                                                        const float* demand, int64_t* cur, const int64_t* action,
                                                        uint8_t* mask, uint8_t* done, int64_t R, int64_t B, int N)
 {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
-    if (r >= R) return;
+    const auto [lane, wv, r, live] = wave_row(R);
+    if (!live) return;
     cvrp_step_mask_row<STEP>(visited, used, vcap, demand, cur, mask, done, N, r, r % B, lane, STEP ? action[r] : (int64_t)-1);
 }
 
@@ -104,9 +101,8 @@ __global__ __launch_bounds__(EB) void k_sdvrp_step_mask(float* rem, float* used,
                                                         const int64_t* action, uint8_t* mask, uint8_t* done, int64_t R,
                                                         int M)
 {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
-    if (r >= R) return;
+    const auto [lane, wv, r, live] = wave_row(R);
+    if (!live) return;
     float* rr = rem + r * M;
     float u = used[r];
     const float cap = vcap[r];
@@ -149,9 +145,8 @@ __global__ __launch_bounds__(EB) void k_check_sdvrp(const int64_t* actions, cons
                                                     int64_t R, int64_t B, int N, int T, int32_t* bad)
 {
     extern __shared__ float dem_all[];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t r = (int64_t)blockIdx.x * ROWS_PER_BLOCK + wv;
-    if (r >= R) return;
+    const auto [lane, wv, r, live] = wave_row(R);
+    if (!live) return;
     const int M = N + 1;
     float* d = dem_all + (size_t)wv * M;
     const float cap = vcap[r];
@@ -236,9 +231,8 @@ __global__ __launch_bounds__(EB) void k_op_step_mask(uint8_t* visited, float* to
                                                      const int64_t* action, uint8_t* mask, uint8_t* done, int64_t R,
                                                      int64_t B, int M)
 {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
-    if (r >= R) return;
+    const auto [lane, wv, r, live] = wave_row(R);
+    if (!live) return;
     op_step_mask_row<STEP>(visited, tour_len, prize_tot, prize, locs, maxlen, cur, istep, mask, done, M, r, r % B, lane, STEP ? action[r] : (int64_t)-1);
 }
 
@@ -301,9 +295,8 @@ __global__ __launch_bounds__(EB) void k_cvrptw_step_mask(uint8_t* visited, float
                                                          const float* tw, const float* dur, const int64_t* action,
                                                          uint8_t* mask, uint8_t* done, int64_t R, int64_t B, int N)
 {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
-    if (r >= R) return;
+    const auto [lane, wv, r, live] = wave_row(R);
+    if (!live) return;
     cvrptw_step_mask_row<STEP>(visited, used, vcap, demand, cur, time, locs, tw, dur, mask, done, N, r, r % B, lane, STEP ? action[r] : (int64_t)-1);
 }
 
@@ -336,19 +329,11 @@ __global__ void k_check_cvrptw_time(const int64_t* actions, const float* locs, c
 __global__ __launch_bounds__(EB) void k_op_reward(const float* prize, const int64_t* actions, float* reward, int64_t R,
                                                   int64_t B, int M, int T)
 {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
-    if (r >= R) return;
+    const auto [lane, wv, r, live] = wave_row(R);
+    if (!live) return;
     const float* pz = prize + (r % B) * (int64_t)M;
     const int64_t* act = actions + r * T;
-    float total = 0.0f;
-    for (int b0 = 0; b0 < T; b0 += 64) {
-        const int t = b0 + lane;
-        int64_t a = t < T ? act[t] : 0;
-        a = a < 0 ? 0 : (a >= M ? M - 1 : a);
-        const float s = wave_tree_sum(t < T ? pz[a] : 0.0f);
-        total = (b0 == 0) ? s : total + s;
-    }
+    const float total = chunked_tree_sum(T, lane, [&](int t) { return pz[clamp_node(act[t], M)]; });
     if (lane == 0) reward[r] = total;
 }
 
@@ -357,32 +342,21 @@ __global__ __launch_bounds__(EB) void k_check_op(const int64_t* actions, const f
                                                  int64_t B, int M, int T, int32_t* bad)
 {
     __shared__ uint32_t seen_all[ROWS_PER_BLOCK][128];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t r = (int64_t)blockIdx.x * ROWS_PER_BLOCK + wv;
-    if (r >= R) return;
-    uint32_t* seen = seen_all[wv];
-    for (int i = lane; i < 128; i += 64) seen[i] = 0;
-    __builtin_amdgcn_wave_barrier();
+    const auto [lane, wv, r, live] = wave_row(R);
+    if (!live) return;
+    const SeenBits seen{seen_all[wv]};
+    seen.clear(128, lane);
     const int64_t* act = actions + r * T;
     const float* L = locs + (r % B) * (int64_t)M * 2;
     int bad_lane = 0;
-    float length = 0.0f;
-    for (int b0 = 0; b0 < T; b0 += 64) {
-        const int t = b0 + lane;
-        float d = 0.0f;
-        if (t < T) {
-            int64_t a0 = act[t], a1 = act[(t + 1 == T) ? 0 : t + 1];
-            if (a0 < 0 || a0 >= M) { bad_lane = 1; a0 = 0; }
-            else if (a0 != 0) {
-                const uint32_t bit = 1u << (a0 & 31);
-                if (atomicOr(&seen[a0 >> 5], bit) & bit) bad_lane = 1;
-            }
-            a1 = a1 < 0 ? 0 : (a1 >= M ? M - 1 : a1);
-            d = rule::leg(L[2 * a1], L[2 * a1 + 1], L[2 * a0], L[2 * a0 + 1]);
-        }
-        const float s = wave_tree_sum(d);
-        length = (b0 == 0) ? s : length + s;
-    }
+    // the closed length over the actions, marking each step's node on the way: a customer twice is invalid, the depot may repeat
+    const float length = chunked_tree_sum(T, lane, [&](int t) {
+        int64_t a0 = act[t], a1 = act[(t + 1 == T) ? 0 : t + 1];      // both loads before the mark
+        if (a0 < 0 || a0 >= M) { bad_lane = 1; a0 = 0; }
+        else if (a0 != 0 && seen.mark(a0)) bad_lane = 1;
+        a1 = clamp_node(a1, M);
+        return rule::leg(L[2 * a1], L[2 * a1 + 1], L[2 * a0], L[2 * a0 + 1]);
+    });
     const bool invalid = __ballot(bad_lane != 0) != 0ull;
     int ex = 0;
     const float* ml = maxlen + (r % B) * (int64_t)M;
@@ -442,9 +416,8 @@ __global__ __launch_bounds__(EB) void k_pctsp_step_mask(uint8_t* visited, float*
                                                         int64_t* istep, const int64_t* action, uint8_t* mask,
                                                         uint8_t* done, int64_t R, int64_t B, int M)
 {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
-    if (r >= R) return;
+    const auto [lane, wv, r, live] = wave_row(R);
+    if (!live) return;
     pctsp_step_mask_row<STEP>(visited, prize_tot, pen_tot, prize, penalty, cur, istep, mask, done, M, r, r % B, lane, STEP ? action[r] : (int64_t)-1);
 }
 
@@ -454,20 +427,17 @@ __global__ __launch_bounds__(EB) void k_check_pctsp(const int64_t* actions, cons
                                                     int T, int32_t* bad)
 {
     __shared__ uint32_t seen_all[ROWS_PER_BLOCK][128];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t r = (int64_t)blockIdx.x * ROWS_PER_BLOCK + wv;
-    if (r >= R) return;
-    uint32_t* seen = seen_all[wv];
-    for (int i = lane; i < 128; i += 64) seen[i] = 0;
-    __builtin_amdgcn_wave_barrier();
+    const auto [lane, wv, r, live] = wave_row(R);
+    if (!live) return;
+    const SeenBits seen{seen_all[wv]};
+    seen.clear(128, lane);
     const int64_t* act = actions + r * T;
-    int bad_lane = 0, cnt = 0;
+    int bad_lane = 0, cnt = 0;      // cnt: distinct customers
     for (int t = lane; t < T; t += 64) {
         const int64_t a = act[t];
         if (a < 0 || a >= M) { bad_lane = 1; continue; }
         if (a == 0) continue;
-        const uint32_t bit = 1u << (a & 31);
-        if (atomicOr(&seen[a >> 5], bit) & bit) bad_lane = 1;
+        if (seen.mark(a)) bad_lane = 1;
         else ++cnt;
     }
     const bool invalid = __ballot(bad_lane != 0) != 0ull;
@@ -485,51 +455,15 @@ __global__ __launch_bounds__(EB) void k_check_pctsp(const int64_t* actions, cons
 __global__ __launch_bounds__(EB) void k_tour_length(const float* locs, const int64_t* actions, float* reward, int64_t R,
                                                     int64_t B, int M, int T, int with_depot, const float* penalty)
 {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
-    if (r >= R) return;
+    const auto [lane, wv, r, live] = wave_row(R);
+    if (!live) return;
     const float* L = locs + (r % B) * (int64_t)M * 2;
     const int64_t* act = actions + r * T;
-    const int P = T + (with_depot ? 1 : 0);
-    float total = 0.0f;
-    for (int b0 = 0; b0 < P; b0 += 64) {
-        const int t = b0 + lane;
-        float d = 0.0f;
-        if (t < P) {
-            int64_t a0, a1;
-            if (with_depot) {
-                a0 = (t == 0) ? 0 : act[t - 1];
-                a1 = (t + 1 == P) ? 0 : act[t];
-            } else {
-                a0 = act[t];
-                a1 = act[(t + 1 == P) ? 0 : t + 1];
-            }
-            // caller-supplied tours: keep the gather inside the instance whatever the indices are
-            a0 = a0 < 0 ? 0 : (a0 >= M ? M - 1 : a0);
-            a1 = a1 < 0 ? 0 : (a1 >= M ? M - 1 : a1);
-            const float2 p0 = *reinterpret_cast<const float2*>(L + 2 * a0);
-            const float2 p1 = *reinterpret_cast<const float2*>(L + 2 * a1);
-            const float dx = p1.x - p0.x, dy = p1.y - p0.y;
-            d = __builtin_sqrtf(fma_(dy, dy, dx * dx));
-        }
-        const float s = wave_tree_sum(d);
-        total = (b0 == 0) ? s : total + s;
-    }
+    const float total = closed_tour_length(L, act, T, M, with_depot != 0, lane);
     if (penalty) {
         const float* pen = penalty + (r % B) * (int64_t)M;
-        float saved = 0.0f, all = 0.0f;
-        for (int b0 = 0; b0 < T; b0 += 64) {
-            const int t = b0 + lane;
-            int64_t a = t < T ? act[t] : 0;
-            a = a < 0 ? 0 : (a >= M ? M - 1 : a);
-            const float s = wave_tree_sum(t < T ? pen[a] : 0.0f);
-            saved = (b0 == 0) ? s : saved + s;
-        }
-        for (int b0 = 0; b0 < M - 1; b0 += 64) {
-            const int n = b0 + lane;
-            const float s = wave_tree_sum(n < M - 1 ? pen[1 + n] : 0.0f);
-            all = (b0 == 0) ? s : all + s;
-        }
+        const float saved = chunked_tree_sum(T, lane, [&](int t) { return pen[clamp_node(act[t], M)]; });
+        const float all = chunked_tree_sum(M - 1, lane, [&](int n) { return pen[1 + n]; });
         if (lane == 0) reward[r] = saved - (total + all);
         return;
     }
@@ -608,52 +542,6 @@ __global__ __launch_bounds__(256) void k_beam_topk(const float* logprobs, const 
     }
 }
 
-// One wavefront per row; "seen" bitmap in LDS (M <= 4096).
-__global__ __launch_bounds__(EB) void k_check_solution(int env, const int64_t* actions, const float* demand,
-                                                       const float* vcap, int64_t R, int64_t B, int N, int T,
-                                                       int32_t* bad)
-{
-    __shared__ uint32_t seen_all[ROWS_PER_BLOCK][128];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t r = (int64_t)blockIdx.x * ROWS_PER_BLOCK + wv;
-    if (r >= R) return;
-    uint32_t* seen = seen_all[wv];
-    for (int i = lane; i < 128; i += 64) seen[i] = 0;
-    __builtin_amdgcn_wave_barrier();
-    const int64_t* act = actions + r * T;
-    const int top = (env == EAMRL_ENV_TSP) ? N - 1 : N;  // highest legal node id
-    int bad_lane = 0;
-    for (int t = lane; t < T; t += 64) {
-        const int64_t a = act[t];
-        if (a < 0 || a > top) { bad_lane = 1; continue; }
-        if (env == EAMRL_ENV_CVRP && a == 0) continue;
-        const uint32_t bit = 1u << (a & 31);
-        const uint32_t old = atomicOr(&seen[a >> 5], bit);
-        if (old & bit) bad_lane = 1;  // visited twice
-    }
-    __builtin_amdgcn_wave_barrier();
-    const int lo = (env == EAMRL_ENV_TSP) ? 0 : 1;
-    for (int n = lo + lane; n <= top; n += 64)
-        if (!((seen[n >> 5] >> (n & 31)) & 1u)) bad_lane = 1;  // never visited
-    const bool invalid = __ballot(bad_lane != 0) != 0ull;
-    if (lane != 0) return;
-    if (invalid) { atomicAdd(&bad[0], 1); return; }
-    if (env == EAMRL_ENV_CVRP) {
-        // running load, depot resets it (cvrp/env.py:172-185)
-        const float cap = vcap[r], lim = cap + 1e-5f;
-        const float* dem = demand + (r % B) * N;
-        float usedc = 0.0f;
-        int over = 0;
-        for (int t = 0; t < T; ++t) {
-            const int64_t a = act[t];
-            usedc = usedc + ((a == 0) ? -cap : dem[a - 1]);
-            if (usedc < 0.0f) usedc = 0.0f;
-            if (usedc > lim) over = 1;
-        }
-        if (over) atomicAdd(&bad[1], 1);
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // The env state BEFORE every decode step of given action rows, in one launch (depot envs; TSP is closed-form in the
 // actions: k_tsp_mask_bits): a wavefront keeps its row's state in LDS and alternates "record" (mask as a 128-bit set,
@@ -675,9 +563,8 @@ __global__ __launch_bounds__(EB) void k_replay_states(ReplayArgs a)
     __shared__ uint8_t s_mask[ROWS_PER_BLOCK][SLOTS], s_vis[ROWS_PER_BLOCK][SLOTS], s_done[ROWS_PER_BLOCK][8];
     __shared__ float s_used[ROWS_PER_BLOCK], s_time[ROWS_PER_BLOCK];
     __shared__ int64_t s_cur[ROWS_PER_BLOCK], s_istep[ROWS_PER_BLOCK];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t r = (int64_t)blockIdx.x * ROWS_PER_BLOCK + wv;
-    if (r >= a.R) return;
+    const auto [lane, wv, r, live] = wave_row(a.R);
+    if (!live) return;
     const int M = a.M, T = a.T;
     const int64_t bi = r % a.B;
     for (int n = lane; n < SLOTS; n += 64) {
@@ -746,9 +633,8 @@ __global__ __launch_bounds__(EB) void k_replay_sdvrp(const float* __restrict__ r
                                                      int32_t* __restrict__ idxA, float* __restrict__ sc, float* __restrict__ rem_out,
                                                      int64_t R, int M, int T)
 {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
-    if (r >= R) return;
+    const auto [lane, wv, r, live] = wave_row(R);
+    if (!live) return;
     const int n0 = lane, n1 = lane + 64;
     float r0 = n0 < M ? rem[r * M + n0] : 0.0f, r1 = n1 < M ? rem[r * M + n1] : 0.0f;
     float u = used[r];
@@ -791,9 +677,8 @@ __global__ __launch_bounds__(EB) void k_replay_sdvrp_big(const float* __restrict
                                                          int64_t R, int M, int T)
 {
     __shared__ uint8_t s_ok[ROWS_PER_BLOCK][1024];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t r = (int64_t)blockIdx.x * ROWS_PER_BLOCK + wv;
-    if (r >= R) return;
+    const auto [lane, wv, r, live] = wave_row(R);
+    if (!live) return;
     const int nkc = (M + 111) / 112;
     float rr[16];
 #pragma unroll
@@ -849,119 +734,69 @@ __global__ __launch_bounds__(EB) void k_replay_sdvrp_big(const float* __restrict
 int launch_replay_sdvrp(const float* rem, const float* used, const float* vcap, const int64_t* cur, const int64_t* actions,
                         uint32_t* bits, int32_t* idxA, float* sc, float* rem_out, int64_t R, int M, int T, hipStream_t st)
 {
-    if (M > 112) {
-        hipLaunchKernelGGL(k_replay_sdvrp_big, dim3((unsigned)((R + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK)), dim3(EB), 0, st, rem, used,
-                           vcap, cur, actions, bits, idxA, sc, rem_out, R, M, T);
-        return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
-    }
-    hipLaunchKernelGGL(k_replay_sdvrp, dim3((unsigned)((R + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK)), dim3(EB), 0, st, rem, used, vcap, cur, actions, bits, idxA, sc, rem_out,
+    return launch_rows(M > 112 ? k_replay_sdvrp_big : k_replay_sdvrp, R, st, rem, used, vcap, cur, actions, bits, idxA, sc, rem_out,
                        R, M, T);
-    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
+}
+
+// TSPEnv / CVRPEnv.check_solution_validity of a row (M <= 4096 nodes): every node (CVRP: every customer; the depot may repeat)
+// exactly once, then the CVRP load.  bad[0] += rows that fail the first, bad[1] += valid rows whose load exceeds the capacity.
+__device__ __forceinline__ void check_tsp_cvrp_row(SeenBits seen, const int64_t* act, int T, int M, bool with_depot,
+                                                   const float* dem, const float* cap_r, int32_t* bad, int lane)
+{
+    seen.clear(128, lane);
+    int bad_lane = 0;
+    for (int t = lane; t < T; t += 64) {
+        const int64_t a = act[t];
+        if (a < 0 || a >= M) { bad_lane = 1; continue; }
+        if (with_depot && a == 0) continue;
+        if (seen.mark(a)) bad_lane = 1;
+    }
+    bad_lane |= seen.misses(with_depot ? 1 : 0, M - 1, lane);
+    if (__ballot(bad_lane != 0) != 0ull) {
+        if (lane == 0) atomicAdd(&bad[0], 1);
+        return;
+    }
+    if (with_depot) {
+        const float cap = *cap_r;
+        if (cvrp_overloaded(act, dem, cap, cap + 1e-5f, T, lane) && lane == 0) atomicAdd(&bad[1], 1);
+    }
+}
+
+__global__ __launch_bounds__(EB) void k_check_solution(int env, const int64_t* actions, const float* demand,
+                                                       const float* vcap, int64_t R, int64_t B, int N, int T,
+                                                       int32_t* bad)
+{
+    __shared__ uint32_t seen_all[ROWS_PER_BLOCK][128];
+    const auto [lane, wv, r, live] = wave_row(R);
+    if (!live) return;
+    const bool with_depot = env != EAMRL_ENV_TSP;
+    check_tsp_cvrp_row(SeenBits{seen_all[wv]}, actions + r * T, T, with_depot ? N + 1 : N, with_depot,
+                       with_depot ? demand + (r % B) * N : nullptr, vcap + r, bad, lane);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Rollout epilogue in one launch (TSP / CVRP): reward (k_tour_length), validity (k_check_solution) and the log-likelihood
-// (k_sum_logp) of a row by one wavefront, in exactly the orders of the three kernels it replaces.
+// Rollout epilogue in one launch (TSP / CVRP): the reward, the log-likelihood (in the order of k_sum_logp) and the validity
+// (the row function of k_check_solution) of a row by one wavefront; each output is optional.
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(EB) void k_rollout_finish(int env, const float* locs, const int64_t* actions, const float* logp,
                                                        int64_t ld, const float* demand, const float* vcap, float* reward,
                                                        float* ll, int32_t* bad, int64_t R, int64_t B, int M, int T)
 {
     __shared__ uint32_t seen_all[ROWS_PER_BLOCK][128];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t r = (int64_t)blockIdx.x * ROWS_PER_BLOCK + wv;
-    if (r >= R) return;
-    const int with_depot = env != EAMRL_ENV_TSP;
-    const float* L = locs + (r % B) * (int64_t)M * 2;
+    const auto [lane, wv, r, live] = wave_row(R);
+    if (!live) return;
+    const bool with_depot = env != EAMRL_ENV_TSP;
     const int64_t* act = actions + r * T;
-    // ---- tour length: lane tree over the legs --------------------------------------------------------------------------
+    const int64_t bi = r % B;
     if (reward) {
-        const int P = T + with_depot;
-        float total = 0.0f;
-        for (int b0 = 0; b0 < P; b0 += 64) {
-            const int t = b0 + lane;
-            float d = 0.0f;
-            if (t < P) {
-                int64_t a0, a1;
-                if (with_depot) {
-                    a0 = (t == 0) ? 0 : act[t - 1];
-                    a1 = (t + 1 == P) ? 0 : act[t];
-                } else {
-                    a0 = act[t];
-                    a1 = act[(t + 1 == P) ? 0 : t + 1];
-                }
-                a0 = a0 < 0 ? 0 : (a0 >= M ? M - 1 : a0);
-                a1 = a1 < 0 ? 0 : (a1 >= M ? M - 1 : a1);
-                const float2 p0 = *reinterpret_cast<const float2*>(L + 2 * a0);
-                const float2 p1 = *reinterpret_cast<const float2*>(L + 2 * a1);
-                const float dx = p1.x - p0.x, dy = p1.y - p0.y;
-                d = __builtin_sqrtf(fma_(dy, dy, dx * dx));
-            }
-            const float s = wave_tree_sum(d);
-            total = (b0 == 0) ? s : total + s;
-        }
-        if (lane == 0) reward[r] = -total;
+        const float length = closed_tour_length(locs + bi * (int64_t)M * 2, act, T, M, with_depot, lane);
+        if (lane == 0) reward[r] = -length;
     }
-    // ---- log-likelihood: strictly sequential over the steps --------------------------------------------------------------
     if (ll) {
-        float s = 0.0f;
-        for (int t0 = 0; t0 < T; t0 += 64) {
-            const float v = (t0 + lane < T) ? logp[r * ld + t0 + lane] : 0.0f;
-            const int tn = T - t0 < 64 ? T - t0 : 64;
-#pragma unroll
-            for (int t = 0; t < 64; ++t)
-                if (t < tn) s = s + __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), t));
-        }
+        const float s = sum_in_order(logp + r * ld, T, lane);
         if (lane == 0) ll[r] = s;
     }
-    // ---- validity ---------------------------------------------------------------------------------------------------------
-    if (!bad) return;
-    uint32_t* seen = seen_all[wv];
-    for (int i = lane; i < 128; i += 64) seen[i] = 0;
-    __builtin_amdgcn_wave_barrier();
-    const int N = with_depot ? M - 1 : M;
-    const int top = with_depot ? N : N - 1;
-    int bad_lane = 0;
-    for (int t = lane; t < T; t += 64) {
-        const int64_t a = act[t];
-        if (a < 0 || a > top) { bad_lane = 1; continue; }
-        if (with_depot && a == 0) continue;
-        const uint32_t bit = 1u << (a & 31);
-        const uint32_t old = atomicOr(&seen[a >> 5], bit);
-        if (old & bit) bad_lane = 1;
-    }
-    __builtin_amdgcn_wave_barrier();
-    for (int n = with_depot + lane; n <= top; n += 64)
-        if (!((seen[n >> 5] >> (n & 31)) & 1u)) bad_lane = 1;
-    const bool invalid = __ballot(bad_lane != 0) != 0ull;
-    if (invalid) {
-        if (lane == 0) atomicAdd(&bad[0], 1);
-        return;
-    }
-    if (with_depot) {
-        // running load, depot resets it (cvrp/env.py:172-185): strictly sequential over the steps; the 64 load changes of
-        // a block are fetched by the lanes at once and consumed in step order through v_readlane (every lane the same chain)
-        const float cap = vcap[r], lim = cap + 1e-5f;
-        const float* dem = demand + (r % B) * N;
-        float usedc = 0.0f;
-        int over = 0;
-        for (int t0 = 0; t0 < T; t0 += 64) {
-            float delta = 0.0f;
-            if (t0 + lane < T) {
-                const int64_t a = act[t0 + lane];
-                delta = (a == 0) ? -cap : dem[a - 1];
-            }
-            const int tn = T - t0 < 64 ? T - t0 : 64;
-#pragma unroll
-            for (int t = 0; t < 64; ++t)
-                if (t < tn) {
-                    usedc = usedc + __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, delta), t));
-                    if (usedc < 0.0f) usedc = 0.0f;
-                    if (usedc > lim) over = 1;
-                }
-        }
-        if (over && lane == 0) atomicAdd(&bad[1], 1);
-    }
+    if (bad) check_tsp_cvrp_row(SeenBits{seen_all[wv]}, act, T, M, with_depot, demand + bi * (M - 1), vcap + r, bad, lane);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -985,50 +820,32 @@ __global__ __launch_bounds__(256) void k_multi_copy(MultiCopyArgs a)
     for (int64_t i = (nv << 4) + i0; i < n; i += stride) dst[i] = src ? src[i] : (char)0;
 }
 
-static inline unsigned row_blocks(int64_t R) { return (unsigned)((R + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK); }
-
+// The step launchers pick STEP once: 1 (transition, then mask) with an action, 0 (mask only) without.
 int launch_tsp_step(uint8_t* mask, int64_t* first, int64_t* cur, int64_t* istep, const int64_t* action,
                     uint8_t* done, int64_t R, int N, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_tsp_step, dim3(row_blocks(R)), dim3(EB), 0, st, mask, first, cur, istep, action, done, R, N);
-    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
+    return launch_rows(k_tsp_step, R, st, mask, first, cur, istep, action, done, R, N);
 }
 
 int launch_cvrp(int step, uint8_t* visited, float* used, const float* vcap, const float* demand, int64_t* cur,
                 const int64_t* action, uint8_t* mask, uint8_t* done, int64_t R, int64_t B, int N, hipStream_t st)
 {
-    if (step)
-        hipLaunchKernelGGL(k_cvrp_step_mask<1>, dim3(row_blocks(R)), dim3(EB), 0, st, visited, used, vcap, demand, cur,
-                           action, mask, done, R, B, N);
-    else
-        hipLaunchKernelGGL(k_cvrp_step_mask<0>, dim3(row_blocks(R)), dim3(EB), 0, st, visited, used, vcap, demand, cur,
-                           action, mask, done, R, B, N);
-    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
+    return launch_rows(step ? k_cvrp_step_mask<1> : k_cvrp_step_mask<0>, R, st, visited, used, vcap, demand, cur, action, mask,
+                       done, R, B, N);
 }
 
 int launch_sdvrp(float* rem, float* used, const float* vcap, int64_t* cur, const int64_t* action, uint8_t* mask,
                  uint8_t* done, int64_t R, int M, hipStream_t st)
 {
-    if (action)
-        hipLaunchKernelGGL(k_sdvrp_step_mask<1>, dim3(row_blocks(R)), dim3(EB), 0, st, rem, used, vcap, cur, action, mask,
-                           done, R, M);
-    else
-        hipLaunchKernelGGL(k_sdvrp_step_mask<0>, dim3(row_blocks(R)), dim3(EB), 0, st, rem, used, vcap, cur, action, mask,
-                           done, R, M);
-    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
+    return launch_rows(action ? k_sdvrp_step_mask<1> : k_sdvrp_step_mask<0>, R, st, rem, used, vcap, cur, action, mask, done, R, M);
 }
 
 int launch_cvrptw(uint8_t* visited, float* used, const float* vcap, const float* demand, int64_t* cur, float* time,
                   const float* locs, const float* tw, const float* dur, const int64_t* action, uint8_t* mask, uint8_t* done,
                   int64_t R, int64_t B, int N, hipStream_t st)
 {
-    if (action)
-        hipLaunchKernelGGL(k_cvrptw_step_mask<1>, dim3(row_blocks(R)), dim3(EB), 0, st, visited, used, vcap, demand, cur, time,
-                           locs, tw, dur, action, mask, done, R, B, N);
-    else
-        hipLaunchKernelGGL(k_cvrptw_step_mask<0>, dim3(row_blocks(R)), dim3(EB), 0, st, visited, used, vcap, demand, cur, time,
-                           locs, tw, dur, action, mask, done, R, B, N);
-    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
+    return launch_rows(action ? k_cvrptw_step_mask<1> : k_cvrptw_step_mask<0>, R, st, visited, used, vcap, demand, cur, time, locs,
+                       tw, dur, action, mask, done, R, B, N);
 }
 
 int launch_cvrptw_check(const int64_t* actions, const float* locs, const float* tw, const float* dur, int64_t R, int64_t B,
@@ -1043,48 +860,34 @@ int launch_op(uint8_t* visited, float* tour_len, float* prize_tot, const float* 
               int64_t* cur, int64_t* istep, const int64_t* action, uint8_t* mask, uint8_t* done, int64_t R, int64_t B, int M,
               hipStream_t st)
 {
-    if (action)
-        hipLaunchKernelGGL(k_op_step_mask<1>, dim3(row_blocks(R)), dim3(EB), 0, st, visited, tour_len, prize_tot, prize, locs,
-                           maxlen, cur, istep, action, mask, done, R, B, M);
-    else
-        hipLaunchKernelGGL(k_op_step_mask<0>, dim3(row_blocks(R)), dim3(EB), 0, st, visited, tour_len, prize_tot, prize, locs,
-                           maxlen, cur, istep, action, mask, done, R, B, M);
-    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
+    return launch_rows(action ? k_op_step_mask<1> : k_op_step_mask<0>, R, st, visited, tour_len, prize_tot, prize, locs, maxlen,
+                       cur, istep, action, mask, done, R, B, M);
 }
 
 int launch_op_reward(const float* prize, const int64_t* actions, float* reward, int64_t R, int64_t B, int M, int T,
                      hipStream_t st)
 {
-    hipLaunchKernelGGL(k_op_reward, dim3(row_blocks(R)), dim3(EB), 0, st, prize, actions, reward, R, B, M, T);
-    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
+    return launch_rows(k_op_reward, R, st, prize, actions, reward, R, B, M, T);
 }
 
 int launch_op_check(const int64_t* actions, const float* locs, const float* maxlen, int64_t R, int64_t B, int M, int T,
                     int32_t* bad, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_check_op, dim3(row_blocks(R)), dim3(EB), 0, st, actions, locs, maxlen, R, B, M, T, bad);
-    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
+    return launch_rows(k_check_op, R, st, actions, locs, maxlen, R, B, M, T, bad);
 }
 
 int launch_pctsp(uint8_t* visited, float* prize_tot, float* pen_tot, const float* prize, const float* penalty, int64_t* cur,
                  int64_t* istep, const int64_t* action, uint8_t* mask, uint8_t* done, int64_t R, int64_t B, int M,
                  hipStream_t st)
 {
-    if (action)
-        hipLaunchKernelGGL(k_pctsp_step_mask<1>, dim3(row_blocks(R)), dim3(EB), 0, st, visited, prize_tot, pen_tot, prize,
-                           penalty, cur, istep, action, mask, done, R, B, M);
-    else
-        hipLaunchKernelGGL(k_pctsp_step_mask<0>, dim3(row_blocks(R)), dim3(EB), 0, st, visited, prize_tot, pen_tot, prize,
-                           penalty, cur, istep, action, mask, done, R, B, M);
-    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
+    return launch_rows(action ? k_pctsp_step_mask<1> : k_pctsp_step_mask<0>, R, st, visited, prize_tot, pen_tot, prize, penalty,
+                       cur, istep, action, mask, done, R, B, M);
 }
 
 int launch_tour_length(const float* locs, const int64_t* actions, float* reward, int64_t R, int64_t B, int M, int T,
                        int with_depot, hipStream_t st, const float* penalty)
 {
-    hipLaunchKernelGGL(k_tour_length, dim3(row_blocks(R)), dim3(EB), 0, st, locs, actions, reward, R, B, M, T, with_depot,
-                       penalty);
-    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
+    return launch_rows(k_tour_length, R, st, locs, actions, reward, R, B, M, T, with_depot, penalty);
 }
 
 int launch_sum_logp(const float* logp, int64_t ld, float* out, int64_t R, int T, hipStream_t st)
@@ -1099,27 +902,21 @@ int launch_replay_states(int env, const uint8_t* mask, const uint8_t* visited, c
                          int64_t R, int64_t B, int M, int T, hipStream_t st)
 {
     ReplayArgs a{mask, visited, used, vcap, cur, istep, time, demand, locs, tw, dur, actions, bits, idxA, sc, R, B, M, T};
-    const dim3 grid(row_blocks(R)), block(EB);
-    if (M > 112) {              // the chunked mask layout (graphs above 112 nodes)
-        if (env == EAMRL_ENV_CVRP) hipLaunchKernelGGL((k_replay_states<EAMRL_ENV_CVRP, 1024>), grid, block, 0, st, a);
-        else if (env == EAMRL_ENV_CVRPTW) hipLaunchKernelGGL((k_replay_states<EAMRL_ENV_CVRPTW, 1024>), grid, block, 0, st, a);
-        else if (env == EAMRL_ENV_PCTSP) hipLaunchKernelGGL((k_replay_states<EAMRL_ENV_PCTSP, 1024>), grid, block, 0, st, a);
-        else if (env == EAMRL_ENV_OP) hipLaunchKernelGGL((k_replay_states<EAMRL_ENV_OP, 1024>), grid, block, 0, st, a);
-    } else if (env == EAMRL_ENV_CVRP) hipLaunchKernelGGL(k_replay_states<EAMRL_ENV_CVRP>, grid, block, 0, st, a);
-    else if (env == EAMRL_ENV_CVRPTW) hipLaunchKernelGGL(k_replay_states<EAMRL_ENV_CVRPTW>, grid, block, 0, st, a);
-    else if (env == EAMRL_ENV_PCTSP) hipLaunchKernelGGL(k_replay_states<EAMRL_ENV_PCTSP>, grid, block, 0, st, a);
-    else if (env == EAMRL_ENV_OP) hipLaunchKernelGGL(k_replay_states<EAMRL_ENV_OP>, grid, block, 0, st, a);
+    const bool big = M > 112;   // the chunked mask layout (graphs above 112 nodes)
+    void (*k)(ReplayArgs);
+    if (env == EAMRL_ENV_CVRP) k = big ? k_replay_states<EAMRL_ENV_CVRP, 1024> : k_replay_states<EAMRL_ENV_CVRP>;
+    else if (env == EAMRL_ENV_CVRPTW) k = big ? k_replay_states<EAMRL_ENV_CVRPTW, 1024> : k_replay_states<EAMRL_ENV_CVRPTW>;
+    else if (env == EAMRL_ENV_PCTSP) k = big ? k_replay_states<EAMRL_ENV_PCTSP, 1024> : k_replay_states<EAMRL_ENV_PCTSP>;
+    else if (env == EAMRL_ENV_OP) k = big ? k_replay_states<EAMRL_ENV_OP, 1024> : k_replay_states<EAMRL_ENV_OP>;
     else return EAMRL_E_ARG;
-    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
+    return launch_rows(k, R, st, a);
 }
 
 int launch_rollout_finish(int env, const float* locs, const int64_t* actions, const float* logp, int64_t ld, const float* demand,
                           const float* vcap, float* reward, float* ll, int32_t* bad, int64_t R, int64_t B, int M, int T,
                           hipStream_t st)
 {
-    hipLaunchKernelGGL(k_rollout_finish, dim3(row_blocks(R)), dim3(EB), 0, st, env, locs, actions, logp, ld, demand, vcap, reward,
-                       ll, bad, R, B, M, T);
-    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
+    return launch_rows(k_rollout_finish, R, st, env, locs, actions, logp, ld, demand, vcap, reward, ll, bad, R, B, M, T);
 }
 
 int launch_multi_copy(int n, const void* const* src, void* const* dst, const int64_t* bytes, hipStream_t st)
@@ -1156,10 +953,7 @@ int launch_check_solution(int env, const int64_t* actions, const float* demand, 
                           int N, int T, int32_t* bad, hipStream_t st)
 {
     if (N + 1 > 4096) return EAMRL_E_ARG;
-    if (env == EAMRL_ENV_PCTSP) {       // demand = real_prize [B][N+1]
-        hipLaunchKernelGGL(k_check_pctsp, dim3(row_blocks(R)), dim3(EB), 0, st, actions, demand, R, B, N + 1, T, bad);
-        return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
-    }
+    if (env == EAMRL_ENV_PCTSP) return launch_rows(k_check_pctsp, R, st, actions, demand, R, B, N + 1, T, bad);      // real_prize [B][N+1]
     if (env == EAMRL_ENV_SDVRP) {
         const size_t lds = (size_t)ROWS_PER_BLOCK * (N + 1) * sizeof(float);
         if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(k_check_sdvrp),
@@ -1168,8 +962,7 @@ int launch_check_solution(int env, const int64_t* actions, const float* demand, 
         hipLaunchKernelGGL(k_check_sdvrp, dim3(row_blocks(R)), dim3(EB), lds, st, actions, demand, vcap, R, B, N, T, bad);
         return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
     }
-    hipLaunchKernelGGL(k_check_solution, dim3(row_blocks(R)), dim3(EB), 0, st, env, actions, demand, vcap, R, B, N, T, bad);
-    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
+    return launch_rows(k_check_solution, R, st, env, actions, demand, vcap, R, B, N, T, bad);
 }
 
 }  // namespace eamrl

@@ -19,7 +19,7 @@
 // evolution_large.hip, which run the same loop on populations in device memory, call them too.
 // Sorting is stable ascending (ties keep index order) where the reference leaves tie order to numpy's argsort.
 #pragma once
-#include "kernels.hpp"
+#include "tour_row.hpp"
 
 namespace eamrl {
 
@@ -96,48 +96,30 @@ __device__ __forceinline__ void reverse_row(int16_t* o, int lo, int hi)
     for (; lo < hi; ++lo, --hi) { const int16_t x = o[lo]; o[lo] = o[hi]; o[hi] = x; }
 }
 
-// Wavefront sums: canonical leg (sqrtf(fmaf(dy,dy,dx*dx))) and lane-tree order, identical to eamrl_tour_length;
-// every lane gets the result.
-__device__ __forceinline__ float leg_length(float2 p0, float2 p1)
-{
-    const float dx = p1.x - p0.x, dy = p1.y - p0.y;
-    return __builtin_sqrtf(fma_(dy, dy, dx * dx));
-}
-
+// Wavefront sums over an int16 row in LDS: the leg of env_rule.hpp in the chunked lane-tree order of tour_row.hpp, identical to
+// eamrl_tour_length; every lane gets the result.
 // open TSP cycle of row `tour` (int16 [N])
 __device__ __forceinline__ float wave_tour_length(const int16_t* tour, const float2* loc, int N, int lane)
 {
-    float total = 0.0f;
-    for (int b0 = 0; b0 < N; b0 += 64) {
-        const int t = b0 + lane;
-        const float s = wave_tree_sum(t < N ? leg_length(loc[tour[t]], loc[tour[(t + 1 == N) ? 0 : t + 1]]) : 0.0f);
-        total = (b0 == 0) ? s : total + s;
-    }
-    return total;
+    return chunked_tree_sum(N, lane, [&](int t) {
+        const float2 p0 = loc[tour[t]], p1 = loc[tour[(t + 1 == N) ? 0 : t + 1]];
+        return rule::leg(p1.x, p1.y, p0.x, p0.y);
+    });
 }
 
 // closed tour depot -> row -> depot (L + 1 legs)
 __device__ __forceinline__ float wave_route_length(const int16_t* row, const float2* loc, int L, int lane)
 {
-    float total = 0.0f;
-    for (int b0 = 0; b0 <= L; b0 += 64) {
-        const int t = b0 + lane;
-        const float s = wave_tree_sum(t <= L ? leg_length(loc[t == 0 ? 0 : row[t - 1]], loc[t == L ? 0 : row[t]]) : 0.0f);
-        total = (b0 == 0) ? s : total + s;
-    }
-    return total;
+    return chunked_tree_sum(L + 1, lane, [&](int t) {
+        const float2 p0 = loc[t == 0 ? 0 : row[t - 1]], p1 = loc[t == L ? 0 : row[t]];
+        return rule::leg(p1.x, p1.y, p0.x, p0.y);
+    });
 }
 
-// lane tree over v[row[t]], t < L (orc lane_tree: 64-blocks summed ascending)
+// lane tree over v[row[t]], t < L
 __device__ __forceinline__ float wave_gather_sum(const int16_t* row, const float* v, int L, int lane)
 {
-    float total = 0.0f;
-    for (int b0 = 0; b0 < L; b0 += 64) {
-        const int t = b0 + lane;
-        const float s = wave_tree_sum(t < L ? v[row[t]] : 0.0f);
-        total = (b0 == 0) ? s : total + s;
-    }
-    return total;
+    return chunked_tree_sum(L, lane, [&](int t) { return v[row[t]]; });
 }
 
 // bytes of the carve in k_ea without the three populations and the env's tail

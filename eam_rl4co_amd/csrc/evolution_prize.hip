@@ -214,15 +214,8 @@ struct PrizeOps {
             aux[i] = a.aux[b * M + i];
         }
         global_max = (double)a.aux[b * M];                                // OP: td["max_length"][0], the depot's entry
-        pen_total = 0.0f;
-        if (ENV == PRIZE_PCTSP) {
-            // penalties of all customers, lane tree over aux[1..M-1] (every wavefront computes the same value)
-            for (int b0 = 0; b0 < M - 1; b0 += 64) {
-                const int t = b0 + lane;
-                const float s = wave_tree_sum(t < M - 1 ? a.aux[b * M + 1 + t] : 0.0f);
-                pen_total = (b0 == 0) ? s : pen_total + s;
-            }
-        }
+        // penalties of all customers, lane tree over aux[1..M-1] (every wavefront computes the same value)
+        pen_total = ENV == PRIZE_PCTSP ? chunked_tree_sum(M - 1, lane, [&](int t) { return a.aux[b * M + 1 + t]; }) : 0.0f;
     }
     __device__ __forceinline__ void mutate_row(int16_t* row, const double* u2) const
     {

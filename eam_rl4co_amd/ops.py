@@ -46,8 +46,8 @@ def _stream(t):
 
 
 def _bytes(t):
-    """bool tensors are passed as their uint8 storage."""
-    return t.view(torch.uint8) if t.dtype == torch.bool else t
+    """bool tensors are passed as their uint8 storage; None stays None."""
+    return t.view(torch.uint8) if t is not None and t.dtype == torch.bool else t
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -930,7 +930,7 @@ def sdvrp_step_mask_(rem, used, vcap, cur, action, mask, done=None):
         _chk(action, "action", torch.int64, (R,))
         _chk(done, "done", torch.bool, (R,))
     _lib.check(lib.eamrl_sdvrp_step_mask(_ptr(rem), _ptr(used), _ptr(vcap), _ptr(cur), _ptr(action), _ptr(_bytes(mask)),
-                                         _ptr(_bytes(done)) if done is not None else None, R, M, _stream(mask)),
+                                         _ptr(_bytes(done)), R, M, _stream(mask)),
                "eamrl_sdvrp_step_mask")
     return mask
 
@@ -956,7 +956,7 @@ def pctsp_step_mask_(visited, prize_tot, pen_tot, prize, penalty, cur, istep, ac
             _chk(penalty, "penalty", torch.float32, (B, M))
     _lib.check(lib.eamrl_pctsp_step_mask(_ptr(_bytes(visited)), _ptr(prize_tot), _ptr(pen_tot), _ptr(prize), _ptr(penalty),
                                          _ptr(cur), _ptr(istep), _ptr(action), _ptr(_bytes(mask)),
-                                         _ptr(_bytes(done)) if done is not None else None, R, B, M, _stream(mask)),
+                                         _ptr(_bytes(done)), R, B, M, _stream(mask)),
                "eamrl_pctsp_step_mask")
     return mask
 
@@ -977,7 +977,7 @@ def pdp_step_mask_(visited, to_deliver, cur, action, mask, done=None):
         _chk(action, "action", torch.int64, (R,))
         _chk(done, "done", torch.bool, (R,))
     _lib.check(lib.eamrl_pdp_step_mask(_ptr(_bytes(visited)), _ptr(_bytes(to_deliver)), _ptr(cur), _ptr(action),
-                                       _ptr(_bytes(mask)), _ptr(_bytes(done)) if done is not None else None, R, M,
+                                       _ptr(_bytes(mask)), _ptr(_bytes(done)), R, M,
                                        _stream(mask)), "eamrl_pdp_step_mask")
     return mask
 
@@ -1028,7 +1028,7 @@ def cvrptw_step_mask_(visited, used, vcap, demand, cur, time, locs, tw, dur, act
         _chk(done, "done", torch.bool, (R,))
     _lib.check(lib.eamrl_cvrptw_step_mask(_ptr(visited), _ptr(used), _ptr(vcap), _ptr(demand), _ptr(cur), _ptr(time),
                                           _ptr(locs), _ptr(tw), _ptr(dur), _ptr(action), _ptr(_bytes(mask)),
-                                          _ptr(_bytes(done)) if done is not None else None, R, B, N, _stream(mask)),
+                                          _ptr(_bytes(done)), R, B, N, _stream(mask)),
                "eamrl_cvrptw_step_mask")
     return mask
 
@@ -1070,7 +1070,7 @@ def op_step_mask_(visited, tour_len, prize_tot, prize, locs, maxlen, cur, istep,
             _chk(prize, "prize", torch.float32, (B, M))
     _lib.check(lib.eamrl_op_step_mask(_ptr(_bytes(visited)), _ptr(tour_len), _ptr(prize_tot), _ptr(prize), _ptr(locs),
                                       _ptr(maxlen), _ptr(cur), _ptr(istep), _ptr(action), _ptr(_bytes(mask)),
-                                      _ptr(_bytes(done)) if done is not None else None, R, B, M, _stream(mask)),
+                                      _ptr(_bytes(done)), R, B, M, _stream(mask)),
                "eamrl_op_step_mask")
     return mask
 
@@ -1177,6 +1177,14 @@ def call_spec(entry, td, actions, vcap=None):
                                  else td[a].contiguous() for a in entry[1]))
 
 
+def _row_capacity(vcap, R):
+    """vehicle_capacity as one fp32 per row: [R], the per-instance values repeated for the rows of every start."""
+    vc = vcap.reshape(-1).contiguous()
+    if vc.numel() != R:
+        vc = vc.repeat(R // vc.numel())
+    return _chk(vc, "vehicle_capacity", torch.float32, (R,))
+
+
 def rollout_finish(env_name, locs, actions, logp=None, demand=None, vcap=None, want_reward=True, bad=None):
     """Reward, summed log-likelihood and validity counters of TSP / CVRP tours in one launch (eamrl_rollout_finish):
     bit-identical to tour_length_reward / sum_logp / check_solution.  bad: int32[2] device tensor to add to, or None.
@@ -1198,10 +1206,7 @@ def rollout_finish(env_name, locs, actions, logp=None, demand=None, vcap=None, w
     vc = None
     if env_name == "cvrp" and bad is not None:
         _chk(demand, "demand", torch.float32, (B, M - 1))
-        vc = vcap.reshape(-1).contiguous()
-        if vc.numel() != R:
-            vc = vc.repeat(R // vc.numel())
-        _chk(vc, "vehicle_capacity", torch.float32, (R,))
+        vc = _row_capacity(vcap, R)
     _lib.check(lib.eamrl_rollout_finish(ENVS[env_name], _ptr(locs), _ptr(actions), _ptr(logp), ld, _ptr(demand), _ptr(vc),
                                         _ptr(reward), _ptr(ll), _ptr(bad), R, B, M, T, _stream(locs)), "eamrl_rollout_finish")
     return reward, ll
@@ -1229,10 +1234,7 @@ def check_solution(env_name, actions, demand=None, vcap=None, num_loc=None):
     else:
         _chk(demand, "demand", torch.float32)
         B, N = demand.shape
-        vc = vcap.reshape(-1).contiguous()
-        if vc.numel() != R:
-            vc = vc.repeat(R // vc.numel())
-        _chk(vc, "vehicle_capacity", torch.float32, (R,))
+        vc = _row_capacity(vcap, R)
         _lib.check(lib.eamrl_check_solution(ENVS[env_name], _ptr(actions), _ptr(demand), _ptr(vc), R, B, N, T, _ptr(bad),
                                             _stream(actions)), "eamrl_check_solution")
     return bad

@@ -95,7 +95,8 @@ def test_multistart_rows_read_instance_r_mod_B(env, S):
 
 @pytest.mark.parametrize("env", ["tsp", "cvrp"])
 def test_rollout_finish_adds_the_same_counts(env):
-    """The second implementation of the TSP / CVRP check: `bad +=`, with and without the log-likelihood and the reward."""
+    """The TSP / CVRP check behind eamrl_rollout_finish (the row function of eamrl_check_solution's kernel, called from the
+    epilogue kernel): `bad +=`, with and without the log-likelihood and the reward."""
     from eam_rl4co_amd import ops
 
     rng = np.random.default_rng(5)
