@@ -88,6 +88,14 @@ class EasLayer(C.Structure):
                 ("dW1", _vp), ("db1", _vp), ("dW2", _vp), ("db2", _vp)]
 
 
+class MoeLayer(C.Structure):
+    """struct eamrl_moe_layer"""
+    _fields_ = ([(n, _vp) for n in ("x", "w_gate", "w_noise", "noise", "W1p", "b1", "W2p", "b2", "res", "bn_gamma", "bn_beta",
+                                    "bn_mean", "bn_var")]
+                + [("bn_eps", _f32), ("y", _vp), ("sel", _vp), ("g", _vp), ("scratch", _vp), ("scratch_bytes", _i64), ("rows", _i64),
+                   ("embed_dim", C.c_int32), ("hidden", C.c_int32), ("n_exp", C.c_int32), ("k", C.c_int32)])
+
+
 # name -> argtypes (all return int unless listed in _RESTYPES); mirrors include/eamrl.h one to one
 PROTOTYPES = {
     "eamrl_version": [],
@@ -188,12 +196,14 @@ PROTOTYPES = {
     "eamrl_ptrnet_encode": [C.POINTER(PtrNet), _vp],
     "eamrl_ptrnet_rollout": [C.POINTER(PtrNet), _i32, _vp, _vp, _vp, _vp, _vp],
     "eamrl_ptrnet_rollout_seeded": [C.POINTER(PtrNet), C.c_uint64, _vp, _vp, _vp],
+    "eamrl_moe_ffn_scratch": [_i64, _i32, _i32],
+    "eamrl_moe_ffn": [C.POINTER(MoeLayer), _vp],
     "eamrl_math_probe": [_i32, _vp, _vp, _i64, _vp],
     "eamrl_wave_probe": [_i32, _vp, _vp, _vp, _vp, _i64, _vp],
 }
 _RESTYPES = {"eamrl_last_error": C.c_char_p, "eamrl_linear_wgrad_scratch": C.c_int64,
              "eamrl_small_linear_wgrad_scratch": C.c_int64, "eamrl_batchnorm_backward_scratch": C.c_int64,
-             "eamrl_reeval_scratch_floats": C.c_int64, "eamrl_ea_large_scratch_bytes": C.c_size_t}
+             "eamrl_reeval_scratch_floats": C.c_int64, "eamrl_moe_ffn_scratch": C.c_int64, "eamrl_ea_large_scratch_bytes": C.c_size_t}
 
 _lib = None
 

@@ -1263,4 +1263,26 @@ __attribute__((visibility("default"))) int eamrl_ptrnet_rollout_seeded(const eam
                     "eamrl_ptrnet_rollout_seeded");
 }
 
+__attribute__((visibility("default"))) int64_t eamrl_moe_ffn_scratch(int64_t rows, int n_exp, int k)
+{
+    return moe_ffn_scratch_bytes(rows, n_exp, k);
+}
+
+__attribute__((visibility("default"))) int eamrl_moe_ffn(const eamrl_moe_layer* m, void* stream)
+{
+    REQUIRE(m, "eamrl_moe_ffn");
+    REQUIRE(m->embed_dim == 128 && m->hidden == 512, "eamrl_moe_ffn");
+    REQUIRE(m->n_exp >= 1 && m->n_exp <= 8 && m->k >= 1 && m->k <= m->n_exp, "eamrl_moe_ffn");
+    REQUIRE(moe_ffn_supports(m->rows, m->embed_dim, m->hidden, m->n_exp, m->k), "eamrl_moe_ffn");
+    if (m->rows == 0) return 0;
+    REQUIRE(m->x && m->w_gate && m->W1p && m->b1 && m->W2p && m->b2 && m->y && m->sel && m->g && m->scratch, "eamrl_moe_ffn");
+    REQUIRE(!m->noise || m->w_noise, "eamrl_moe_ffn");
+    REQUIRE((m->bn_gamma && m->bn_beta && m->bn_mean && m->bn_var) || (!m->bn_gamma && !m->bn_beta && !m->bn_mean && !m->bn_var),
+            "eamrl_moe_ffn");
+    REQUIRE(m->scratch_bytes >= moe_ffn_scratch_bytes(m->rows, m->n_exp, m->k), "eamrl_moe_ffn");
+    REQUIRE((((uintptr_t)m->x | (uintptr_t)m->W1p | (uintptr_t)m->W2p | (uintptr_t)m->b2 | (uintptr_t)m->res | (uintptr_t)m->y |
+              (uintptr_t)m->scratch) & 15) == 0, "eamrl_moe_ffn");
+    return launched(launch_moe_ffn(*m, (hipStream_t)stream), "eamrl_moe_ffn");
+}
+
 }  // extern "C"

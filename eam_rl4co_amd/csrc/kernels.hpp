@@ -177,5 +177,9 @@ int launch_tsp_two_opt(const float* locs, const float* distances, const int64_t*
 int launch_ptrnet_encode(const eamrl_ptrnet& p, hipStream_t st);
 int launch_ptrnet_rollout(const eamrl_ptrnet& p, int mode, const float* noise, const int64_t* given, int use_rng, uint64_t seed,
                           int64_t* actions, float* logp, hipStream_t st);
+// MoE feed-forward sublayer of the MVMoE encoder (moe_ffn.hip): gate, grouped expert GEMM, combine
+bool moe_ffn_supports(int64_t rows, int E, int F, int n_exp, int k);
+int64_t moe_ffn_scratch_bytes(int64_t rows, int n_exp, int k);
+int launch_moe_ffn(const eamrl_moe_layer& m, hipStream_t st);
 
 }  // namespace eamrl

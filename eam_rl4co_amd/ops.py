@@ -404,6 +404,107 @@ def pack_linear_weight(W, out=None):
     return out
 
 
+# the shapes eamrl_moe_ffn is built for
+MOE_EMBED_DIM, MOE_HIDDEN, MOE_MAX_EXPERTS = 128, 512, 8
+
+
+def moe_ffn_scratch(rows, n_exp, k) -> int:
+    """Bytes of device scratch `moe_ffn` needs (eamrl_moe_ffn_scratch; host only): 64 + 16 * ceil(rows * n_exp / 4) +
+    512 * rows * k, or -1 for a shape outside 1 <= k <= n_exp <= 8."""
+    return int(_lib.load().eamrl_moe_ffn_scratch(int(rows), int(n_exp), int(k)))
+
+
+def pack_moe_experts(W1, b1, W2, b2, out=None):
+    """The experts' parameters -- lists of n_exp tensors W1 [512, 128], b1 [512], W2 [128, 512], b2 [128] -- as the operand dict of
+    `moe_ffn`: W1p / W2p [n_exp, 65536] in the fragment order of `pack_linear_weight`, b1 [n_exp, 512], b2 [n_exp, 128].
+    out: such a dict to refresh in place (a captured graph keeps reading its buffers)."""
+    n = len(W1)
+    dev = W1[0].device
+    if out is None:
+        out = {"W1p": torch.empty(n, MOE_HIDDEN * MOE_EMBED_DIM, device=dev), "b1": torch.empty(n, MOE_HIDDEN, device=dev),
+               "W2p": torch.empty(n, MOE_EMBED_DIM * MOE_HIDDEN, device=dev), "b2": torch.empty(n, MOE_EMBED_DIM, device=dev)}
+    for e in range(n):
+        _chk(W1[e], "expert lins.0.weight", torch.float32, (MOE_HIDDEN, MOE_EMBED_DIM))
+        _chk(W2[e], "expert lins.1.weight", torch.float32, (MOE_EMBED_DIM, MOE_HIDDEN))
+        pack_linear_weight(W1[e], out=out["W1p"][e])
+        pack_linear_weight(W2[e], out=out["W2p"][e])
+        out["b1"][e].copy_(b1[e])
+        out["b2"][e].copy_(b2[e])
+    return out
+
+
+_MOE_SCRATCH = {}
+
+
+def _moe_scratch(device, need):
+    """The scratch of `moe_ffn`, kept per (device, stream) and grown on demand: the calls of one stream run one after the
+    other, so the layers of an encoder share it (106 MB at 103 424 rows, k = 2).  Under HIP-graph capture a private buffer is
+    allocated instead, in the graph's own pool."""
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(need, device=device, dtype=torch.uint8)
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    buf = _MOE_SCRATCH.get(key)
+    if buf is None or buf.numel() < need:
+        _MOE_SCRATCH[key] = buf = torch.empty(need, device=device, dtype=torch.uint8)
+    return buf
+
+
+def moe_ffn(x, w_gate, experts, k, w_noise=None, noise=None, residual=None, bn=None, out=None, return_routing=False):
+    """[BN_eval](residual + MoE(x)) for x [..., 128]: noisy top-k gating over n_exp = w_gate.shape[1] experts, the selected
+    experts' 128 -> 512 -> 128 ReLU MLPs and their gate-weighted sum (eamrl_moe_ffn: three launches, no host synchronisation).
+    experts: the dict of `pack_moe_experts`.  noise [rows, n_exp] standard-normal draws (with w_noise): training-mode noisy
+    gating; None: clean logits.  bn = (gamma, beta, running_mean, running_var, eps).  out may be `residual` (in place).
+    return_routing: also (sel [rows, k] int8, gates [rows, k]), larger gate first."""
+    lib = _lib.load()
+    _chk(x, "x", torch.float32)
+    _chk(w_gate, "w_gate", torch.float32)
+    E, n_exp, k = x.shape[-1], w_gate.shape[1] if w_gate.dim() == 2 else -1, int(k)
+    rows = x.numel() // max(E, 1)
+    if E != MOE_EMBED_DIM or w_gate.dim() != 2 or w_gate.shape[0] != E:
+        raise NotImplementedError(f"moe_ffn: embed_dim {E} with w_gate {tuple(w_gate.shape)}; the kernels are built for embed_dim "
+                                  f"{MOE_EMBED_DIM} and w_gate [{MOE_EMBED_DIM}, n_exp]")
+    if not 1 <= k <= n_exp <= MOE_MAX_EXPERTS:
+        raise NotImplementedError(f"moe_ffn: k = {k}, num_experts = {n_exp}; built for 1 <= k <= num_experts <= {MOE_MAX_EXPERTS}")
+    _chk(experts["W1p"], "experts['W1p']", torch.float32, (n_exp, MOE_HIDDEN * E))
+    _chk(experts["b1"], "experts['b1']", torch.float32, (n_exp, MOE_HIDDEN))
+    _chk(experts["W2p"], "experts['W2p']", torch.float32, (n_exp, E * MOE_HIDDEN))
+    _chk(experts["b2"], "experts['b2']", torch.float32, (n_exp, E))
+    if noise is not None:
+        if w_noise is None:
+            raise ValueError("moe_ffn: noise needs w_noise")
+        _chk(w_noise, "w_noise", torch.float32, (E, n_exp))
+        _chk(noise, "noise", torch.float32, (rows, n_exp))
+    if residual is not None:
+        _chk(residual, "residual", torch.float32, tuple(x.shape))
+    if out is None:
+        out = torch.empty_like(x)
+    _chk(out, "out", torch.float32, tuple(x.shape))
+    m = _lib.MoeLayer()
+    if bn is not None:
+        gamma, beta, mean, var, eps = bn
+        for nm, t in (("gamma", gamma), ("beta", beta), ("running_mean", mean), ("running_var", var)):
+            _chk(t, nm, torch.float32, (E,))
+        m.bn_gamma, m.bn_beta, m.bn_mean, m.bn_var, m.bn_eps = gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(), var.data_ptr(), float(eps)
+    sel = torch.empty(rows, k, device=x.device, dtype=torch.int8)
+    g = torch.empty(rows, k, device=x.device, dtype=torch.float32)
+    if rows == 0:
+        return (out, sel, g) if return_routing else out
+    need = lib.eamrl_moe_ffn_scratch(rows, n_exp, k)
+    if need < 0:
+        raise NotImplementedError(f"moe_ffn: {rows} rows are above the 2^24 rows of one call")
+    scratch = _moe_scratch(x.device, need)
+    m.x, m.w_gate = x.data_ptr(), w_gate.data_ptr()
+    if noise is not None:
+        m.w_noise, m.noise = w_noise.data_ptr(), noise.data_ptr()
+    m.W1p, m.b1, m.W2p, m.b2 = (experts[n].data_ptr() for n in ("W1p", "b1", "W2p", "b2"))
+    if residual is not None:
+        m.res = residual.data_ptr()
+    m.y, m.sel, m.g, m.scratch, m.scratch_bytes = out.data_ptr(), sel.data_ptr(), g.data_ptr(), scratch.data_ptr(), need
+    m.rows, m.embed_dim, m.hidden, m.n_exp, m.k = rows, E, MOE_HIDDEN, n_exp, k
+    _lib.check(lib.eamrl_moe_ffn(C.byref(m), _stream(x)), "eamrl_moe_ffn")
+    return (out, sel, g) if return_routing else out
+
+
 def encoder_fused_supported(M, E, H, ff_hidden, nlayers) -> bool:
     return bool(_lib.load().eamrl_encoder_fused_supported(int(M), int(E), int(H), int(ff_hidden), int(nlayers)))
 

@@ -202,6 +202,66 @@ class _MLPParams(nn.Module):
         self.lins = nn.ModuleList(nn.Linear(a, b) for a, b in zip(dims[:-1], dims[1:]))
 
 
+class MoE(nn.Module):
+    """Parameters of the reference's sparsely gated mixture of experts (nn/moe.py:114-146, its names and its initialisation:
+    `w_gate` = `w_noise` = 0, default Linear experts, buffers `mean` / `std`) as the feed-forward sublayer of an encoder layer
+    (MVMoE, Zhou et al. 2024).  `sublayer` is the native forward (ops.moe_ffn: gate, grouped expert GEMM, combine); under
+    autograd the sublayer is the torch expression `train.moe_autograd`.  Extra keyword arguments (e.g. `routing_level`) are
+    swallowed, as the reference's constructor does."""
+
+    def __init__(self, input_size, output_size, num_neurons=(), hidden_act="ReLU", out_bias=True, num_experts=4, k=2,
+                 noisy_gating=True, **kwargs):
+        super().__init__()
+        num_neurons = list(num_neurons)
+        if input_size != ops.MOE_EMBED_DIM or output_size != ops.MOE_EMBED_DIM or num_neurons != [ops.MOE_HIDDEN]:
+            raise NotImplementedError(f"MoE encoder: embed_dim {input_size} -> {num_neurons} -> {output_size}; the expert kernel is "
+                                      f"built for embed_dim {ops.MOE_EMBED_DIM} and feedforward_hidden {ops.MOE_HIDDEN}")
+        if hidden_act != "ReLU":
+            raise NotImplementedError(f"MoE encoder: hidden_act={hidden_act!r}; the expert kernel is built for 'ReLU'")
+        if not (isinstance(num_experts, int) and isinstance(k, int) and 1 <= k <= num_experts <= ops.MOE_MAX_EXPERTS):
+            raise NotImplementedError(f"MoE encoder: k={k}, num_experts={num_experts}; built for 1 <= k <= num_experts <= "
+                                      f"{ops.MOE_MAX_EXPERTS}")
+        self.noisy_gating, self.num_experts, self.k = bool(noisy_gating), num_experts, k
+        self.input_size, self.output_size = input_size, output_size
+        self.experts = nn.ModuleList(_MLPParams(input_size, output_size, num_neurons) for _ in range(num_experts))
+        self.w_gate = nn.Parameter(torch.zeros(input_size, num_experts), requires_grad=True)
+        self.w_noise = nn.Parameter(torch.zeros(input_size, num_experts), requires_grad=True)
+        self.register_buffer("mean", torch.tensor([0.0]))
+        self.register_buffer("std", torch.tensor([1.0]))
+
+    def packed_experts(self):
+        """The operand dict of ops.moe_ffn: the experts' weights in fragment order and their biases, in persistent buffers
+        refreshed in place when a parameter changes (a captured HIP graph keeps reading them), as `_fused_layers` keeps its packs."""
+        ps = [p for ex in self.experts for lin in ex.lins for p in (lin.weight, lin.bias)]
+        key = tuple((p.data_ptr(), p._version) for p in ps) + (ps[0].device,)
+        slot = self.__dict__.get("_packed")
+        if slot is None or slot[0] != key:
+            buf = None if slot is None or slot[1]["W1p"].device != ps[0].device else slot[1]
+            with torch.no_grad():
+                buf = ops.pack_moe_experts([ex.lins[0].weight.detach() for ex in self.experts],
+                                           [ex.lins[0].bias.detach() for ex in self.experts],
+                                           [ex.lins[1].weight.detach() for ex in self.experts],
+                                           [ex.lins[1].bias.detach() for ex in self.experts], out=buf)
+            self.__dict__["_packed"] = slot = (key, buf)
+        return slot[1]
+
+    def draw_noise(self, rows, device):
+        """The standard-normal draws of noisy gating [rows, num_experts] (nn/moe.py:223), or None where the reference adds
+        none: eval mode, or noisy_gating off."""
+        if not (self.noisy_gating and self.training):
+            return None
+        return torch.randn(rows, self.num_experts, device=device, dtype=torch.float32)
+
+    def sublayer(self, h, bn=None, noise=None, return_routing=False):
+        """[BN_eval](h + MoE(h)) on the native kernels; noise: the draws to use instead of fresh ones (training mode)."""
+        h = h.contiguous()
+        if noise is None:
+            noise = self.draw_noise(h.numel() // h.shape[-1], h.device)
+        return ops.moe_ffn(h, self.w_gate.detach(), self.packed_experts(), self.k,
+                           w_noise=self.w_noise.detach() if noise is not None else None, noise=noise, residual=h,
+                           bn=bn, return_routing=return_routing)
+
+
 class Normalization(nn.Module):
     def __init__(self, embed_dim, normalization="batch"):
         super().__init__()
@@ -237,11 +297,14 @@ class Normalization(nn.Module):
 class MultiHeadAttentionLayer(nn.Sequential):
     """[SkipConnection(MHA), Normalization, SkipConnection(MLP), Normalization] (nn/graph/attnnet.py:16-57)."""
 
-    def __init__(self, embed_dim, num_heads=8, feedforward_hidden=512, normalization="batch", bias=True):
+    def __init__(self, embed_dim, num_heads=8, feedforward_hidden=512, normalization="batch", bias=True, moe_kwargs=None):
+        num_neurons = [feedforward_hidden] if feedforward_hidden > 0 else []
+        ffn = MoE(embed_dim, embed_dim, num_neurons=num_neurons, **moe_kwargs) if moe_kwargs is not None \
+            else _MLPParams(embed_dim, embed_dim, num_neurons)
         super().__init__(
             _Holder(_MHAParams(embed_dim, num_heads, bias=bias)),
             Normalization(embed_dim, normalization),
-            _Holder(_MLPParams(embed_dim, embed_dim, [feedforward_hidden] if feedforward_hidden > 0 else [])),
+            _Holder(ffn),
             Normalization(embed_dim, normalization),
         )
 
@@ -253,6 +316,9 @@ class MultiHeadAttentionLayer(nn.Sequential):
         h = ops.linear(att, mha.out_proj.weight, mha.out_proj.bias, residual=h, bn=bn1)    # norm(h + MHA(h))
         if bn1 is None:
             h = self[1].apply_(h)
+        if isinstance(ffn, MoE):
+            h = ffn.sublayer(h, bn=bn2)                                                     # norm(h + MoE(h))
+            return h if bn2 is not None else self[3].apply_(h)
         x = h
         for lin in ffn.lins[:-1]:
             x = ops.linear(x, lin.weight, lin.bias, relu=True)
@@ -261,9 +327,10 @@ class MultiHeadAttentionLayer(nn.Sequential):
 
 
 class GraphAttentionNetwork(nn.Module):
-    def __init__(self, num_heads, embed_dim, num_layers, normalization="batch", feedforward_hidden=512):
+    def __init__(self, num_heads, embed_dim, num_layers, normalization="batch", feedforward_hidden=512, moe_kwargs=None):
         super().__init__()
-        self.layers = nn.Sequential(*(MultiHeadAttentionLayer(embed_dim, num_heads, feedforward_hidden, normalization)
+        self.layers = nn.Sequential(*(MultiHeadAttentionLayer(embed_dim, num_heads, feedforward_hidden, normalization,
+                                                              moe_kwargs=moe_kwargs)
                                       for _ in range(num_layers)))
         self.dtype16 = None     # torch.float16 / torch.bfloat16: the fused kernel runs on 16-bit operands (policy.precision)
 
@@ -305,6 +372,8 @@ class GraphAttentionNetwork(nn.Module):
         training mode, EAMRL_FUSED_ENCODER=0) the fp32 layer-by-layer path runs, whatever dtype16 says."""
         if os.environ.get("EAMRL_FUSED_ENCODER", "1") == "0" or len(self.layers) == 0:
             return None
+        if any(isinstance(layer[2].module, MoE) for layer in self.layers):
+            return None                 # MoE layers: the fp32 layer-by-layer path (ops.moe_ffn between its launches)
         first = self.layers[0]
         mha0, ffn0 = first[0].module, first[2].module
         if len(ffn0.lins) != 2:
@@ -358,16 +427,19 @@ class AttentionModelEncoder(nn.Module):
                  normalization="batch", feedforward_hidden=512, net=None, sdpa_fn=None, moe_kwargs=None):
         super().__init__()
         env_name = _kind(env_name)
-        if moe_kwargs is not None or sdpa_fn is not None:
-            raise NotImplementedError("moe_kwargs / sdpa_fn injection is outside the MI355X rollout path")
+        if sdpa_fn is not None:
+            raise NotImplementedError("sdpa_fn injection is outside the MI355X rollout path")
+        if moe_kwargs is not None and net is not None:
+            raise NotImplementedError("moe_kwargs with net=: the MoE sublayer is built into GraphAttentionNetwork; pass "
+                                      "GraphAttentionNetwork(..., moe_kwargs=...) as the net")
         self.env_name = env_name
         if init_embedding is None:
             init_embedding = {"tsp": TSPInitEmbedding, "cvrp": VRPInitEmbedding, "sdvrp": VRPInitEmbedding,
                               "pctsp": PCTSPInitEmbedding, "op": OPInitEmbedding,
                               "cvrptw": VRPTWInitEmbedding, "pdp": PDPInitEmbedding}[env_name](embed_dim)
         self.init_embedding = init_embedding
-        self.net = GraphAttentionNetwork(num_heads, embed_dim, num_layers, normalization, feedforward_hidden) \
-            if net is None else net
+        self.net = GraphAttentionNetwork(num_heads, embed_dim, num_layers, normalization, feedforward_hidden,
+                                         moe_kwargs=moe_kwargs) if net is None else net
 
     def forward(self, td, mask=None, cache_spec=None, want_hidden=True, want_init=True):
         """-> (embeddings, init embeddings).  With a `cache_spec` the whole encoder can be ONE launch that starts from the
@@ -584,8 +656,12 @@ class AttentionModelDecoder(nn.Module):
             raise NotImplementedError("pointer=: only eam_rl4co_amd.PointerAttention (mask_inner, no output bias, the decoder's "
                                       "head count) can replace the built-in pointer; its project_out is what the fused "
                                       "kernels fold into the logit key")
-        if any(x is not None for x in (context_embedding, dynamic_embedding, sdpa_fn, moe_kwargs)) or linear_bias:
-            raise NotImplementedError("custom context/dynamic embeddings, sdpa_fn, MoE and decoder biases are "
+        if moe_kwargs is not None:
+            raise NotImplementedError("moe_kwargs['decoder'] (PointerAttnMoE, light or not) is not built: only the encoder half of "
+                                      "MVMoE is (moe_kwargs['encoder']); a per-row project_out breaks the folded logit key of the "
+                                      "one-launch rollout")
+        if any(x is not None for x in (context_embedding, dynamic_embedding, sdpa_fn)) or linear_bias:
+            raise NotImplementedError("custom context/dynamic embeddings, sdpa_fn and decoder biases are "
                                       "outside the MI355X rollout path (the routing AttentionModel family only)")
         assert embed_dim % num_heads == 0
         self.env_name, self.embed_dim, self.num_heads = env_name, embed_dim, num_heads
@@ -835,15 +911,21 @@ class AttentionModelPolicy(nn.Module):
         if env_name not in ("tsp", "cvrp", "cvrptw", "sdvrp", "pctsp", "op", "pdp"):
             raise NotImplementedError(f"env_name={env_name!r}: the MI355X rollout path covers 'tsp', 'cvrp', 'cvrptw', 'pdp', "
                                       "'sdvrp', 'pctsp', 'spctsp' and 'op'")
-        if moe_kwargs not in (None, {"encoder": None, "decoder": None}) or any(
-                x is not None for x in (sdpa_fn, sdpa_fn_encoder, sdpa_fn_decoder, encoder_network)):
-            raise NotImplementedError("MoE / sdpa_fn / encoder_network injection is outside the MI355X rollout path")
+        if any(x is not None for x in (sdpa_fn, sdpa_fn_encoder, sdpa_fn_decoder, encoder_network)):
+            raise NotImplementedError("sdpa_fn / encoder_network injection is outside the MI355X rollout path")
+        moe_kwargs = {"encoder": None, "decoder": None} if moe_kwargs is None else moe_kwargs
+        if moe_kwargs.get("decoder") is not None:
+            raise NotImplementedError("moe_kwargs['decoder'] (PointerAttnMoE, light or not) is not built: only the encoder half of "
+                                      "MVMoE is (moe_kwargs['encoder'])")
+        if moe_kwargs.get("encoder") is not None and encoder is not None:
+            raise NotImplementedError("moe_kwargs['encoder'] with encoder=: build the encoder with its own moe_kwargs")
         if not mask_logits:
             raise NotImplementedError("mask_logits=False is not built for MI355X")
         self.env_name = env_name
         self.encoder = encoder if encoder is not None else AttentionModelEncoder(
             embed_dim=embed_dim, num_heads=num_heads, num_layers=num_encoder_layers, env_name=env_name,
-            normalization=normalization, feedforward_hidden=feedforward_hidden, init_embedding=init_embedding)
+            normalization=normalization, feedforward_hidden=feedforward_hidden, init_embedding=init_embedding,
+            moe_kwargs=moe_kwargs.get("encoder"))
         self.decoder = decoder if decoder is not None else AttentionModelDecoder(
             embed_dim=embed_dim, num_heads=num_heads, env_name=env_name, context_embedding=context_embedding,
             dynamic_embedding=dynamic_embedding, mask_inner=mask_inner, out_bias_pointer_attn=out_bias_pointer_attn,
@@ -930,6 +1012,11 @@ class AttentionModelPolicy(nn.Module):
             self.__dict__["_key_tensors"] = lists
         return lists[0]
 
+    def _has_moe(self) -> bool:
+        from .train import has_moe_encoder
+
+        return has_moe_encoder(self)
+
     def _one_encoder_pass(self, td, return_init_embeds) -> bool:
         """Training: where the differentiable encoder of the gradient graph reproduces the native encoder bit for bit
         (train.graph_encoder_equals_native), it is built FIRST and its embeddings feed the rollout -- one encoder pass per step
@@ -940,6 +1027,11 @@ class AttentionModelPolicy(nn.Module):
 
         if not (isinstance(self.encoder, AttentionModelEncoder) and isinstance(self.decoder, AttentionModelDecoder)
                 and hasattr(td, "items") and train.graph_encoder_equals_native(self, td)):
+            if self.training and train.has_noisy_moe_encoder(self):
+                # two encoder passes would draw two sets of gating noise: the rollout's log-likelihood and its gradient would
+                # belong to differently routed networks
+                raise NotImplementedError("training a noisy-gating MoE policy needs the single encoder pass, which serves the "
+                                          "built-in AttentionModelEncoder / AttentionModelDecoder on fp32 GPU tensors only")
             return False
         own = getattr(self, "_shared_dt", None) is None
         if own:
@@ -1059,7 +1151,10 @@ class AttentionModelPolicy(nn.Module):
             Bq, Mq = td["action_mask"].shape
             spec = self.decoder._fused_cache_spec(Bq, Mq, td["action_mask"].device, dtype=self._dtype16)
         shared, ekey, ent = getattr(self, "_shared_dt", None), None, None
-        if shared is not None and spec is not None:     # train.shared_decoder_tensors: same instances, same parameters
+        # train.shared_decoder_tensors: same instances, same parameters (without a fused cache spec -- graphs above 128 nodes --
+        # only for an MoE policy, to take over the embeddings of the training graph `_one_encoder_pass` has built: its gating
+        # noise must be the rollout's)
+        if shared is not None and (spec is not None or (shared.get("native") is not None and self._has_moe())):
             from .train import _graph_key
 
             ekey = _graph_key(self, td)
@@ -1077,7 +1172,7 @@ class AttentionModelPolicy(nn.Module):
                 hidden, init_embeds = self.encoder(td, cache_spec=spec, want_hidden=need_emb, want_init=return_init_embeds)
             else:
                 hidden, init_embeds = self.encoder(td, cache_spec=spec) if spec is not None else self.encoder(td)
-            if ekey is not None and spec.get("filled"):
+            if ekey is not None and spec is not None and spec.get("filled"):
                 shared["native"] = (ekey, hidden, init_embeds, spec)
         cache = self.decoder._precompute_cache(hidden, num_starts=S, prefilled=spec)
 
@@ -1674,6 +1769,10 @@ class GraphedRollout:
             net = getattr(self.policy.encoder, "net", None)
             if hasattr(net, "_fused_layers"):
                 net._fused_layers(self._embed_probe)          # re-packs changed encoder weights into the buffers the graph reads
+            for layer in getattr(net, "layers", ()):
+                ffn = getattr(layer[2], "module", None) if isinstance(layer, nn.Sequential) and len(layer) > 2 else None
+                if isinstance(ffn, MoE):
+                    ffn.packed_experts()                      # ... and the MoE layers' expert packs
             refresh = getattr(self.policy.encoder, "refresh_packs", None)
             if refresh is not None:
                 refresh()

@@ -62,11 +62,14 @@ class _BatchNormTrainFn(torch.autograd.Function):
     statistics are not touched here (the rollout updated them once for this forward)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, eps):
+    def forward(ctx, x, weight, bias, eps, running=None):
         from . import ops
 
         y = x.clone(memory_format=torch.contiguous_format)          # the kernel normalises in place; x is kept for the backward
-        _, mean, var = ops.batchnorm_train_(y, weight.detach(), bias.detach(), None, None, 0.0, eps)
+        # running = (running_mean, running_var, momentum): this forward is the step's only encoder pass (MoE policies) and
+        # updates the running statistics as the rollout's pass would have
+        rm, rv, mom = running if running is not None else (None, None, 0.0)
+        _, mean, var = ops.batchnorm_train_(y, weight.detach(), bias.detach(), rm, rv, mom, eps)
         ctx.save_for_backward(x.contiguous(), mean, var, weight)
         ctx.eps = eps
         ctx.affine = weight.requires_grad or bias.requires_grad
@@ -78,7 +81,7 @@ class _BatchNormTrainFn(torch.autograd.Function):
 
         x, mean, var, weight = ctx.saved_tensors
         dx, dg, db = ops.batchnorm_backward(x, dy.contiguous(), mean, var, weight.detach(), ctx.eps, need_affine_grads=ctx.affine)
-        return dx, dg, db, None
+        return dx, dg, db, None, None
 
 
 class _SmallLinearFn(torch.autograd.Function):
@@ -188,7 +191,9 @@ def _self_attention(qkv, B, N, E, H):
     return F.scaled_dot_product_attention(q[0], q[1], q[2]).permute(0, 2, 1, 3).reshape(B, N, E)
 
 
-def _normalize(norm: nn.Module, x: torch.Tensor, training: bool) -> torch.Tensor:
+def _normalize(norm: nn.Module, x: torch.Tensor, training: bool, update_running: bool = False) -> torch.Tensor:
+    """update_running: a training-mode batch norm also updates its running statistics (the graph's forward is the step's only
+    encoder pass: MoE policies)."""
     n = norm.normalizer
     if isinstance(n, nn.BatchNorm1d):
         # Batch statistics when training, as the reference (nn/ops.py:45-47) and as the native rollout that drew the
@@ -196,9 +201,17 @@ def _normalize(norm: nn.Module, x: torch.Tensor, training: bool) -> torch.Tensor
         x2 = x.reshape(-1, x.size(-1))
         if training and x2.is_cuda and x2.dtype == torch.float32 and n.weight is not None and n.bias is not None and x2.size(-1) % 4 == 0 \
                 and os.environ.get("EAMRL_TORCH_BATCHNORM", "0") != "1":
-            y = _BatchNormTrainFn.apply(x2, n.weight, n.bias, float(n.eps))
+            running = None
+            if update_running and n.running_mean is not None:
+                running = (n.running_mean, n.running_var, 0.1 if n.momentum is None else n.momentum)
+                n.num_batches_tracked.add_(1)
+            y = _BatchNormTrainFn.apply(x2, n.weight, n.bias, float(n.eps), running)
         elif training:
-            y = F.batch_norm(x2, None, None, n.weight, n.bias, True, 0.0, n.eps)
+            upd = update_running and n.running_mean is not None
+            if upd:
+                n.num_batches_tracked.add_(1)
+            y = F.batch_norm(x2, n.running_mean if upd else None, n.running_var if upd else None, n.weight, n.bias, True,
+                             (0.1 if n.momentum is None else n.momentum) if upd else 0.0, n.eps)
         else:
             y = F.batch_norm(x2, n.running_mean, n.running_var, n.weight, n.bias, False, 0.0, n.eps)
         return y.view_as(x)
@@ -332,20 +345,67 @@ def _encode_autograd_ham(policy, td):
     return h
 
 
+def has_moe_encoder(policy) -> bool:
+    """Whether an encoder layer's feed-forward sublayer is a mixture of experts (policy.MoE)."""
+    from .policy import MoE
+
+    layers = getattr(getattr(getattr(policy, "encoder", None), "net", None), "layers", None)
+    return layers is not None and any(isinstance(getattr(layer[2], "module", None), MoE) for layer in layers
+                                      if isinstance(layer, nn.Sequential) and len(layer) > 2)
+
+
+def has_noisy_moe_encoder(policy) -> bool:
+    """has_moe_encoder, and one of the MoE layers adds gating noise in training mode."""
+    from .policy import MoE
+
+    return has_moe_encoder(policy) and any(isinstance(layer[2].module, MoE) and layer[2].module.noisy_gating
+                                           for layer in policy.encoder.net.layers)
+
+
+def moe_autograd(moe, h, training: bool):
+    """MoE(h) of an encoder layer as a torch expression on the module's parameters: the reference's function (nn/moe.py:208-277
+    -- noisy top-k gating with its 1e-2 floor, gates normalised over the selected experts with + 1e-6, gate-weighted sum of the
+    selected experts' outputs; the load-balancing loss is multiplied by loss_coef = 0 there and not formed here).  Every expert
+    runs on all rows and unselected experts carry a zero gate, so nothing synchronises with the host; the selection breaks
+    ties towards the lower expert index, as the kernels do (a stable sort).  h [..., E] -> [..., E]."""
+    x = h.reshape(-1, h.shape[-1])
+    logits = x @ moe.w_gate
+    if moe.noisy_gating and training:
+        std = F.softplus(x @ moe.w_noise) + 1e-2
+        logits = logits + torch.randn_like(logits) * std
+    p = torch.softmax(logits, -1)
+    top_p, top_i = torch.sort(p, dim=-1, descending=True, stable=True)
+    top_p, top_i = top_p[:, :moe.k], top_i[:, :moe.k]
+    top_g = top_p / (top_p.sum(1, keepdim=True) + 1e-6)
+    gates = torch.zeros_like(p).scatter(-1, top_i, top_g)
+    y = None
+    for e, ex in enumerate(moe.experts):
+        o = _linear(_linear(x, ex.lins[0].weight, ex.lins[0].bias, relu=True), ex.lins[1].weight, ex.lins[1].bias)
+        o = gates[:, e:e + 1] * o
+        y = o if y is None else y + o
+    return y.view_as(h)
+
+
 def encode_autograd(policy, td):
     enc = policy.encoder
-    from .policy import GraphHeterogeneousAttentionEncoder
+    from .policy import GraphHeterogeneousAttentionEncoder, MoE
 
     if isinstance(enc, GraphHeterogeneousAttentionEncoder):
         return _encode_autograd_ham(policy, td)
     h = init_embedding_autograd(policy, td)
     training = policy.training
+    # an MoE policy's step runs the encoder once, here (graph_encoder_equals_native): rollout and gradient must see the same
+    # gating noise.  This pass then also keeps the batch norms' running statistics, which the rollout's pass keeps otherwise.
+    single = has_moe_encoder(policy)
     for layer in enc.net.layers:
         mha, ffn = layer[0].module, layer[2].module
         B, N, E = h.shape
         H = mha.num_heads
         att = _self_attention(_linear(h, mha.Wqkv.weight, mha.Wqkv.bias), B, N, E, H)
-        h = _normalize(layer[1], _linear(att, mha.out_proj.weight, mha.out_proj.bias, residual=h), training)
+        h = _normalize(layer[1], _linear(att, mha.out_proj.weight, mha.out_proj.bias, residual=h), training, single)
+        if isinstance(ffn, MoE):
+            h = _normalize(layer[3], h + moe_autograd(ffn, h, training), training, single)
+            continue
         x = h
         for lin in ffn.lins[:-1]:
             x = _linear(x, lin.weight, lin.bias, relu=True)
@@ -576,13 +636,22 @@ def graph_encoder_equals_native(policy, td) -> bool:
     library's kernels (none of the EAMRL_TORCH_* switches), fp32 on the GPU.  Batch-norm policies keep two passes: their graph
     runs on the same kernels since round 3 (`_BatchNormTrainFn`), but the rollout's pass is the one that updates the running
     statistics.  Graphs of up to 1024 nodes, where the self-attention's backward is native (the native re-evaluation's limit
-    too); above that the graph's attention is torch's."""
+    too); above that the graph's attention is torch's.
+    MoE policies (`has_moe_encoder`) are the exception: the answer is True on fp32 GPU tensors whatever the norm and whatever the
+    EAMRL_TORCH_* / EAMRL_SEPARATE_ENCODER_PASSES switches say.  Their graph does NOT reproduce the native bits (the MoE
+    sublayer is a torch expression there); it stands in for the native encoder because rollout and gradient must see one draw
+    of the gating noise."""
     from . import ops
 
+    locs = td["locs"]
+    if has_moe_encoder(policy):
+        # MoE policies: the graph's embeddings are not the native encoder's bits (its MoE sublayer is a torch expression), but
+        # they MUST stand in for them -- with noisy gating a second pass would draw other noise and route rows differently, so
+        # the rollout's log-likelihood and its gradient would belong to different networks.  Any norm, any switch.
+        return bool(locs.is_cuda and locs.dtype == torch.float32)
     if any(os.environ.get(k, "0") == "1" for k in ("EAMRL_TORCH_LINEAR", "EAMRL_TORCH_ATTENTION", "EAMRL_TORCH_INSTANCE_NORM",
                                                   "EAMRL_SEPARATE_ENCODER_PASSES")):
         return False
-    locs = td["locs"]
     enc = getattr(policy, "encoder", None)
     layers = getattr(getattr(enc, "net", None), "layers", None)
     if layers is None or not locs.is_cuda or locs.dtype != torch.float32:

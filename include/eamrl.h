@@ -966,6 +966,47 @@ int eamrl_ptrnet_rollout(const eamrl_ptrnet* p, int mode, const float* noise, co
                          void* stream);
 int eamrl_ptrnet_rollout_seeded(const eamrl_ptrnet* p, uint64_t seed, int64_t* actions, float* logp, void* stream);
 
+/* ---- MVMoE encoder: the sparsely gated mixture-of-experts feed-forward sublayer ---------------------- */
+
+/* MoE.forward  [models/nn/moe.py:114-277] in place of an encoder layer's MLP  [nn/graph/attnnet.py:38-42], followed by the
+ * SkipConnection's residual and, optionally, Normalization(batch, eval):   y = [BN_eval](res + MoE(x)).
+ * Per row, all float32 and nothing contracted (chain_k = the k-ordered fma chain of eamrl_linear):
+ *   logit[e] = chain_k(x[k], w_gate[k][e], 128, 0)
+ *   with noise != NULL:  std[e] = softplus(chain_k(x[k], w_noise[k][e], 128, 0)) + 1e-2f,  logit[e] += noise[row][e] * std[e]
+ *     (multiply, then add; softplus(v) = v > 20 ? v : log(1 + exp(v)) on the library's defined exp / log); the standard-normal
+ *     draws are an input, the library draws none
+ *   p = softmax(logit): exp(logit - max), summed in ascending expert order, one correctly rounded division per expert
+ *   sel = the k largest p, larger first, TIES TO THE LOWER EXPERT INDEX;  g[j] = p[sel j] / (sum_j p[sel j] + 1e-6f), the sum in
+ *     selection order
+ *   o_e = b2_e + W2_e relu(b1_e + W1_e x), each product the chain of eamrl_linear
+ *   MoE(x) = 0, then for the selected experts in ascending expert index: y = y + g_e * o_e (multiply, then add); an expert that
+ *     is not selected is skipped, never multiplied by zero
+ * Shapes: embed_dim 128, hidden 512, 1 <= k <= n_exp <= 8, rows <= 2^24.  x, res, y [rows][128] (y may alias res or x);
+ * w_gate, w_noise [128][n_exp]; noise [rows][n_exp] or NULL (then w_noise is not read); W1p [n_exp][512 * 128] and W2p
+ * [n_exp][128 * 512]: every expert's Linear.weight in the fragment order of eamrl_pack_linear_weight; b1 [n_exp][512],
+ * b2 [n_exp][128]; bn_*: all NULL or the [128] parameters of eamrl_linear_bn; sel [rows][k] int8 and g [rows][k] are outputs.
+ * scratch: eamrl_moe_ffn_scratch(rows, n_exp, k) bytes of device memory, 16-byte aligned
+ *   = 64 + 16 * ceil(rows * n_exp / 4) + 512 * rows * k   (counters, the experts' row lists, the selected experts' outputs);
+ *   -1: shape not supported.  Host only.
+ * One memset and three launches (gate, grouped expert GEMM on v_mfma_f32_16x16x4_f32, combine) on `stream`; no host
+ * synchronisation, no floating-point atomics; grids depend on (rows, n_exp, k) only, so a captured graph replays for any routing.
+ * Everything is checked before the first launch. */
+typedef struct eamrl_moe_layer {
+    const float* x;
+    const float* w_gate; const float* w_noise; const float* noise;
+    const float* W1p; const float* b1; const float* W2p; const float* b2;
+    const float* res;
+    const float* bn_gamma; const float* bn_beta; const float* bn_mean; const float* bn_var; float bn_eps;
+    float* y;
+    int8_t* sel;
+    float* g;
+    void* scratch; int64_t scratch_bytes;
+    int64_t rows;
+    int32_t embed_dim, hidden, n_exp, k;
+} eamrl_moe_layer;
+int64_t eamrl_moe_ffn_scratch(int64_t rows, int n_exp, int k);
+int eamrl_moe_ffn(const eamrl_moe_layer* m, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
