@@ -96,6 +96,15 @@ class MoeLayer(C.Structure):
                    ("embed_dim", C.c_int32), ("hidden", C.c_int32), ("n_exp", C.c_int32), ("k", C.c_int32)])
 
 
+class MoeExperts(C.Structure):
+    """struct eamrl_moe_experts"""
+    _fields_ = ([(n, _vp) for n in ("x", "sel", "g", "W1p", "b1", "W2p", "b2", "W1Tp", "W2Tp", "y", "state")]
+                + [("state_bytes", _i64)]
+                + [(n, _vp) for n in ("dy", "dx", "dg", "dW1", "db1", "dW2", "db2", "scratch")]
+                + [("scratch_bytes", _i64), ("rows", _i64),
+                   ("embed_dim", C.c_int32), ("hidden", C.c_int32), ("n_exp", C.c_int32), ("k", C.c_int32)])
+
+
 # name -> argtypes (all return int unless listed in _RESTYPES); mirrors include/eamrl.h one to one
 PROTOTYPES = {
     "eamrl_version": [],
@@ -198,12 +207,17 @@ PROTOTYPES = {
     "eamrl_ptrnet_rollout_seeded": [C.POINTER(PtrNet), C.c_uint64, _vp, _vp, _vp],
     "eamrl_moe_ffn_scratch": [_i64, _i32, _i32],
     "eamrl_moe_ffn": [C.POINTER(MoeLayer), _vp],
+    "eamrl_moe_experts_forward_scratch": [_i64, _i32, _i32],
+    "eamrl_moe_experts_backward_scratch": [_i64, _i32, _i32],
+    "eamrl_moe_experts_forward": [C.POINTER(MoeExperts), _vp],
+    "eamrl_moe_experts_backward": [C.POINTER(MoeExperts), _vp],
     "eamrl_math_probe": [_i32, _vp, _vp, _i64, _vp],
     "eamrl_wave_probe": [_i32, _vp, _vp, _vp, _vp, _i64, _vp],
 }
 _RESTYPES = {"eamrl_last_error": C.c_char_p, "eamrl_linear_wgrad_scratch": C.c_int64,
              "eamrl_small_linear_wgrad_scratch": C.c_int64, "eamrl_batchnorm_backward_scratch": C.c_int64,
-             "eamrl_reeval_scratch_floats": C.c_int64, "eamrl_moe_ffn_scratch": C.c_int64, "eamrl_ea_large_scratch_bytes": C.c_size_t}
+             "eamrl_reeval_scratch_floats": C.c_int64, "eamrl_moe_ffn_scratch": C.c_int64,
+             "eamrl_moe_experts_forward_scratch": C.c_int64, "eamrl_moe_experts_backward_scratch": C.c_int64, "eamrl_ea_large_scratch_bytes": C.c_size_t}
 
 _lib = None
 

@@ -1285,4 +1285,45 @@ __attribute__((visibility("default"))) int eamrl_moe_ffn(const eamrl_moe_layer* 
     return launched(launch_moe_ffn(*m, (hipStream_t)stream), "eamrl_moe_ffn");
 }
 
+__attribute__((visibility("default"))) int64_t eamrl_moe_experts_forward_scratch(int64_t rows, int n_exp, int k)
+{
+    return moe_experts_state_bytes(rows, n_exp, k);
+}
+
+__attribute__((visibility("default"))) int64_t eamrl_moe_experts_backward_scratch(int64_t rows, int n_exp, int k)
+{
+    return moe_experts_bwd_scratch_bytes(rows, n_exp, k);
+}
+
+__attribute__((visibility("default"))) int eamrl_moe_experts_forward(const eamrl_moe_experts* m, void* stream)
+{
+    REQUIRE(m, "eamrl_moe_experts_forward");
+    REQUIRE(m->embed_dim == 128 && m->hidden == 512, "eamrl_moe_experts_forward");
+    REQUIRE(m->n_exp >= 1 && m->n_exp <= 8 && m->k >= 1 && m->k <= m->n_exp, "eamrl_moe_experts_forward");
+    REQUIRE(moe_ffn_supports(m->rows, m->embed_dim, m->hidden, m->n_exp, m->k), "eamrl_moe_experts_forward");
+    if (m->rows == 0) return 0;
+    REQUIRE(m->x && m->sel && m->g && m->W1p && m->b1 && m->W2p && m->b2 && m->y && m->state, "eamrl_moe_experts_forward");
+    REQUIRE(m->state_bytes >= moe_experts_state_bytes(m->rows, m->n_exp, m->k), "eamrl_moe_experts_forward");
+    REQUIRE((((uintptr_t)m->x | (uintptr_t)m->W1p | (uintptr_t)m->W2p | (uintptr_t)m->b2 | (uintptr_t)m->y | (uintptr_t)m->state) & 15) == 0,
+            "eamrl_moe_experts_forward");
+    return launched(launch_moe_experts_forward(*m, (hipStream_t)stream), "eamrl_moe_experts_forward");
+}
+
+__attribute__((visibility("default"))) int eamrl_moe_experts_backward(const eamrl_moe_experts* m, void* stream)
+{
+    REQUIRE(m, "eamrl_moe_experts_backward");
+    REQUIRE(m->embed_dim == 128 && m->hidden == 512, "eamrl_moe_experts_backward");
+    REQUIRE(m->n_exp >= 1 && m->n_exp <= 8 && m->k >= 1 && m->k <= m->n_exp, "eamrl_moe_experts_backward");
+    REQUIRE(moe_ffn_supports(m->rows, m->embed_dim, m->hidden, m->n_exp, m->k), "eamrl_moe_experts_backward");
+    if (m->rows == 0) return 0;
+    REQUIRE(m->x && m->g && m->W1p && m->b1 && m->W1Tp && m->W2Tp && m->dy && m->state && m->scratch, "eamrl_moe_experts_backward");
+    REQUIRE((m->dW1 && m->db1 && m->dW2 && m->db2) || (!m->dW1 && !m->db1 && !m->dW2 && !m->db2), "eamrl_moe_experts_backward");
+    REQUIRE(m->state_bytes >= moe_experts_state_bytes(m->rows, m->n_exp, m->k), "eamrl_moe_experts_backward");
+    REQUIRE(m->scratch_bytes >= moe_experts_bwd_scratch_bytes(m->rows, m->n_exp, m->k), "eamrl_moe_experts_backward");
+    REQUIRE((((uintptr_t)m->x | (uintptr_t)m->W1p | (uintptr_t)m->W1Tp | (uintptr_t)m->W2Tp | (uintptr_t)m->dy | (uintptr_t)m->dx |
+              (uintptr_t)m->dW1 | (uintptr_t)m->db1 | (uintptr_t)m->dW2 | (uintptr_t)m->db2 | (uintptr_t)m->state |
+              (uintptr_t)m->scratch) & 15) == 0, "eamrl_moe_experts_backward");
+    return launched(launch_moe_experts_backward(*m, (hipStream_t)stream), "eamrl_moe_experts_backward");
+}
+
 }  // extern "C"

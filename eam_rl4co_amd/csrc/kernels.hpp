@@ -181,5 +181,16 @@ int launch_ptrnet_rollout(const eamrl_ptrnet& p, int mode, const float* noise, c
 bool moe_ffn_supports(int64_t rows, int E, int F, int n_exp, int k);
 int64_t moe_ffn_scratch_bytes(int64_t rows, int n_exp, int k);
 int launch_moe_ffn(const eamrl_moe_layer& m, hipStream_t st);
+// the experts alone on a given routing, for the training graph: deterministic row lists, grouped expert GEMM, combine; and their
+// backward (data gradients as grouped GEMMs on transposed packs, weight gradients on the grouped k_linear_wgrad of train_gemm.hip)
+int64_t moe_experts_state_bytes(int64_t rows, int n_exp, int k);
+int64_t moe_experts_bwd_scratch_bytes(int64_t rows, int n_exp, int k);
+int launch_moe_experts_forward(const eamrl_moe_experts& m, hipStream_t st);
+int launch_moe_experts_backward(const eamrl_moe_experts& m, hipStream_t st);
+// Linear weight gradient per group of a grouped GEMM (train_gemm.hip): group e owns cnt[e] consecutive rows of dy and x, the
+// counts live in device memory; dW [n_grp][out][in], db [n_grp][out]; an empty group gets zeros
+int64_t grouped_wgrad_scratch(int64_t rows, int n_grp, int out_dim, int in_dim);
+int launch_grouped_wgrad(const float* dy, int64_t ldy, const float* x, int64_t ldx, int64_t rows, const int32_t* cnt, int n_grp,
+                         int out_dim, int in_dim, float* dW, float* db, float* scratch, hipStream_t st);
 
 }  // namespace eamrl

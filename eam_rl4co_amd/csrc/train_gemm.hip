@@ -23,9 +23,10 @@ namespace {
 constexpr int WT = 128;      // block of dW per workgroup (WT x WT)
 constexpr int WK = 16;       // rows per slab
 
-__global__ __launch_bounds__(256, 2) void k_linear_wgrad(const float* __restrict__ dy, int64_t ldy, const float* __restrict__ x,
-                                                         int64_t ldx, int64_t rows, int out_dim, int in_dim,
-                                                         int64_t rows_per_chunk, float* __restrict__ part)
+// one workgroup's 128 x 128 block of dW (and, in the first column of blocks, of db) over the rows r_begin .. r_end - 1, written
+// to the partial block `pp0` of its chunk
+__device__ __forceinline__ void wgrad_block(const float* __restrict__ dy, int64_t ldy, const float* __restrict__ x, int64_t ldx,
+                                            int64_t r_begin, int64_t r_end, int out_dim, int in_dim, float* __restrict__ pp0)
 {
     __shared__ __attribute__((aligned(16))) float As[2][WK][WT];
     __shared__ __attribute__((aligned(16))) float Bs[2][WK][WT];
@@ -33,8 +34,6 @@ __global__ __launch_bounds__(256, 2) void k_linear_wgrad(const float* __restrict
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int oh = wv & 1, ih = wv >> 1;
     const int o0 = blockIdx.x * WT, i0 = blockIdx.y * WT;
-    const int64_t r_begin = (int64_t)blockIdx.z * rows_per_chunk;
-    const int64_t r_end = r_begin + rows_per_chunk < rows ? r_begin + rows_per_chunk : rows;
     const int nslab = (int)((r_end - r_begin + WK - 1) / WK);
     // staging role: rows lr and lr + 8 of the slab, columns 4 c4 .. 4 c4 + 3 of both operands
     const int lr = tid >> 5, c4 = tid & 31;
@@ -88,8 +87,7 @@ __global__ __launch_bounds__(256, 2) void k_linear_wgrad(const float* __restrict
         }
     }
     // partial block of this chunk: tile (a, b) register r of lane l -> row 8 (r >> 2) + 4 (l >> 5) + (r & 3), column l & 31
-    const int64_t pstride = (int64_t)out_dim * in_dim + out_dim;         // per chunk: the block of dW, then db
-    float* pp = part + blockIdx.z * pstride + (int64_t)(o0 + oh * 64) * in_dim + i0 + ih * 64;
+    float* pp = pp0 + (int64_t)(o0 + oh * 64) * in_dim + i0 + ih * 64;       // per chunk: the block of dW, then db
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -103,11 +101,36 @@ __global__ __launch_bounds__(256, 2) void k_linear_wgrad(const float* __restrict
         bs0 += __shfl_xor(bs0, 32);
         bs1 += __shfl_xor(bs1, 32);
         if (lane < 32) {
-            float* bq = part + blockIdx.z * pstride + (int64_t)out_dim * in_dim + o0 + oh * 64 + lane;
+            float* bq = pp0 + (int64_t)out_dim * in_dim + o0 + oh * 64 + lane;
             bq[0] = bs0;
             bq[32] = bs1;
         }
     }
+}
+
+__global__ __launch_bounds__(256, 2) void k_linear_wgrad(const float* __restrict__ dy, int64_t ldy, const float* __restrict__ x,
+                                                         int64_t ldx, int64_t rows, int out_dim, int in_dim,
+                                                         int64_t rows_per_chunk, float* __restrict__ part)
+{
+    const int64_t r_begin = (int64_t)blockIdx.z * rows_per_chunk;
+    const int64_t r_end = r_begin + rows_per_chunk < rows ? r_begin + rows_per_chunk : rows;
+    wgrad_block(dy, ldy, x, ldx, r_begin, r_end, out_dim, in_dim, part + blockIdx.z * ((int64_t)out_dim * in_dim + out_dim));
+}
+
+// The same contraction per group of a grouped GEMM (the experts of moe_ffn.hip): group e owns the rows
+// sum(cnt[0 .. e-1]) .. + cnt[e] - 1 of both operands, the counts are read from device memory, and blockIdx.z = e * nch + chunk.
+// A chunk past the group's last row (an empty group: every chunk) writes a block of zeros, so the reduction needs no counts.
+__global__ __launch_bounds__(256, 2) void k_grouped_wgrad(const float* __restrict__ dy, int64_t ldy, const float* __restrict__ x,
+                                                          int64_t ldx, const int32_t* __restrict__ cnt, int out_dim, int in_dim,
+                                                          int nch, float* __restrict__ part)
+{
+    const int e = blockIdx.z / nch, ch = blockIdx.z - e * nch;
+    int64_t seg = 0;
+    for (int i = 0; i < e; ++i) seg += cnt[i];
+    const int64_t c = cnt[e];
+    const int64_t rpc = ((c + nch - 1) / nch + WK - 1) / WK * WK;
+    const int64_t b = ch * rpc < c ? ch * rpc : c, t = (ch + 1) * rpc < c ? (ch + 1) * rpc : c;
+    wgrad_block(dy, ldy, x, ldx, seg + b, seg + t, out_dim, in_dim, part + blockIdx.z * ((int64_t)out_dim * in_dim + out_dim));
 }
 
 // out[e] = sum_c part[c][e]: 64 float4 elements per workgroup, the chunks dealt to four thread groups (four loads in
@@ -118,6 +141,10 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce(const float* __restrict__ 
     __shared__ float4 red[4][64];
     const int e = threadIdx.x & 63, g = threadIdx.x >> 6;
     const int64_t i = (int64_t)blockIdx.x * 64 + e;
+    // blockIdx.y: the group of a grouped weight gradient (its nchunks partial blocks, its dW, its db); 0 for a single Linear
+    part += (int64_t)blockIdx.y * nchunks * n4 * 4;
+    dW += (int64_t)blockIdx.y * nw4 * 4;
+    if (db) db += (int64_t)blockIdx.y * (n4 - nw4) * 4;
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
     if (i < n4) {
         const float4* p = reinterpret_cast<const float4*>(part) + i;
@@ -173,6 +200,31 @@ int launch_linear_wgrad(const float* dy, int64_t ldy, const float* x, int64_t ld
                        in_dim, rpc, scratch);
     const int64_t nw4 = (int64_t)out_dim * in_dim / 4, n4 = nw4 + out_dim / 4;
     hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)((n4 + 63) / 64)), dim3(256), 0, st, scratch, dW, db, nw4, n4, nch);
+    return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
+}
+
+// chunks per group: two workgroups per CU over all groups' blocks, no more chunks than 64-row pieces of the rows
+int grouped_wgrad_chunks(int64_t rows, int n_grp)
+{
+    int64_t n = 128 / n_grp;
+    const int64_t most = (rows + 4 * WK - 1) / (4 * WK);
+    if (n > most) n = most;
+    return (int)(n < 1 ? 1 : n);
+}
+
+int64_t grouped_wgrad_scratch(int64_t rows, int n_grp, int out_dim, int in_dim)
+{
+    return (int64_t)n_grp * grouped_wgrad_chunks(rows, n_grp) * ((int64_t)out_dim * in_dim + out_dim);
+}
+
+int launch_grouped_wgrad(const float* dy, int64_t ldy, const float* x, int64_t ldx, int64_t rows, const int32_t* cnt, int n_grp,
+                         int out_dim, int in_dim, float* dW, float* db, float* scratch, hipStream_t st)
+{
+    const int nch = grouped_wgrad_chunks(rows, n_grp);
+    hipLaunchKernelGGL(k_grouped_wgrad, dim3(out_dim / WT, in_dim / WT, n_grp * nch), dim3(256), 0, st, dy, ldy, x, ldx, cnt,
+                       out_dim, in_dim, nch, scratch);
+    const int64_t nw4 = (int64_t)out_dim * in_dim / 4, n4 = nw4 + out_dim / 4;
+    hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)((n4 + 63) / 64), n_grp), dim3(256), 0, st, scratch, dW, db, nw4, n4, nch);
     return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
 }
 

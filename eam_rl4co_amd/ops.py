@@ -505,6 +505,118 @@ def moe_ffn(x, w_gate, experts, k, w_noise=None, noise=None, residual=None, bn=N
     return (out, sel, g) if return_routing else out
 
 
+def moe_experts_forward_scratch(rows, n_exp, k) -> int:
+    """Bytes of the state `moe_experts_forward` leaves for the backward (eamrl_moe_experts_forward_scratch; host only):
+    64 + 16 * ceil(rows * n_exp / 4) + 512 * rows * k + 16 * ceil(rows * k / 16) + 32 * ceil(rows / 256), or -1."""
+    return int(_lib.load().eamrl_moe_experts_forward_scratch(int(rows), int(n_exp), int(k)))
+
+
+def moe_experts_backward_scratch(rows, n_exp, k) -> int:
+    """Bytes of device scratch `moe_experts_backward` needs (eamrl_moe_experts_backward_scratch; host only):
+    5632 * rows * k + 264192 * n_exp * max(1, min(128 // n_exp, ceil(rows * k / 64))), or -1."""
+    return int(_lib.load().eamrl_moe_experts_backward_scratch(int(rows), int(n_exp), int(k)))
+
+
+def pack_moe_experts_backward(W1, W2, out=None):
+    """The packs of the experts' backward next to those of `pack_moe_experts`: W1Tp [n_exp, 65536] = pack_linear_weight of
+    W1^T [128, 512] (dx = dHid W1), W2Tp [n_exp, 65536] = of W2^T [512, 128] (dHid = dO W2).  out: such a dict to refresh."""
+    n = len(W1)
+    dev = W1[0].device
+    if out is None:
+        out = {"W1Tp": torch.empty(n, MOE_EMBED_DIM * MOE_HIDDEN, device=dev), "W2Tp": torch.empty(n, MOE_HIDDEN * MOE_EMBED_DIM, device=dev)}
+    for e in range(n):
+        _chk(W1[e], "expert lins.0.weight", torch.float32, (MOE_HIDDEN, MOE_EMBED_DIM))
+        _chk(W2[e], "expert lins.1.weight", torch.float32, (MOE_EMBED_DIM, MOE_HIDDEN))
+        pack_linear_weight(W1[e].t().contiguous(), out=out["W1Tp"][e])
+        pack_linear_weight(W2[e].t().contiguous(), out=out["W2Tp"][e])
+    return out
+
+
+def _moe_experts_struct(what, x, g, experts, names):
+    """(struct, rows, n_exp, k) of eamrl_moe_experts with x, g and the packs `names` of `experts` checked and bound."""
+    _chk(x, "x", torch.float32)
+    _chk(g, "gates", torch.float32)
+    E = x.shape[-1]
+    rows = x.numel() // max(E, 1)
+    if E != MOE_EMBED_DIM:
+        raise NotImplementedError(f"{what}: embed_dim {E}; the kernels are built for embed_dim {MOE_EMBED_DIM}")
+    n_exp = experts["b1"].shape[0] if isinstance(experts.get("b1"), torch.Tensor) and experts["b1"].dim() == 2 else -1
+    k = g.shape[1] if g.dim() == 2 else -1
+    if not 1 <= k <= n_exp <= MOE_MAX_EXPERTS:
+        raise NotImplementedError(f"{what}: k = {k}, num_experts = {n_exp}; built for 1 <= k <= num_experts <= {MOE_MAX_EXPERTS}")
+    _chk(g, "gates", torch.float32, (rows, k))
+    shapes = {"W1p": (n_exp, MOE_HIDDEN * E), "b1": (n_exp, MOE_HIDDEN), "W2p": (n_exp, E * MOE_HIDDEN), "b2": (n_exp, E),
+              "W1Tp": (n_exp, E * MOE_HIDDEN), "W2Tp": (n_exp, MOE_HIDDEN * E)}
+    m = _lib.MoeExperts()
+    for nm in names:
+        setattr(m, nm, _chk(experts[nm], f"experts['{nm}']", torch.float32, shapes[nm]).data_ptr())
+    m.x, m.g = x.data_ptr(), g.data_ptr()
+    m.rows, m.embed_dim, m.hidden, m.n_exp, m.k = rows, E, MOE_HIDDEN, n_exp, k
+    return m, rows, n_exp, k
+
+
+def moe_experts_forward(x, sel, g, experts):
+    """The selected experts on a GIVEN routing (eamrl_moe_experts_forward): y[row] = sum over the row's slots, in ascending
+    expert index sel[row, j], of g[row, j] * expert(x[row]) -- with the (sel, g) `moe_ffn` returned, `moe_ffn`'s y bit for bit.
+    x [..., 128]; sel [rows, k] int8; g [rows, k]; experts: the dict of `pack_moe_experts`.  Returns (y, state): `state` (a
+    uint8 tensor: row counts and row lists in ascending row order, per-slot expert outputs, the checked routing) is what
+    `moe_experts_backward` reads.  A `sel` entry outside 0 .. n_exp - 1 or repeated within its row is dropped on the device
+    (no contribution, zero gate gradient) and counted: `moe_experts_dropped(state)`."""
+    lib = _lib.load()
+    _chk(x, "x", torch.float32)
+    m, rows, n_exp, k = _moe_experts_struct("moe_experts_forward", x, g, experts, ("W1p", "b1", "W2p", "b2"))
+    _chk(sel, "sel", torch.int8, (rows, k))
+    y = torch.empty_like(x)
+    need = lib.eamrl_moe_experts_forward_scratch(rows, n_exp, k)
+    if need < 0:
+        raise NotImplementedError(f"moe_experts_forward: {rows} rows are above the 2^24 rows of one call")
+    state = torch.empty(need, device=x.device, dtype=torch.uint8)
+    if rows == 0:
+        return y, state
+    m.sel, m.y, m.state, m.state_bytes = sel.data_ptr(), y.data_ptr(), state.data_ptr(), need
+    _lib.check(lib.eamrl_moe_experts_forward(C.byref(m), _stream(x)), "eamrl_moe_experts_forward")
+    return y, state
+
+
+def moe_experts_dropped(state) -> int:
+    """How many `sel` entries the forward that wrote `state` dropped (counter word 15; synchronises with the host)."""
+    return int(state[60:64].view(torch.int32).item()) if state.numel() >= 64 else 0
+
+
+def moe_experts_backward(dy, x, g, experts, state, need_dx=True, need_dg=True, need_weight_grads=True):
+    """Backward of `moe_experts_forward` (eamrl_moe_experts_backward) from dy [..., 128] and the forward's x, g, `state`:
+    -> (dx like x, dg [rows, k], dW1 [n_exp, 512, 128], db1 [n_exp, 512], dW2 [n_exp, 128, 512], db2 [n_exp, 128]); the ones not
+    asked for are None.  experts: the dicts of `pack_moe_experts` and `pack_moe_experts_backward` merged (W1p, b1, W1Tp, W2Tp are
+    read).  An expert without rows gets zero gradients; two calls on the same inputs give the same bits."""
+    lib = _lib.load()
+    _chk(dy, "dy", torch.float32, tuple(x.shape))
+    m, rows, n_exp, k = _moe_experts_struct("moe_experts_backward", x, g, experts, ("W1p", "b1", "W1Tp", "W2Tp"))
+    need_state = lib.eamrl_moe_experts_forward_scratch(rows, n_exp, k)
+    need = lib.eamrl_moe_experts_backward_scratch(rows, n_exp, k)
+    if need < 0:
+        raise NotImplementedError(f"moe_experts_backward: {rows} rows are above the 2^24 rows of one call")
+    _chk(state, "state", torch.uint8, (need_state,))
+    dev = x.device
+    dx = torch.empty_like(x) if need_dx else None
+    dg = torch.empty(rows, k, device=dev, dtype=torch.float32) if need_dg else None
+    dW1 = db1 = dW2 = db2 = None
+    if need_weight_grads:
+        dW1, db1 = torch.empty(n_exp, MOE_HIDDEN, MOE_EMBED_DIM, device=dev), torch.empty(n_exp, MOE_HIDDEN, device=dev)
+        dW2, db2 = torch.empty(n_exp, MOE_EMBED_DIM, MOE_HIDDEN, device=dev), torch.empty(n_exp, MOE_EMBED_DIM, device=dev)
+    if rows == 0:
+        for t in (dW1, db1, dW2, db2):
+            if t is not None:
+                t.zero_()
+        return dx, dg, dW1, db1, dW2, db2
+    scratch = _moe_scratch(dev, need)
+    m.dy, m.state, m.state_bytes, m.scratch, m.scratch_bytes = dy.data_ptr(), state.data_ptr(), need_state, scratch.data_ptr(), need
+    for nm, t in (("dx", dx), ("dg", dg), ("dW1", dW1), ("db1", db1), ("dW2", dW2), ("db2", db2)):
+        if t is not None:
+            setattr(m, nm, t.data_ptr())
+    _lib.check(lib.eamrl_moe_experts_backward(C.byref(m), _stream(x)), "eamrl_moe_experts_backward")
+    return dx, dg, dW1, db1, dW2, db2
+
+
 def encoder_fused_supported(M, E, H, ff_hidden, nlayers) -> bool:
     return bool(_lib.load().eamrl_encoder_fused_supported(int(M), int(E), int(H), int(ff_hidden), int(nlayers)))
 

@@ -206,8 +206,9 @@ class MoE(nn.Module):
     """Parameters of the reference's sparsely gated mixture of experts (nn/moe.py:114-146, its names and its initialisation:
     `w_gate` = `w_noise` = 0, default Linear experts, buffers `mean` / `std`) as the feed-forward sublayer of an encoder layer
     (MVMoE, Zhou et al. 2024).  `sublayer` is the native forward (ops.moe_ffn: gate, grouped expert GEMM, combine); under
-    autograd the sublayer is the torch expression `train.moe_autograd`.  Extra keyword arguments (e.g. `routing_level`) are
-    swallowed, as the reference's constructor does."""
+    autograd the gate is a torch expression and the experts run on `train._MoEExpertsFn` (native sparse forward and backward;
+    `train.moe_autograd`, the all-torch expression, off the GPU or with EAMRL_MOE_NATIVE_BACKWARD=0).  Extra keyword arguments
+    (e.g. `routing_level`) are swallowed, as the reference's constructor does."""
 
     def __init__(self, input_size, output_size, num_neurons=(), hidden_act="ReLU", out_bias=True, num_experts=4, k=2,
                  noisy_gating=True, **kwargs):
@@ -243,6 +244,20 @@ class MoE(nn.Module):
                                            [ex.lins[1].weight.detach() for ex in self.experts],
                                            [ex.lins[1].bias.detach() for ex in self.experts], out=buf)
             self.__dict__["_packed"] = slot = (key, buf)
+        return slot[1]
+
+    def packed_experts_backward(self):
+        """`packed_experts()` plus the transposed packs the experts' native backward reads (ops.pack_moe_experts_backward), kept
+        and refreshed by parameter version in the same way: the operand dict of train._MoEExpertsFn."""
+        fwd = self.packed_experts()
+        key = self.__dict__["_packed"][0]
+        slot = self.__dict__.get("_packed_bwd")
+        if slot is None or slot[0] != key:
+            buf = None if slot is None or slot[1]["W1Tp"].device != fwd["W1p"].device else {n: slot[1][n] for n in ("W1Tp", "W2Tp")}
+            with torch.no_grad():
+                buf = ops.pack_moe_experts_backward([ex.lins[0].weight.detach() for ex in self.experts],
+                                                    [ex.lins[1].weight.detach() for ex in self.experts], out=buf)
+            self.__dict__["_packed_bwd"] = slot = (key, dict(fwd, **buf))
         return slot[1]
 
     def draw_noise(self, rows, device):

@@ -386,6 +386,73 @@ def moe_autograd(moe, h, training: bool):
     return y.view_as(h)
 
 
+class _MoEExpertsFn(torch.autograd.Function):
+    """The selected experts of an MoE sublayer and their gate-weighted sum on a given routing: forward eamrl_moe_experts_forward
+    (the rollout's expert and combine kernels on row lists in ascending row order), backward eamrl_moe_experts_backward.  Only
+    the selected (row, expert) pairs are computed and only their outputs [rows, k, 128] are kept; the hidden activations are
+    recomputed in the backward by the forward's own tile code.
+
+    apply(x [rows, 128], gates [rows, k], sel [rows, k] (any integer dtype), packs, *params) -> y [rows, 128], with params = the
+    n_exp lins.0.weight, then the n_exp lins.0.bias, lins.1.weight, lins.1.bias, and packs = the operand dict of
+    MoE.packed_experts_backward() for those parameters (None: packed here).  Gradients: x, gates and every parameter; an expert
+    that received no row gets zeros, not None."""
+
+    @staticmethod
+    def forward(ctx, x, gates, sel, packs, *params):
+        from . import ops
+
+        n = len(params) // 4
+        if packs is None:
+            W1, b1, W2, b2 = (list(p.detach() for p in params[i * n:(i + 1) * n]) for i in range(4))
+            packs = dict(ops.pack_moe_experts(W1, b1, W2, b2), **ops.pack_moe_experts_backward(W1, W2))
+        xc, gc = x.contiguous(), gates.contiguous()
+        y, state = ops.moe_experts_forward(xc, sel.to(torch.int8).contiguous(), gc, packs)
+        ctx.save_for_backward(xc, gc, state)
+        ctx.packs, ctx.n = packs, n
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        from . import ops
+
+        x, g, state = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        n = ctx.n
+        dx, dg, dW1, db1, dW2, db2 = ops.moe_experts_backward(dy.contiguous(), x, g, ctx.packs, state, need_dx=need[0], need_dg=need[1],
+                                                              need_weight_grads=any(need[4:]))
+        grads = [None] * (4 * n)
+        if dW1 is not None:
+            for i, t in enumerate((dW1, db1, dW2, db2)):
+                for e in range(n):
+                    if need[4 + i * n + e]:
+                        grads[i * n + e] = t[e]
+        return (dx, dg, None, None, *grads)
+
+
+def moe_native_backward(moe, h) -> bool:
+    """Whether the MoE sublayer of the training graph runs on `_MoEExpertsFn`: CUDA float32 tensors, unless
+    EAMRL_MOE_NATIVE_BACKWARD=0 asks for the torch expression `moe_autograd`."""
+    return (h.is_cuda and h.dtype == torch.float32 and moe.w_gate.is_cuda and moe.w_gate.dtype == torch.float32
+            and os.environ.get("EAMRL_MOE_NATIVE_BACKWARD", "1") != "0")
+
+
+def moe_autograd_native(moe, h, training: bool):
+    """`moe_autograd` with the experts on the native sparse path: the gate is the same torch expression (the same draw from the
+    same generator state, the same stable sort, so the same routing), the selected experts, their weighted sum and all their
+    gradients are `_MoEExpertsFn` -- k experts' arithmetic and saved activations per row instead of num_experts'."""
+    x = h.reshape(-1, h.shape[-1])
+    logits = x @ moe.w_gate
+    if moe.noisy_gating and training:
+        std = F.softplus(x @ moe.w_noise) + 1e-2
+        logits = logits + torch.randn_like(logits) * std
+    p = torch.softmax(logits, -1)
+    top_p, top_i = torch.sort(p, dim=-1, descending=True, stable=True)
+    top_p, top_i = top_p[:, :moe.k], top_i[:, :moe.k]
+    top_g = top_p / (top_p.sum(1, keepdim=True) + 1e-6)
+    params = [getattr(ex.lins[i], nm) for i, nm in ((0, "weight"), (0, "bias"), (1, "weight"), (1, "bias")) for ex in moe.experts]
+    return _MoEExpertsFn.apply(x, top_g, top_i, moe.packed_experts_backward(), *params).view_as(h)
+
+
 def encode_autograd(policy, td):
     enc = policy.encoder
     from .policy import GraphHeterogeneousAttentionEncoder, MoE
@@ -404,7 +471,8 @@ def encode_autograd(policy, td):
         att = _self_attention(_linear(h, mha.Wqkv.weight, mha.Wqkv.bias), B, N, E, H)
         h = _normalize(layer[1], _linear(att, mha.out_proj.weight, mha.out_proj.bias, residual=h), training, single)
         if isinstance(ffn, MoE):
-            h = _normalize(layer[3], h + moe_autograd(ffn, h, training), training, single)
+            moe_fn = moe_autograd_native if moe_native_backward(ffn, h) else moe_autograd
+            h = _normalize(layer[3], h + moe_fn(ffn, h, training), training, single)
             continue
         x = h
         for lin in ffn.lins[:-1]:

@@ -1007,6 +1007,59 @@ typedef struct eamrl_moe_layer {
 int64_t eamrl_moe_ffn_scratch(int64_t rows, int n_exp, int k);
 int eamrl_moe_ffn(const eamrl_moe_layer* m, void* stream);
 
+/* The experts of that sublayer on a routing the caller gives, and their backward: the sparse half of the training graph (the
+ * gate stays with the caller, which differentiates it).
+ *
+ * eamrl_moe_experts_forward:   y[row] = sum over the row's slots j, in ascending expert index e = sel[row][j], of
+ *   g[row][j] * (b2_e + W2_e relu(b1_e + W1_e x[row]))   -- the expert and combine arithmetic of eamrl_moe_ffn (the same MFMA
+ *   chains, its combine kernel), so with the (sel, g) eamrl_moe_ffn returned, y equals its y (res = NULL, no norm) bit for bit.
+ *   It fills `state` for the backward: 16 int32 counters (rows per expert; word 15 counts the dropped `sel` entries), the
+ *   experts' row lists in ASCENDING ROW ORDER (per-workgroup counts, an exclusive scan, a ballot-ranked fill: no order depends on
+ *   scheduling), the per-slot expert outputs o [rows][k][128] and the checked copy of sel.
+ *   A `sel` entry outside 0 .. n_exp - 1, or one that repeats an earlier entry of its row, is DROPPED on the device: the slot
+ *   contributes nothing to y, dx or any weight gradient, its dg is 0, and counter word 15 of `state` is incremented; nothing is
+ *   read or written out of bounds and the host is not told (no synchronisation).
+ * eamrl_moe_experts_backward:  from dy [rows][128] and the forward's `state`
+ *   dg[row][j] = <dy[row], o[row][j]>
+ *   per expert e over its own row list:  dO = g * dy,  dHid = (dO W2_e) * [hid > 0],  dW2_e = dO^T hid,  db2_e = sum dO,
+ *                                        dW1_e = dHid^T x,  db1_e = sum dHid
+ *   dx[row]    = sum over the row's slots in ascending expert index of dHid W1_e
+ *   hid = relu(b1_e + W1_e x) is RECOMPUTED by the forward's own tile code (same MFMA chain, same bits, so the same mask);
+ *   nothing of size [rows * k][512] survives the forward.  An expert without rows gets zero gradients.
+ *   dx, dg may be NULL (not wanted); dW1, db1, dW2, db2 are all NULL or all set.
+ *   Same inputs give the same bits: lists in row order, every cross-workgroup sum as fixed-order partials plus a reduce.
+ * Shapes: embed_dim 128, hidden 512, 1 <= k <= n_exp <= 8, rows <= 2^24 (rows == 0: nothing is launched, 0 is returned).
+ *   x, y, dy, dx [rows][128]; sel [rows][k] int8; g, dg [rows][k]; W1p, W2p, b1, b2 as in eamrl_moe_layer;
+ *   W1Tp [n_exp][128 * 512]: eamrl_pack_linear_weight of W1_e^T [128][512];  W2Tp [n_exp][512 * 128]: of W2_e^T [512][128]
+ *   (backward only);  dW1 [n_exp][512][128], db1 [n_exp][512], dW2 [n_exp][128][512], db2 [n_exp][128].
+ *   The forward reads x, sel, g, W1p, b1, W2p, b2 and writes y, state; the backward reads x, g, W1p, b1, W1Tp, W2Tp, dy, state.
+ * state:   eamrl_moe_experts_forward_scratch(rows, n_exp, k) bytes, 16-byte aligned, kept by the caller until the backward
+ *   = 64 + 16 * ceil(rows * n_exp / 4) + 512 * rows * k + 16 * ceil(rows * k / 16) + 32 * ceil(rows / 256)
+ * scratch: eamrl_moe_experts_backward_scratch(rows, n_exp, k) bytes, 16-byte aligned, free after the call
+ *   = 5632 * rows * k + 264192 * n_exp * nch,  nch = max(1, min(128 / n_exp, ceil(rows * k / 64)))
+ *   (compact x, dO, hid, dHid in list order, per-slot dx, the weight gradients' partial blocks);  -1: shape not supported.
+ * All products on v_mfma_f32_16x16x4_f32 / v_mfma_f32_32x32x2_f32; no floating-point atomics, no host synchronisation; grids
+ * depend on (rows, n_exp, k) only.  Everything is checked before the first launch. */
+typedef struct eamrl_moe_experts {
+    const float* x;
+    const int8_t* sel;
+    const float* g;
+    const float* W1p; const float* b1; const float* W2p; const float* b2;
+    const float* W1Tp; const float* W2Tp;
+    float* y;
+    void* state; int64_t state_bytes;
+    const float* dy;
+    float* dx; float* dg;
+    float* dW1; float* db1; float* dW2; float* db2;
+    void* scratch; int64_t scratch_bytes;
+    int64_t rows;
+    int32_t embed_dim, hidden, n_exp, k;
+} eamrl_moe_experts;
+int64_t eamrl_moe_experts_forward_scratch(int64_t rows, int n_exp, int k);
+int64_t eamrl_moe_experts_backward_scratch(int64_t rows, int n_exp, int k);
+int eamrl_moe_experts_forward(const eamrl_moe_experts* m, void* stream);
+int eamrl_moe_experts_backward(const eamrl_moe_experts* m, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
