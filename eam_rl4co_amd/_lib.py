@@ -135,6 +135,7 @@ PROTOTYPES = {
     "eamrl_batchnorm_backward_scratch": [_i64, _i32],
     "eamrl_batchnorm_backward": [_vp, _vp, _vp, _vp, _vp, _f32, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp],
     "eamrl_mha_encoder": [_vp, _vp, _i64, _i32, _i32, _i32, _vp],
+    "eamrl_mha_encoder_variant": [_vp, _vp, _i64, _i32, _i32, _i32],
     "eamrl_mha_encoder_backward_supported": [_i32, _i32, _i32],
     "eamrl_mha_encoder_backward": [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp],
     "eamrl_hetero_mha_supported": [_i32, _i32, _i32],

@@ -319,6 +319,14 @@ __attribute__((visibility("default"))) int eamrl_mha_encoder(const float* qkv, f
     return launched(launch_mha_encoder(qkv, out, B, N, E, H, (hipStream_t)stream), "eamrl_mha_encoder");
 }
 
+__attribute__((visibility("default"))) int eamrl_mha_encoder_variant(const float* qkv, const float* out, int64_t B, int N, int E,
+                                                                    int H)
+{
+    REQUIRE(qkv && out, "eamrl_mha_encoder_variant");
+    REQUIRE(B >= 0 && N > 0 && E > 0 && H > 0 && E % H == 0, "eamrl_mha_encoder_variant");
+    return mha_encoder_variant(qkv, out, B, N, E, H);
+}
+
 __attribute__((visibility("default"))) int eamrl_normalize(float* x, int64_t B, int N, int E, int kind,
                                                           const float* gamma, const float* beta, const float* mean,
                                                           const float* var, float eps, void* stream)

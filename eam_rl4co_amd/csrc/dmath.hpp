@@ -438,14 +438,31 @@ __device__ __forceinline__ float lane_groups_sum(float v)
     auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
     return __uint_as_float(s[0]) + __uint_as_float(s[1]);
 }
-__device__ __forceinline__ float wave_tree_sum(float v)
+// The four DPP levels of a 16-lane row (levels 1, 2, 4, 8 of the butterfly), stated once for every combine: each lane of a row
+// ends with the row's result.  (The _dpp suffix tells them from row16_sum of mfma_tile.hpp, which goes through __shfl_xor.)
+__device__ __forceinline__ float row_sum_dpp(float v)
 {
     v = v + dpp_f<DPP_XOR1>(v);
     v = v + dpp_f<DPP_XOR2>(v);
     v = v + dpp_f<DPP_HALF_MIRROR>(v);
-    v = v + dpp_f<DPP_MIRROR>(v);
-    return lane_groups_sum(v);
+    return v + dpp_f<DPP_MIRROR>(v);
 }
+__device__ __forceinline__ int row_min_dpp(int v)
+{
+    v = min(v, dpp_i<DPP_XOR1>(v));
+    v = min(v, dpp_i<DPP_XOR2>(v));
+    v = min(v, dpp_i<DPP_HALF_MIRROR>(v));
+    return min(v, dpp_i<DPP_MIRROR>(v));
+}
+// fmaxf, not vmax_raw: for the gradient kernels, which are not bit-pinned (row_max_dpp below is the bit-exact path's)
+__device__ __forceinline__ float row_fmax_dpp(float v)
+{
+    v = fmaxf(v, dpp_f<DPP_XOR1>(v));
+    v = fmaxf(v, dpp_f<DPP_XOR2>(v));
+    v = fmaxf(v, dpp_f<DPP_HALF_MIRROR>(v));
+    return fmaxf(v, dpp_f<DPP_MIRROR>(v));
+}
+__device__ __forceinline__ float wave_tree_sum(float v) { return lane_groups_sum(row_sum_dpp(v)); }
 
 // max(a, b) as the single v_max_f32 it is (the builtin adds two canonicalising v_max x,x per call)
 __device__ __forceinline__ float vmax_raw(float a, float b)
@@ -481,14 +498,17 @@ __device__ __forceinline__ float lane_groups_max(float v)
     auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
     return vmax_raw(__uint_as_float(s[0]), __uint_as_float(s[1]));
 }
-__device__ __forceinline__ float wave_max(float v)
+// the four DPP levels of a 16-lane row on vmax_raw (the control words of DPP_XOR1, DPP_XOR2, DPP_HALF_MIRROR, DPP_MIRROR as
+// the assembler spells them)
+__device__ __forceinline__ float row_max_dpp(float v)
 {
     EAMRL_MAX_DPP(v, "quad_perm:[1,0,3,2]");
     EAMRL_MAX_DPP(v, "quad_perm:[2,3,0,1]");
     EAMRL_MAX_DPP(v, "row_half_mirror");
     EAMRL_MAX_DPP(v, "row_mirror");
-    return lane_groups_max(v);
+    return v;
 }
+__device__ __forceinline__ float wave_max(float v) { return lane_groups_max(row_max_dpp(v)); }
 
 // argmax with torch.argmax's tie rule (lowest index); every lane gets the winner.
 __device__ __forceinline__ void argmax_pick(float& v, int& i, float ov, int oi)

@@ -12,6 +12,7 @@
 // Reference: rl4co/models/zoo/am/encoder.py:70-91, rl4co/models/nn/graph/attnnet.py:16-103,
 // rl4co/models/nn/attention.py:66-136, rl4co/models/nn/ops.py:32-56, rl4co/models/nn/mlp.py:52-61,
 // rl4co/models/nn/env_embeddings/init.py:55-68,115-138, rl4co/models/zoo/am/decoder.py:206-235.
+#include <climits>
 #include <cstdlib>
 
 #include "kernels.hpp"
@@ -544,13 +545,62 @@ __global__ __launch_bounds__(128) void k_mha_encoder(const float* qkv, float* ou
     }
 }
 
-// Register-blocked variant for D = 16: one block = (instance, group of 4 heads), one thread = TWO query rows of one
-// head, so every K / V row fetched from LDS feeds two fma chains and the kernel is VALU-bound instead of
-// LDS-bound (a broadcast ds_read_b128 still costs 4 LDS cycles).  Same per-row arithmetic as k_mha_encoder.
+// ---- the row pair of the two blocked kernels (D = 16): a thread owns TWO query rows of one head, side by side in f32x2, so every
+// K / V row fetched from LDS feeds two fma chains on packed fp32 math.  Same per-row arithmetic as k_mha_encoder.
+constexpr int MHA_D = 16, MHA_HG = 4, MHA_W = MHA_HG * MHA_D;      // 4 heads per block: 64 floats of K (and of V) per node in LDS
+// q of the rows at p0 and p1.  1/sqrt(16) folded into q: a power of two, so chain(0.25 q, k) == 0.25 chain(q, k) bit for bit
+__device__ __forceinline__ void pair_load_q(f32x2 (&q2)[MHA_D], const float* p0, const float* p1)
+{
+#pragma unroll
+    for (int d = 0; d < MHA_D; d += 4) {
+        const float4 a = *reinterpret_cast<const float4*>(p0 + d);
+        const float4 c = *reinterpret_cast<const float4*>(p1 + d);
+        q2[d] = (f32x2){a.x, c.x} * 0.25f; q2[d + 1] = (f32x2){a.y, c.y} * 0.25f;
+        q2[d + 2] = (f32x2){a.z, c.z} * 0.25f; q2[d + 3] = (f32x2){a.w, c.w} * 0.25f;
+    }
+}
+// the pair's scores against the key row kr (LDS): the chain over d ascending
+__device__ __forceinline__ f32x2 pair_score(const f32x2 (&q2)[MHA_D], const float* kr)
+{
+    f32x2 a2 = splat2(0.0f);
+#pragma unroll
+    for (int d = 0; d < MHA_D; d += 4) {
+        const float4 kk = *reinterpret_cast<const float4*>(kr + d);
+        a2 = pk_fma(q2[d], splat2(kk.x), a2);
+        a2 = pk_fma(q2[d + 1], splat2(kk.y), a2);
+        a2 = pk_fma(q2[d + 2], splat2(kk.z), a2);
+        a2 = pk_fma(q2[d + 3], splat2(kk.w), a2);
+    }
+    return a2;
+}
+// o2 += w2 x the value row vr (LDS)
+__device__ __forceinline__ void pair_accumulate(f32x2 (&o2)[MHA_D], const f32x2 w2, const float* vr)
+{
+#pragma unroll
+    for (int d = 0; d < MHA_D; d += 4) {
+        const float4 vv = *reinterpret_cast<const float4*>(vr + d);
+        o2[d] = pk_fma(w2, splat2(vv.x), o2[d]);
+        o2[d + 1] = pk_fma(w2, splat2(vv.y), o2[d + 1]);
+        o2[d + 2] = pk_fma(w2, splat2(vv.z), o2[d + 2]);
+        o2[d + 3] = pk_fma(w2, splat2(vv.w), o2[d + 3]);
+    }
+}
+// the output row of side S of the pair: o / Z, an IEEE division per element (not a product with a reciprocal)
+template <int S>
+__device__ __forceinline__ void pair_store_row(float* op, const f32x2 (&o2)[MHA_D], const f32x2 Z2)
+{
+    const float Z = Z2[S];
+#pragma unroll
+    for (int d = 0; d < MHA_D; d += 4)
+        *reinterpret_cast<float4*>(op + d) = make_float4(o2[d][S] / Z, o2[d + 1][S] / Z, o2[d + 2][S] / Z, o2[d + 3][S] / Z);
+}
+
+// Register-blocked variant for D = 16: one block = (instance, group of 4 heads), one thread = a row pair of one head: the
+// kernel is VALU-bound instead of LDS-bound (a broadcast ds_read_b128 still costs 4 LDS cycles).
 __global__ __launch_bounds__(256) void k_mha_encoder_x2(const float* __restrict__ qkv, float* __restrict__ out, int N, int E,
                                                         int H)
 {
-    constexpr int D = 16, HG = 4, W = HG * D;          // 64 floats of K (and of V) per node in LDS
+    constexpr int D = MHA_D, HG = MHA_HG, W = MHA_W;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* ks = reinterpret_cast<float*>(smem);        // [N][W]
     float* vs = ks + (size_t)N * W;                    // [N][W]
@@ -571,32 +621,13 @@ __global__ __launch_bounds__(256) void k_mha_encoder_x2(const float* __restrict_
     const int i0 = pr, i1 = pr + P;                     // rows i0 < P <= i1
     const bool has1 = i1 < N;
     const int i1c = has1 ? i1 : N - 1;
-    f32x2 q2[D];                                        // (row i0, row i1) side by side: packed fp32 math
-    {
-        const float* p0 = base + (int64_t)i0 * 3 * E + (h0 + hh) * D;
-        const float* p1 = base + (int64_t)i1c * 3 * E + (h0 + hh) * D;
-#pragma unroll
-        for (int d = 0; d < D; d += 4) {
-            const float4 a = *reinterpret_cast<const float4*>(p0 + d);
-            const float4 c = *reinterpret_cast<const float4*>(p1 + d);
-            // 1/sqrt(16) folded into q: a power of two, so chain(0.25 q, k) == 0.25 chain(q, k) bit for bit
-            q2[d] = (f32x2){a.x, c.x} * 0.25f; q2[d + 1] = (f32x2){a.y, c.y} * 0.25f;
-            q2[d + 2] = (f32x2){a.z, c.z} * 0.25f; q2[d + 3] = (f32x2){a.w, c.w} * 0.25f;
-        }
-    }
+    f32x2 q2[D];
+    pair_load_q(q2, base + (int64_t)i0 * 3 * E + (h0 + hh) * D, base + (int64_t)i1c * 3 * E + (h0 + hh) * D);
     const float* kh = ks + hh * D;
     const float* vh = vs + hh * D;
     f32x2 m2 = splat2(-INFINITY);
     for (int j = 0; j < N; ++j) {
-        f32x2 a2 = splat2(0.0f);
-#pragma unroll
-        for (int d = 0; d < D; d += 4) {
-            const float4 kk = *reinterpret_cast<const float4*>(kh + j * W + d);
-            a2 = pk_fma(q2[d], splat2(kk.x), a2);
-            a2 = pk_fma(q2[d + 1], splat2(kk.y), a2);
-            a2 = pk_fma(q2[d + 2], splat2(kk.z), a2);
-            a2 = pk_fma(q2[d + 3], splat2(kk.w), a2);
-        }
+        const f32x2 a2 = pair_score(q2, kh + j * W);
         m2.x = __builtin_fmaxf(m2.x, a2.x);
         m2.y = __builtin_fmaxf(m2.y, a2.y);
     }
@@ -605,41 +636,13 @@ __global__ __launch_bounds__(256) void k_mha_encoder_x2(const float* __restrict_
 #pragma unroll
     for (int d = 0; d < D; ++d) o2[d] = splat2(0.0f);
     for (int j = 0; j < N; ++j) {
-        f32x2 a2 = splat2(0.0f);
-#pragma unroll
-        for (int d = 0; d < D; d += 4) {
-            const float4 kk = *reinterpret_cast<const float4*>(kh + j * W + d);
-            a2 = pk_fma(q2[d], splat2(kk.x), a2);
-            a2 = pk_fma(q2[d + 1], splat2(kk.y), a2);
-            a2 = pk_fma(q2[d + 2], splat2(kk.z), a2);
-            a2 = pk_fma(q2[d + 3], splat2(kk.w), a2);
-        }
-        const f32x2 w2 = d_expf2_nonpos(a2 - m2);
+        const f32x2 w2 = d_expf2_nonpos(pair_score(q2, kh + j * W) - m2);
         zr.add(w2);
-#pragma unroll
-        for (int d = 0; d < D; d += 4) {
-            const float4 vv = *reinterpret_cast<const float4*>(vh + j * W + d);
-            o2[d] = pk_fma(w2, splat2(vv.x), o2[d]);
-            o2[d + 1] = pk_fma(w2, splat2(vv.y), o2[d + 1]);
-            o2[d + 2] = pk_fma(w2, splat2(vv.z), o2[d + 2]);
-            o2[d + 3] = pk_fma(w2, splat2(vv.w), o2[d + 3]);
-        }
+        pair_accumulate(o2, w2, vh + j * W);
     }
-    float o0[D], o1[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) { o0[d] = o2[d].x; o1[d] = o2[d].y; }
     const f32x2 Z2 = zr.total(N);
-    const float Z0 = Z2.x, Z1 = Z2.y;
-    float* op0 = out + (b * N + i0) * (int64_t)E + (h0 + hh) * D;
-#pragma unroll
-    for (int d = 0; d < D; d += 4)
-        *reinterpret_cast<float4*>(op0 + d) = make_float4(o0[d] / Z0, o0[d + 1] / Z0, o0[d + 2] / Z0, o0[d + 3] / Z0);
-    if (has1) {
-        float* op1 = out + (b * N + i1) * (int64_t)E + (h0 + hh) * D;
-#pragma unroll
-        for (int d = 0; d < D; d += 4)
-            *reinterpret_cast<float4*>(op1 + d) = make_float4(o1[d] / Z1, o1[d + 1] / Z1, o1[d + 2] / Z1, o1[d + 3] / Z1);
-    }
+    pair_store_row<0>(out + (b * N + i0) * (int64_t)E + (h0 + hh) * D, o2, Z2);
+    if (has1) pair_store_row<1>(out + (b * N + i1) * (int64_t)E + (h0 + hh) * D, o2, Z2);
 }
 
 // Large graphs (N > 127): the blocked kernel with the keys tiled through LDS.  One block = (instance, group of 4
@@ -650,7 +653,7 @@ constexpr int MHA_TK = 128;     // keys per LDS tile
 __global__ __launch_bounds__(256) void k_mha_encoder_tiled(const float* __restrict__ qkv, float* __restrict__ out, int N, int E,
                                                            int H)
 {
-    constexpr int D = 16, HG = 4, W = HG * D;
+    constexpr int D = MHA_D, HG = MHA_HG, W = MHA_W;
     __shared__ __attribute__((aligned(16))) float ks[MHA_TK * W];
     __shared__ __attribute__((aligned(16))) float vs[MHA_TK * W];
     const int groups = H / HG;
@@ -665,17 +668,7 @@ __global__ __launch_bounds__(256) void k_mha_encoder_tiled(const float* __restri
     const bool has0 = i0 < N, has1 = i1 < N;
     const int i0c = has0 ? i0 : N - 1, i1c = has1 ? i1 : N - 1;
     f32x2 q2[D];
-    {
-        const float* p0 = base + (int64_t)i0c * 3 * E + (h0 + hh) * D;
-        const float* p1 = base + (int64_t)i1c * 3 * E + (h0 + hh) * D;
-#pragma unroll
-        for (int d = 0; d < D; d += 4) {
-            const float4 a = *reinterpret_cast<const float4*>(p0 + d);
-            const float4 c = *reinterpret_cast<const float4*>(p1 + d);
-            q2[d] = (f32x2){a.x, c.x} * 0.25f; q2[d + 1] = (f32x2){a.y, c.y} * 0.25f;
-            q2[d + 2] = (f32x2){a.z, c.z} * 0.25f; q2[d + 3] = (f32x2){a.w, c.w} * 0.25f;
-        }
-    }
+    pair_load_q(q2, base + (int64_t)i0c * 3 * E + (h0 + hh) * D, base + (int64_t)i1c * 3 * E + (h0 + hh) * D);
     const float* kh = ks + hh * D;
     const float* vh = vs + hh * D;
     f32x2 m2 = splat2(-INFINITY);
@@ -689,15 +682,7 @@ __global__ __launch_bounds__(256) void k_mha_encoder_tiled(const float* __restri
         }
         __syncthreads();
         for (int j = 0; j < nj; ++j) {
-            f32x2 a2 = splat2(0.0f);
-#pragma unroll
-            for (int d = 0; d < D; d += 4) {
-                const float4 kk = *reinterpret_cast<const float4*>(kh + j * W + d);
-                a2 = pk_fma(q2[d], splat2(kk.x), a2);
-                a2 = pk_fma(q2[d + 1], splat2(kk.y), a2);
-                a2 = pk_fma(q2[d + 2], splat2(kk.z), a2);
-                a2 = pk_fma(q2[d + 3], splat2(kk.w), a2);
-            }
+            const f32x2 a2 = pair_score(q2, kh + j * W);
             m2.x = __builtin_fmaxf(m2.x, a2.x);
             m2.y = __builtin_fmaxf(m2.y, a2.y);
         }
@@ -717,78 +702,66 @@ __global__ __launch_bounds__(256) void k_mha_encoder_tiled(const float* __restri
         }
         __syncthreads();
         for (int j = 0; j < nj; ++j) {
-            f32x2 a2 = splat2(0.0f);
-#pragma unroll
-            for (int d = 0; d < D; d += 4) {
-                const float4 kk = *reinterpret_cast<const float4*>(kh + j * W + d);
-                a2 = pk_fma(q2[d], splat2(kk.x), a2);
-                a2 = pk_fma(q2[d + 1], splat2(kk.y), a2);
-                a2 = pk_fma(q2[d + 2], splat2(kk.z), a2);
-                a2 = pk_fma(q2[d + 3], splat2(kk.w), a2);
-            }
-            const f32x2 w2 = d_expf2_nonpos(a2 - m2);
+            const f32x2 w2 = d_expf2_nonpos(pair_score(q2, kh + j * W) - m2);
             zr.add(w2);
-#pragma unroll
-            for (int d = 0; d < D; d += 4) {
-                const float4 vv = *reinterpret_cast<const float4*>(vh + j * W + d);
-                o2[d] = pk_fma(w2, splat2(vv.x), o2[d]);
-                o2[d + 1] = pk_fma(w2, splat2(vv.y), o2[d + 1]);
-                o2[d + 2] = pk_fma(w2, splat2(vv.z), o2[d + 2]);
-                o2[d + 3] = pk_fma(w2, splat2(vv.w), o2[d + 3]);
-            }
+            pair_accumulate(o2, w2, vh + j * W);
         }
     }
     const f32x2 Z2 = zr.total(N);
-    if (has0) {
-        float* op0 = out + (b * N + i0) * (int64_t)E + (h0 + hh) * D;
-#pragma unroll
-        for (int d = 0; d < D; d += 4)
-            *reinterpret_cast<float4*>(op0 + d) =
-                make_float4(o2[d].x / Z2.x, o2[d + 1].x / Z2.x, o2[d + 2].x / Z2.x, o2[d + 3].x / Z2.x);
-    }
-    if (has1) {
-        float* op1 = out + (b * N + i1) * (int64_t)E + (h0 + hh) * D;
-#pragma unroll
-        for (int d = 0; d < D; d += 4)
-            *reinterpret_cast<float4*>(op1 + d) =
-                make_float4(o2[d].y / Z2.y, o2[d + 1].y / Z2.y, o2[d + 2].y / Z2.y, o2[d + 3].y / Z2.y);
-    }
+    if (has0) pair_store_row<0>(out + (b * N + i0) * (int64_t)E + (h0 + hh) * D, o2, Z2);
+    if (has1) pair_store_row<1>(out + (b * N + i1) * (int64_t)E + (h0 + hh) * D, o2, Z2);
+}
+
+static size_t mha_plain_lds(int N, int D) { return (size_t)2 * N * D * sizeof(float); }     // k_mha_encoder<D>: ks and vs [N][D]
+
+// The dispatch, stated once: which kernel launch_mha_encoder runs (EAMRL_MHA_*), or EAMRL_E_ARG.  Pure host arithmetic on
+// the shape, the two pointers' alignment and the debug keys 3 and 15; no pointer is dereferenced.
+int mha_encoder_variant(const float* qkv, const float* out, int64_t B, int N, int E, int H)
+{
+    const int D = E / H;
+    if (D * H != E || B * H > INT_MAX) return EAMRL_E_ARG;
+    // the blocked and the MFMA kernels: heads of 16 in groups of 4, float4 rows; debug key 3 keeps the one-row-per-thread kernel
+    const bool blocked = D == 16 && H % 4 == 0 && !g_debug[3] && (((uintptr_t)qkv | (uintptr_t)out) & 15) == 0;
+    if (blocked && 2 * (N + 1) <= 256) return EAMRL_MHA_X2;          // 4 * ceil(N / 2) <= 256 threads
+    // large graphs: the key-tiled fp32-MFMA kernel (encoder_attn_mfma.hip); debug key 15 keeps the VALU one for A/B runs
+    if (blocked && !g_debug[15] && mha_encoder_mfma_supports(N, E, H)) return EAMRL_MHA_MFMA;
+    if (blocked && B * (H / 4) * ((N + 127) / 128) <= INT_MAX) return EAMRL_MHA_TILED;
+    if (D != 16 && D != 32) return EAMRL_E_ARG;
+    if (mha_plain_lds(N, D) > 160 * 1024) return EAMRL_E_ARG;        // the plain kernel alone: the others tile the keys
+    return D == 16 ? EAMRL_MHA_PLAIN16 : EAMRL_MHA_PLAIN32;
+}
+
+// dynamic LDS above 64 KiB needs the attribute raised
+template <typename K>
+static bool allow_dynamic_lds(K* kernel, size_t lds)
+{
+    return lds <= 64 * 1024 || hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                   (int)lds) == hipSuccess;
 }
 
 int launch_mha_encoder(const float* qkv, float* out, int64_t B, int N, int E, int H, hipStream_t st)
 {
-    const int D = E / H;
-    const size_t lds = (size_t)2 * N * D * sizeof(float);       // of k_mha_encoder<D> alone: the kernels before it tile the keys
-    if (D * H != E || B * H > 0x7fffffffLL) return EAMRL_E_ARG;
-    dim3 grid((unsigned)(B * H)), block(128);
-    // blocked kernel: 4 heads per block, 2 query rows per thread (needs 4 * ceil(N/2) <= 256 threads, aligned rows)
-    if (D == 16 && H % 4 == 0 && 2 * (N + 1) <= 256 && !g_debug[3] && ((uintptr_t)qkv & 15) == 0 && ((uintptr_t)out & 15) == 0) {
-        const size_t lds2 = (size_t)2 * N * 64 * sizeof(float);
-        hipLaunchKernelGGL(k_mha_encoder_x2, dim3((unsigned)(B * (H / 4))), dim3(256), lds2, st, qkv, out, N, E, H);
-        return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
-    }
-    // large graphs: the key-tiled fp32-MFMA kernel (encoder_attn_mfma.hip); debug key 15 keeps the VALU one for A/B runs
-    if (!g_debug[15] && !g_debug[3] && mha_encoder_mfma_supports(N, E, H) && ((uintptr_t)qkv & 15) == 0 && ((uintptr_t)out & 15) == 0)
-        return launch_mha_encoder_mfma(qkv, out, B, N, E, H, st);
-    if (D == 16 && H % 4 == 0 && !g_debug[3] && ((uintptr_t)qkv & 15) == 0 && ((uintptr_t)out & 15) == 0 &&
-        B * (H / 4) * ((N + 127) / 128) <= 0x7fffffffLL) {              // large graphs: keys tiled through LDS
-        const unsigned nb = (unsigned)(B * (H / 4) * ((N + 127) / 128));
-        hipLaunchKernelGGL(k_mha_encoder_tiled, dim3(nb), dim3(256), 0, st, qkv, out, N, E, H);
-        return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
-    }
-    if (lds > 160 * 1024) return EAMRL_E_ARG;
-    if (D == 16) {
-        if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(k_mha_encoder<16>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return EAMRL_E_LAUNCH;
-        hipLaunchKernelGGL(k_mha_encoder<16>, grid, block, lds, st, qkv, out, N, E, H);
-    } else if (D == 32) {
-        if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(k_mha_encoder<32>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return EAMRL_E_LAUNCH;
-        hipLaunchKernelGGL(k_mha_encoder<32>, grid, block, lds, st, qkv, out, N, E, H);
-    } else {
-        return EAMRL_E_ARG;
+    const int variant = mha_encoder_variant(qkv, out, B, N, E, H);
+    if (variant < 0) return variant;
+    const size_t lds = mha_plain_lds(N, E / H);
+    const dim3 per_head((unsigned)(B * H)), per_group((unsigned)(B * (H / 4)));
+    switch (variant) {
+    case EAMRL_MHA_X2:
+        hipLaunchKernelGGL(k_mha_encoder_x2, per_group, dim3(256), (size_t)2 * N * MHA_W * sizeof(float), st, qkv, out, N, E, H);
+        break;
+    case EAMRL_MHA_MFMA: return launch_mha_encoder_mfma(qkv, out, B, N, E, H, st);      // its launch and LDS attribute: that file
+    case EAMRL_MHA_TILED:
+        hipLaunchKernelGGL(k_mha_encoder_tiled, dim3(per_group.x * (unsigned)((N + 127) / 128)), dim3(256), 0, st, qkv, out, N, E, H);
+        break;
+    case EAMRL_MHA_PLAIN16:
+        if (!allow_dynamic_lds(k_mha_encoder<16>, lds)) return EAMRL_E_LAUNCH;
+        hipLaunchKernelGGL(k_mha_encoder<16>, per_head, dim3(128), lds, st, qkv, out, N, E, H);
+        break;
+    case EAMRL_MHA_PLAIN32:
+        if (!allow_dynamic_lds(k_mha_encoder<32>, lds)) return EAMRL_E_LAUNCH;
+        hipLaunchKernelGGL(k_mha_encoder<32>, per_head, dim3(128), lds, st, qkv, out, N, E, H);
+        break;
+    default: return EAMRL_E_ARG;
     }
     return hipGetLastError() == hipSuccess ? 0 : EAMRL_E_LAUNCH;
 }

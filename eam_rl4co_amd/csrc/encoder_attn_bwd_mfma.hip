@@ -20,37 +20,14 @@
 //            after the NEXT tile's barrier 256 threads add the 8 partials in wave order and store dq.
 // One barrier per query tile, no atomics, and every sum has a fixed order: the result is deterministic and does not depend on the
 // batch.  Keys >= N get -inf scores (P = dS = 0) and zero values; query rows >= N have zero q and dO and are not stored.
-#include "kernels.hpp"
+#include "mfma_tile.hpp"
 
 namespace eamrl {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
 constexpr int AE = 128, AH = 8, AD = 16;
 constexpr int TRS = 20;                                 // row stride (floats) of the per-wave transpose tile
-
-__device__ __forceinline__ f32x4 mfa(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-template <int CTRL>
-__device__ __forceinline__ float dpp(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false)); }
-
-// butterflies over the 16 lanes of a row (xor 1, xor 2, half-row mirror, row mirror): every lane of the row ends with the same value
-__device__ __forceinline__ float row16_max(float v)
-{
-    v = fmaxf(v, dpp<0xB1>(v));
-    v = fmaxf(v, dpp<0x4E>(v));
-    v = fmaxf(v, dpp<0x141>(v));
-    return fmaxf(v, dpp<0x140>(v));
-}
-__device__ __forceinline__ float row16_sum(float v)
-{
-    v = v + dpp<0xB1>(v);
-    v = v + dpp<0x4E>(v);
-    v = v + dpp<0x141>(v);
-    return v + dpp<0x140>(v);
-}
 
 __device__ __forceinline__ void exp4_nonpos(f32x4& x)
 {
@@ -154,14 +131,14 @@ __global__ __launch_bounds__(512, 1) void k_mha_encoder_bwd_mfma(const float* __
             if (kt < NT) {                              // (uniform)
                 const float4 kb = *reinterpret_cast<const float4*>(KB + ((size_t)kt * 64 + lane) * 4);
                 const float4 vb = *reinterpret_cast<const float4*>(VB + ((size_t)kt * 64 + lane) * 4);
-                f32x4 s = mfa(qa.x, kb.x, (f32x4){0.f, 0.f, 0.f, 0.f});
-                f32x4 d = mfa(da.x, vb.x, (f32x4){0.f, 0.f, 0.f, 0.f});
-                s = mfa(qa.y, kb.y, s);
-                d = mfa(da.y, vb.y, d);
-                s = mfa(qa.z, kb.z, s);
-                d = mfa(da.z, vb.z, d);
-                s = mfa(qa.w, kb.w, s);
-                d = mfa(da.w, vb.w, d);
+                f32x4 s = mf(qa.x, kb.x, (f32x4){0.f, 0.f, 0.f, 0.f});
+                f32x4 d = mf(da.x, vb.x, (f32x4){0.f, 0.f, 0.f, 0.f});
+                s = mf(qa.y, kb.y, s);
+                d = mf(da.y, vb.y, d);
+                s = mf(qa.z, kb.z, s);
+                d = mf(da.z, vb.z, d);
+                s = mf(qa.w, kb.w, s);
+                d = mf(da.w, vb.w, d);
                 if (16 * kt + j >= N) s = (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
                 sc[u] = s;
                 dp[u] = d;
@@ -171,7 +148,7 @@ __global__ __launch_bounds__(512, 1) void k_mha_encoder_bwd_mfma(const float* __
         }
         f32x4 zw = (f32x4){0.f, 0.f, 0.f, 0.f}, xw = zw;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) mw[r] = row16_max(mw[r]);
+        for (int r = 0; r < 4; ++r) mw[r] = row_fmax_dpp(mw[r]);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (wv + 8 * u < NT) {
@@ -187,8 +164,8 @@ __global__ __launch_bounds__(512, 1) void k_mha_encoder_bwd_mfma(const float* __
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            zw[r] = row16_sum(zw[r]);
-            xw[r] = row16_sum(xw[r]);
+            zw[r] = row_sum_dpp(zw[r]);
+            xw[r] = row_sum_dpp(xw[r]);
         }
         float* st = STAT + (buf * 8 + wv) * 48 + 4 * G;
         if (j == 0) {
@@ -234,14 +211,14 @@ __global__ __launch_bounds__(512, 1) void k_mha_encoder_bwd_mfma(const float* __
             if (wv + 8 * u < NT) {
                 const f32x4 p = sc[u] * c;
                 const f32x4 ds = p * (dp[u] - delta);
-                dV[u] = mfa(dc[0], p[0], dV[u]);
-                dK[u] = mfa(qc[0], ds[0], dK[u]);
-                dV[u] = mfa(dc[1], p[1], dV[u]);
-                dK[u] = mfa(qc[1], ds[1], dK[u]);
-                dV[u] = mfa(dc[2], p[2], dV[u]);
-                dK[u] = mfa(qc[2], ds[2], dK[u]);
-                dV[u] = mfa(dc[3], p[3], dV[u]);
-                dK[u] = mfa(qc[3], ds[3], dK[u]);
+                dV[u] = mf(dc[0], p[0], dV[u]);
+                dK[u] = mf(qc[0], ds[0], dK[u]);
+                dV[u] = mf(dc[1], p[1], dV[u]);
+                dK[u] = mf(qc[1], ds[1], dK[u]);
+                dV[u] = mf(dc[2], p[2], dV[u]);
+                dK[u] = mf(qc[2], ds[2], dK[u]);
+                dV[u] = mf(dc[3], p[3], dV[u]);
+                dK[u] = mf(qc[3], ds[3], dK[u]);
                 // dS^T: element (query 4 G + r, key j) -> tr[query][key]; read back lane (query j, G): keys 4 G .. 4 G + 3
 #pragma unroll
                 for (int r = 0; r < 4; ++r) tr[(4 * G + r) * TRS + j] = ds[r];
@@ -255,10 +232,10 @@ __global__ __launch_bounds__(512, 1) void k_mha_encoder_bwd_mfma(const float* __
                 // B operand of dq: lane (d j, G), k-step s -> K[16 kt + 4 G + s][j] = KB[kt][lane 16 (j >> 2) + 4 G + s][j & 3]
                 const float* kp = KB + ((size_t)(wv + 8 * u) * 64 + 16 * (j >> 2) + 4 * G) * 4 + (j & 3);
                 f32x4& dq = (u & 1) ? dq1 : dq0;
-                dq = mfa(a.x, kp[0], dq);
-                dq = mfa(a.y, kp[4], dq);
-                dq = mfa(a.z, kp[8], dq);
-                dq = mfa(a.w, kp[12], dq);
+                dq = mf(a.x, kp[0], dq);
+                dq = mf(a.y, kp[4], dq);
+                dq = mf(a.z, kp[8], dq);
+                dq = mf(a.w, kp[12], dq);
             }
         }
         // dq partial: lane (d j, G), register r -> query 4 G + r

@@ -8,24 +8,16 @@
 //   Z = (P0 + P1) + (P2 + P3), P_r = sequential sum of w over the keys j = r (mod 4) ascending, o = chain_j(w, v) / Z.
 //
 // One workgroup = (instance, head), 8 wavefronts.  The head's keys and values (N x 16 floats each) are staged ONCE in LDS in
-// MFMA fragment order: per 16-key tile kt and lane (j, G) one float4 = the A operand of the tile's four k-steps --
-//   KF[kt][lane] = { K[16 kt + pi(j)][4 t + G] : t = 0..3 },  pi(j) = 4 (j & 3) + (j >> 2): with the keys of a tile placed on
-//                  the MFMA rows in this order the score accumulator register r of lane group G is key 16 kt + 4 r + G, i.e.
-//                  the B operand of value k-step r -- the softmax weights never leave their registers;
-//   VF[kt][lane] = { V[16 kt + 4 r + G][j] : r = 0..3 }   (V^T: the A operand of the value product, rows = head columns).
+// MFMA fragment order (KF / VF: stage_kv_fragments of mfma_tile.hpp states the layout).
 // A wavefront takes query tiles qt = wave, wave + 8, ...: pass 1 walks the key tiles for the row maxima (4 MFMAs per tile, four
 // tiles' chains interleaved: the f32 16x16x4 MFMA has a 40-cycle dependent latency against a 32-cycle issue interval), pass 2
 // walks them again in ascending order for exp / Z / PV, so every sum keeps the canonical ascending-key order (the accumulators
 // simply carry across tiles).  Keys >= N get -inf scores (weight exactly 0) and zero values.
-#include "kernels.hpp"
+#include "mfma_tile.hpp"
 
 namespace eamrl {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
-
-__device__ __forceinline__ f32x4 mfa(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 __global__ __launch_bounds__(512, 2) void k_mha_encoder_mfma(const float* __restrict__ qkv, float* __restrict__ out, int N, int E, int H)
 {
@@ -41,28 +33,7 @@ __global__ __launch_bounds__(512, 2) void k_mha_encoder_mfma(const float* __rest
     const int h = (int)(blockIdx.x - b * H);
     const float* base = qkv + b * (int64_t)N * 3 * E + h * D;
 
-    // ---- stage K and V of this head in fragment order (thread = key; rows beyond N are zeros) ----------------------------------
-    for (int n = tid; n < NT * 16; n += blockDim.x) {
-        float kr[16], vr[16];
-#pragma unroll
-        for (int c = 0; c < 16; c += 4) {
-            float4 kk = make_float4(0.f, 0.f, 0.f, 0.f), vv = kk;
-            if (n < N) {
-                kk = *reinterpret_cast<const float4*>(base + (int64_t)n * 3 * E + E + c);
-                vv = *reinterpret_cast<const float4*>(base + (int64_t)n * 3 * E + 2 * E + c);
-            }
-            kr[c] = kk.x; kr[c + 1] = kk.y; kr[c + 2] = kk.z; kr[c + 3] = kk.w;
-            vr[c] = vv.x; vr[c + 1] = vv.y; vr[c + 2] = vv.z; vr[c + 3] = vv.w;
-        }
-        const int kt = n >> 4, kk = n & 15;
-        const int jr = 4 * (kk & 3) + (kk >> 2);        // the MFMA row that carries key kk of its tile (pi is an involution)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-            *reinterpret_cast<float4*>(KF + ((size_t)kt * 64 + 16 * g + jr) * 4) = make_float4(kr[g], kr[4 + g], kr[8 + g], kr[12 + g]);
-        const int r = kk >> 2, g = kk & 3;              // key 16 kt + 4 r + g: k-step r, lane group g
-#pragma unroll
-        for (int e = 0; e < 16; ++e) VF[((size_t)kt * 64 + 16 * g + e) * 4 + r] = vr[e];
-    }
+    stage_kv_fragments(KF, VF, base, 3 * E, E, N, NT);
     __syncthreads();
 
     for (int qt = wv; qt < NT; qt += 8) {
@@ -78,13 +49,13 @@ __global__ __launch_bounds__(512, 2) void k_mha_encoder_mfma(const float* __rest
                 kf[u] = *reinterpret_cast<const float4*>(KF + ((size_t)kt * 64 + lane) * 4);
             }
 #pragma unroll
-            for (int u = 0; u < 4; ++u) s[u] = mfa(kf[u].x, q0, (f32x4){0.f, 0.f, 0.f, 0.f});
+            for (int u = 0; u < 4; ++u) s[u] = mf(kf[u].x, q0, (f32x4){0.f, 0.f, 0.f, 0.f});
 #pragma unroll
-            for (int u = 0; u < 4; ++u) s[u] = mfa(kf[u].y, q1, s[u]);
+            for (int u = 0; u < 4; ++u) s[u] = mf(kf[u].y, q1, s[u]);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) s[u] = mfa(kf[u].z, q2, s[u]);
+            for (int u = 0; u < 4; ++u) s[u] = mf(kf[u].z, q2, s[u]);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) s[u] = mfa(kf[u].w, q3, s[u]);
+            for (int u = 0; u < 4; ++u) s[u] = mf(kf[u].w, q3, s[u]);
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int kt = kt0 + u;
@@ -117,10 +88,10 @@ __global__ __launch_bounds__(512, 2) void k_mha_encoder_mfma(const float* __rest
                     const f32x2 e01 = d_expf2_nonpos((f32x2){s[u][0] - m, s[u][1] - m});
                     const f32x2 e23 = d_expf2_nonpos((f32x2){s[u][2] - m, s[u][3] - m});
                     zp = zp + e01.x; zp = zp + e01.y; zp = zp + e23.x; zp = zp + e23.y;
-                    o = mfa(vf.x, e01.x, o);
-                    o = mfa(vf.y, e01.y, o);
-                    o = mfa(vf.z, e23.x, o);
-                    o = mfa(vf.w, e23.y, o);
+                    o = mf(vf.x, e01.x, o);
+                    o = mf(vf.y, e01.y, o);
+                    o = mf(vf.z, e23.x, o);
+                    o = mf(vf.w, e23.y, o);
                 }
             }
         }

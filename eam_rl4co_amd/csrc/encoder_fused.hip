@@ -65,8 +65,6 @@ __device__ unsigned long long g_enc_stamps[24];
 #define ESTAMP(i) do { } while (0)
 #endif
 
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
 // One ds_read_b64.  The A fragments of two k-steps are 8 bytes at an 8-byte-aligned address; read as plain float2 pairs the
 // compiler fuses neighbouring ones into ds_read2_b64, which the LDS services in 16-lane groups on 32 banks (8 array cycles,
 // and with the (SA, GA) layout 2-way conflicts on top: 16 cycles per pair -- the 46 % conflict cycles of profiles/r02g_pmc_lds_*),
@@ -217,16 +215,16 @@ __device__ __forceinline__ void gemm_pass_n(f32x4 (&acc)[RTW][CT], const float* 
         for (int rt = 0; rt < NRT; ++rt) {
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct)
-                acc[rt][ct] = SWAP ? mfma4(b[c][ct].x, a[c][rt][0].x, acc[rt][ct]) : mfma4(a[c][rt][0].x, b[c][ct].x, acc[rt][ct]);
+                acc[rt][ct] = SWAP ? mf(b[c][ct].x, a[c][rt][0].x, acc[rt][ct]) : mf(a[c][rt][0].x, b[c][ct].x, acc[rt][ct]);
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct)
-                acc[rt][ct] = SWAP ? mfma4(b[c][ct].y, a[c][rt][0].y, acc[rt][ct]) : mfma4(a[c][rt][0].y, b[c][ct].y, acc[rt][ct]);
+                acc[rt][ct] = SWAP ? mf(b[c][ct].y, a[c][rt][0].y, acc[rt][ct]) : mf(a[c][rt][0].y, b[c][ct].y, acc[rt][ct]);
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct)
-                acc[rt][ct] = SWAP ? mfma4(b[c][ct].z, a[c][rt][1].x, acc[rt][ct]) : mfma4(a[c][rt][1].x, b[c][ct].z, acc[rt][ct]);
+                acc[rt][ct] = SWAP ? mf(b[c][ct].z, a[c][rt][1].x, acc[rt][ct]) : mf(a[c][rt][1].x, b[c][ct].z, acc[rt][ct]);
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct)
-                acc[rt][ct] = SWAP ? mfma4(b[c][ct].w, a[c][rt][1].y, acc[rt][ct]) : mfma4(a[c][rt][1].y, b[c][ct].w, acc[rt][ct]);
+                acc[rt][ct] = SWAP ? mf(b[c][ct].w, a[c][rt][1].y, acc[rt][ct]) : mf(a[c][rt][1].y, b[c][ct].w, acc[rt][ct]);
         }
         if (u + 1 < NU) {       // SchedGroupMask: 0x8 MFMA, 0x20 VMEM read, 0x100 DS read
             __builtin_amdgcn_sched_group_barrier(0x20, CT, 0);
@@ -415,13 +413,13 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
                     // the four dependent k-steps of a key tile are interleaved with those of the other tiles (an f32 16x16x4
                     // MFMA has a 40-cycle dependent latency against a 32-cycle issue interval)
 #pragma unroll
-                    for (int kt = 0; kt < RTT; ++kt) s[kt] = mfma4(kf[kt][0], qlo.x, splat4(0.0f));
+                    for (int kt = 0; kt < RTT; ++kt) s[kt] = mf(kf[kt][0], qlo.x, splat4(0.0f));
 #pragma unroll
-                    for (int kt = 0; kt < RTT; ++kt) s[kt] = mfma4(kf[kt][1], qlo.y, s[kt]);
+                    for (int kt = 0; kt < RTT; ++kt) s[kt] = mf(kf[kt][1], qlo.y, s[kt]);
 #pragma unroll
-                    for (int kt = 0; kt < RTT; ++kt) s[kt] = mfma4(kf[kt][2], qhi.x, s[kt]);
+                    for (int kt = 0; kt < RTT; ++kt) s[kt] = mf(kf[kt][2], qhi.x, s[kt]);
 #pragma unroll
-                    for (int kt = 0; kt < RTT; ++kt) s[kt] = mfma4(kf[kt][3], qhi.y, s[kt]);
+                    for (int kt = 0; kt < RTT; ++kt) s[kt] = mf(kf[kt][3], qhi.y, s[kt]);
 #pragma unroll
                     for (int kt = 0; kt < RTT; ++kt) {
                         // (uniform) the tile holds padded keys: the variant's M range leaves the first FULLT tiles always full
@@ -462,7 +460,7 @@ __global__ __launch_bounds__(512, 2) void k_encoder_fused(FusedArgs a)
                                                             // fma(0, 0, o) == o (o is never -0: it starts from +0)
                         if (kt < FULLT || 16 * kt < M) {
 #pragma unroll
-                            for (int r = 0; r < 4; ++r) o = mfma4(vf[4 * kt + r], s[kt][r], o);
+                            for (int r = 0; r < 4; ++r) o = mf(vf[4 * kt + r], s[kt][r], o);
                         }
                     // o: lane (query j, G), reg r -> head column e = 4 G + r -> A layout (g = r, t = 4 cw + G); overwrites q
                     float* op = QA + qrow * SQ + 4 * cw + Gp;

@@ -13,11 +13,9 @@
 #pragma once
 #include <type_traits>
 
-#include "kernels.hpp"
+#include "mfma_tile.hpp"      // f32x4, mf
 
 namespace eamrl {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int FE = 128;          // embed dim
 constexpr int FH = 8;            // heads

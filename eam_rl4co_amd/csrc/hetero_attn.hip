@@ -14,25 +14,21 @@
 // proj [B][M][6E] = q | k | v | qpair | qsame | qother, each "(h d)"; the depot's last 3E are never read.
 //
 // Forward: the layout of k_mha_encoder_mfma (encoder_attn_mfma.hip).  One workgroup = (instance, head), 8 wavefronts; the head's
-// keys and values are staged once in LDS in MFMA fragment order (KF / VF there).  A wavefront takes query tiles of 16 rows.  The
+// keys and values are staged once in LDS in MFMA fragment order (KF / VF: stage_kv_fragments of mfma_tile.hpp).  A wavefront takes query tiles of 16 rows.  The
 // B operand of a 16x16x4 MFMA is per lane = per query row, so for a key tile that holds keys of one role a lane feeds the query
 // its own row has for that role (qsame or qother): one extra score chain per key tile.  The role ranges are not tile-aligned:
 // a tile that holds pickups AND deliveries (at most one per head, besides tile 0 of tiny graphs) runs a second chain, and each
 // accumulator register picks its key's chain.  Pass 1 takes the row maximum over the general, the extra and the pair score
 // before any exp; pass 2 recomputes the scores and feeds w_gen + w_x to the value MFMAs.  The pair term is a 16-wide dot and a
 // 16-wide axpy per row on VALU.  No atomics; every sum has a fixed order, so two runs are bit-equal.
-#include "kernels.hpp"
+#include "mfma_tile.hpp"
 
 namespace eamrl {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
 constexpr int HD = 16;      // head width
 constexpr int HE = 128, HH = 8;
-
-__device__ __forceinline__ f32x4 mfa(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 __global__ __launch_bounds__(512, 2) void k_hetero_mha(const float* __restrict__ proj, float* __restrict__ out, int M)
 {
@@ -49,28 +45,7 @@ __global__ __launch_bounds__(512, 2) void k_hetero_mha(const float* __restrict__
     const int h = (int)(blockIdx.x - b * H);
     const float* base = proj + b * (int64_t)M * LD + h * D;
 
-    // ---- stage K and V of this head in fragment order (thread = key; rows beyond M are zeros) ----------------------------------
-    for (int n = tid; n < NT * 16; n += blockDim.x) {
-        float kr[16], vr[16];
-#pragma unroll
-        for (int c = 0; c < 16; c += 4) {
-            float4 kk = make_float4(0.f, 0.f, 0.f, 0.f), vv = kk;
-            if (n < M) {
-                kk = *reinterpret_cast<const float4*>(base + (int64_t)n * LD + E + c);
-                vv = *reinterpret_cast<const float4*>(base + (int64_t)n * LD + 2 * E + c);
-            }
-            kr[c] = kk.x; kr[c + 1] = kk.y; kr[c + 2] = kk.z; kr[c + 3] = kk.w;
-            vr[c] = vv.x; vr[c + 1] = vv.y; vr[c + 2] = vv.z; vr[c + 3] = vv.w;
-        }
-        const int kt = n >> 4, kk = n & 15;
-        const int jr = 4 * (kk & 3) + (kk >> 2);        // the MFMA row that carries key kk of its tile
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-            *reinterpret_cast<float4*>(KF + ((size_t)kt * 64 + 16 * g + jr) * 4) = make_float4(kr[g], kr[4 + g], kr[8 + g], kr[12 + g]);
-        const int r = kk >> 2, g = kk & 3;              // key 16 kt + 4 r + g: k-step r, lane group g
-#pragma unroll
-        for (int e = 0; e < 16; ++e) VF[((size_t)kt * 64 + 16 * g + e) * 4 + r] = vr[e];
-    }
+    stage_kv_fragments(KF, VF, base, LD, E, M, NT);
     __syncthreads();
 
     for (int qt = wv; qt < NT; qt += 8) {
@@ -124,30 +99,30 @@ __global__ __launch_bounds__(512, 2) void k_hetero_mha(const float* __restrict__
 #pragma unroll
                 for (int t = 0; t < 4; ++t) x[u][t] = hasP[u] ? qa[t] : qb[t];
 #pragma unroll
-            for (int u = 0; u < 2; ++u) sg[u] = mfa(kf[u].x, q[0], (f32x4){0.f, 0.f, 0.f, 0.f});
+            for (int u = 0; u < 2; ++u) sg[u] = mf(kf[u].x, q[0], (f32x4){0.f, 0.f, 0.f, 0.f});
 #pragma unroll
-            for (int u = 0; u < 2; ++u) sx[u] = mfa(kf[u].x, x[u][0], (f32x4){0.f, 0.f, 0.f, 0.f});
+            for (int u = 0; u < 2; ++u) sx[u] = mf(kf[u].x, x[u][0], (f32x4){0.f, 0.f, 0.f, 0.f});
 #pragma unroll
-            for (int u = 0; u < 2; ++u) sg[u] = mfa(kf[u].y, q[1], sg[u]);
+            for (int u = 0; u < 2; ++u) sg[u] = mf(kf[u].y, q[1], sg[u]);
 #pragma unroll
-            for (int u = 0; u < 2; ++u) sx[u] = mfa(kf[u].y, x[u][1], sx[u]);
+            for (int u = 0; u < 2; ++u) sx[u] = mf(kf[u].y, x[u][1], sx[u]);
 #pragma unroll
-            for (int u = 0; u < 2; ++u) sg[u] = mfa(kf[u].z, q[2], sg[u]);
+            for (int u = 0; u < 2; ++u) sg[u] = mf(kf[u].z, q[2], sg[u]);
 #pragma unroll
-            for (int u = 0; u < 2; ++u) sx[u] = mfa(kf[u].z, x[u][2], sx[u]);
+            for (int u = 0; u < 2; ++u) sx[u] = mf(kf[u].z, x[u][2], sx[u]);
 #pragma unroll
-            for (int u = 0; u < 2; ++u) sg[u] = mfa(kf[u].w, q[3], sg[u]);
+            for (int u = 0; u < 2; ++u) sg[u] = mf(kf[u].w, q[3], sg[u]);
 #pragma unroll
-            for (int u = 0; u < 2; ++u) sx[u] = mfa(kf[u].w, x[u][3], sx[u]);
+            for (int u = 0; u < 2; ++u) sx[u] = mf(kf[u].w, x[u][3], sx[u]);
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const int kt = kt0 + u;
                 f32x4 sd = sx[u];                                     // scores against the delivery keys of the tile
                 if (hasP[u] && hasD[u]) {                             // (uniform) both roles in one tile: a chain of its own
-                    sd = mfa(kf[u].x, qb[0], (f32x4){0.f, 0.f, 0.f, 0.f});
-                    sd = mfa(kf[u].y, qb[1], sd);
-                    sd = mfa(kf[u].z, qb[2], sd);
-                    sd = mfa(kf[u].w, qb[3], sd);
+                    sd = mf(kf[u].x, qb[0], (f32x4){0.f, 0.f, 0.f, 0.f});
+                    sd = mf(kf[u].y, qb[1], sd);
+                    sd = mf(kf[u].z, qb[2], sd);
+                    sd = mf(kf[u].w, qb[3], sd);
                 }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -186,10 +161,10 @@ __global__ __launch_bounds__(512, 2) void k_hetero_mha(const float* __restrict__
                     const f32x2 x23 = d_expf2_nonpos((f32x2){sx[u][2] - m, sx[u][3] - m});
                     const float w0 = g01.x + x01.x, w1 = g01.y + x01.y, w2 = g23.x + x23.x, w3 = g23.y + x23.y;
                     zp = zp + w0; zp = zp + w1; zp = zp + w2; zp = zp + w3;
-                    o = mfa(vf.x, w0, o);
-                    o = mfa(vf.y, w1, o);
-                    o = mfa(vf.z, w2, o);
-                    o = mfa(vf.w, w3, o);
+                    o = mf(vf.x, w0, o);
+                    o = mf(vf.y, w1, o);
+                    o = mf(vf.z, w2, o);
+                    o = mf(vf.w, w3, o);
                 }
             }
         }

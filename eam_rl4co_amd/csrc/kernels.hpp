@@ -18,6 +18,8 @@ extern int g_debug[16];   // eamrl_debug_set knobs
 
 int linear_variant(const GemmArgs& g);   // EAMRL_LINEAR_*: the instantiation launch_linear runs (host arithmetic only)
 int launch_linear(const GemmArgs& g, hipStream_t st);
+// EAMRL_MHA_* (or EAMRL_E_ARG): the kernel launch_mha_encoder runs (host arithmetic only)
+int mha_encoder_variant(const float* qkv, const float* out, int64_t B, int N, int E, int H);
 int launch_mha_encoder(const float* qkv, float* out, int64_t B, int N, int E, int H, hipStream_t st);
 int launch_ea_cvrp(const float* locs, const float* demand, const float* vcap, int64_t* pop, float* fitness, int64_t B, int S,
                    int N, int L, int G, double mutation_rate, double crossover_rate, double selection_rate, int top_k,

@@ -27,8 +27,9 @@ namespace {
 
 constexpr int RH = 8;                // heads (D = 16; the embed dim RE is reeval_tile.hpp's)
 
-// maximum over the four lane groups that share a query (its own copy: fmaxf here, where rollout_multistart.hip's takes vmax_raw)
-__device__ __forceinline__ float group_max(float v)
+// maximum over the four lane groups that share a query on fmaxf: this path is not bit-pinned (lane_groups_max of dmath.hpp is
+// the vmax_raw one of the bit-exact kernels, other instructions)
+__device__ __forceinline__ float lane_groups_fmax(float v)
 {
     auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
     v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
@@ -220,7 +221,7 @@ __device__ __forceinline__ float head_softmax(const float (&kf)[RTT][4], const f
 #pragma unroll
     for (int kt = 0; kt < RTT; ++kt) s[kt] = mf(kf[kt][3], qhi.y, s[kt]);
     if (DYN) {
-        const float c = group_sum(fmaf(qhi.y, dl->wk_in(3), fmaf(qhi.x, dl->wk_in(2), fmaf(qlo.y, dl->wk_in(1), qlo.x * dl->wk_in(0)))));   // q~_h . wk_h
+        const float c = lane_groups_sum(fmaf(qhi.y, dl->wk_in(3), fmaf(qhi.x, dl->wk_in(2), fmaf(qlo.y, dl->wk_in(1), qlo.x * dl->wk_in(0)))));   // q~_h . wk_h
 #pragma unroll
         for (int kt = 0; kt < RTT; ++kt) {
             const f32x4 rv = rem_at(remq, kt);
@@ -247,7 +248,7 @@ __device__ __forceinline__ float head_softmax(const float (&kf)[RTT][4], const f
             for (int r = 0; r < 4; ++r) s[kt][r] = fexp(s[kt][r] - m);
         return given[1];
     }
-    m = group_max(m);
+    m = lane_groups_fmax(m);
     if (stats) stats[0] = m;
     if (m == -INFINITY) m = 0.0f;
     float z = 0.0f;
@@ -258,7 +259,7 @@ __device__ __forceinline__ float head_softmax(const float (&kf)[RTT][4], const f
             s[kt][r] = fexp(s[kt][r] - m);
             z += s[kt][r];
         }
-    z = group_sum(z);
+    z = lane_groups_sum(z);
     if (stats) stats[1] = z;
     return z > 0.0f ? 1.0f / z : 0.0f;
 }
@@ -284,7 +285,7 @@ __device__ __forceinline__ void glimpse_tile(const float (&kf)[RTT][4], const fl
 #pragma unroll
             for (int r = 0; r < 4; ++r) ra = fmaf(s[kt][r], rv[r], ra);
         }
-        ra = group_sum(ra);                        // sum_n w[n] rem[n] (unnormalised, like o)
+        ra = lane_groups_sum(ra);                        // sum_n w[n] rem[n] (unnormalised, like o)
 #pragma unroll
         for (int r = 0; r < 4; ++r) o[r] = fmaf(ra, dl->wv_out(r), o[r]);
     }
@@ -311,7 +312,7 @@ __device__ __forceinline__ f32x4 logit_tile_dyn(const float (&lpf)[32], const fl
         u = mf(lpf[4 * g4 + 3], hi.y, u);
         acc = fmaf(hi.y, lw_in[4 * g4 + 3], fmaf(hi.x, lw_in[4 * g4 + 2], fmaf(lo.y, lw_in[4 * g4 + 1], fmaf(lo.x, lw_in[4 * g4], acc))));
     }
-    hl = group_sum(acc);
+    hl = lane_groups_sum(acc);
     return u;
 }
 __device__ __forceinline__ void load_lw_in(const float* dyn, int G, float (&lw_in)[32])
@@ -414,7 +415,7 @@ __global__ __launch_bounds__(512, 2) void k_reeval_fwd(ReevalArgs a)
                 mx = fmaxf(mx, z[r]);
                 if (n0 + G == act) ZA[j] = z[r];
             }
-            mx = group_max(mx);
+            mx = lane_groups_fmax(mx);
             if (G == 0) RED[wv][j] = mx;
         }
         __syncthreads();
@@ -430,10 +431,10 @@ __global__ __launch_bounds__(512, 2) void k_reeval_fwd(ReevalArgs a)
                 sm += e;
                 if (z[r] != -INFINITY) sz = fmaf(e, z[r], sz);
             }
-            sm = group_sum(sm);
+            sm = lane_groups_sum(sm);
             if (G == 0) RED2[wv][j] = sm;
             if (a.entropy) {
-                sz = group_sum(sz);
+                sz = lane_groups_sum(sz);
                 if (G == 0) RED3[wv][j] = sz;
             }
         }
@@ -514,7 +515,7 @@ __global__ __launch_bounds__(512, 2) void k_reeval_mc_glimpse_part(ReevalArgs a)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) ra = fmaf(s[kt][r], rv[r], ra);
             }
-            ra = group_sum(ra);
+            ra = lane_groups_sum(ra);
 #pragma unroll
             for (int r = 0; r < 4; ++r) o[r] = fmaf(ra, dl.wv_out(r), o[r]);
         }
@@ -930,7 +931,7 @@ __global__ __launch_bounds__(512, 2) void k_reeval_bwd_logits(ReevalArgs a)
                     if (DYN) sdr = fmaf(du, rw[r], sdr);
                 }
                 if (DYN) {
-                    sdr = group_sum(sdr);
+                    sdr = lane_groups_sum(sdr);
                     if (G == 0) atomicAdd(&SDR[cur * 16 + j], sdr);
                 }
             }
@@ -962,7 +963,7 @@ __global__ __launch_bounds__(512, 2) void k_reeval_bwd_logits(ReevalArgs a)
             glimpse_tile<RTT, DYN>(kf, vtf, QTB + nxt * 16 * TS, HTB + nxt * 16 * TS, wv, lane, mb, a.M, REMB + nxt * 16 * 16 * RTT, &dl);
     }
     if (DYN) {
-        dlw_acc = group_sum(dlw_acc);
+        dlw_acc = lane_groups_sum(dlw_acc);
         if (G == 0) atomicAdd(a.ddyn + 2 * RE + 16 * wv + j, dlw_acc);
     }
     dlp_flush<RTT>(a, b, wv, lane, dLp);
@@ -1125,7 +1126,7 @@ __device__ __forceinline__ void attention_bwd_tile(const float (&kf)[RTT][4], co
 #pragma unroll
     for (int kt = 0; kt < RTT; ++kt) da[kt] = mf(vaf[kt][3], dhi.y, da[kt]);
     if (DYN) {                                       // da[n] += rem[n] (wv_h . dO_h)
-        const float e1 = group_sum(fmaf(dhi.y, dl->wv_in(3), fmaf(dhi.x, dl->wv_in(2), fmaf(dlo.y, dl->wv_in(1), dlo.x * dl->wv_in(0)))));
+        const float e1 = lane_groups_sum(fmaf(dhi.y, dl->wv_in(3), fmaf(dhi.x, dl->wv_in(2), fmaf(dlo.y, dl->wv_in(1), dlo.x * dl->wv_in(0)))));
 #pragma unroll
         for (int kt = 0; kt < RTT; ++kt) {
             const f32x4 rv = rem_at(remq, kt);
@@ -1145,7 +1146,7 @@ __device__ __forceinline__ void attention_bwd_tile(const float (&kf)[RTT][4], co
             if (DYN) ar = fmaf(s[kt][r], rv[r], ar);
         }
     }
-    rs = given ? given[2] : group_sum(rs);
+    rs = given ? given[2] : lane_groups_sum(rs);
 #pragma unroll
     for (int kt = 0; kt < RTT; ++kt) {
         f32x4 rv = z4();
@@ -1157,8 +1158,8 @@ __device__ __forceinline__ void attention_bwd_tile(const float (&kf)[RTT][4], co
         }
     }
     if (DYN) {
-        ar = group_sum(ar);                          // sum_n a[n] rem[n]
-        sr = group_sum(sr);                          // sum_n ds[n] rem[n]
+        ar = lane_groups_sum(ar);                          // sum_n a[n] rem[n]
+        sr = lane_groups_sum(sr);                          // sum_n ds[n] rem[n]
         if (G == 0) { srw[j] = sr; srw[16 + j] = ar; }
     }
     // staging of key tile 0 (element (key kappa, query q) of a tile at kappa * 16 + (q & 3) * 4 + (q >> 2))
@@ -1364,8 +1365,8 @@ __global__ __launch_bounds__(512, 2) void k_reeval_bwd_glimpse(ReevalArgs a)
         }, REMB + cur * 16 * 16 * RTT, &dl, SRW + wv * 32, &dwk_acc, &dwv_acc, MC ? gv_cur : nullptr);
     }
     if (DYN) {
-        dwk_acc = group_sum(dwk_acc);
-        dwv_acc = group_sum(dwv_acc);
+        dwk_acc = lane_groups_sum(dwk_acc);
+        dwv_acc = lane_groups_sum(dwv_acc);
         if (G == 0) {
             atomicAdd(a.ddyn + 16 * h + j, dwk_acc);
             atomicAdd(a.ddyn + RE + 16 * h + j, dwv_acc);

@@ -46,19 +46,9 @@ constexpr int SMAX = 128;             // starts per instance
 constexpr int PD = 256;               // PolyNet: poly_layer_dim
 constexpr int TS2 = 268, TG2 = 66;    // ... its hidden tile [16][TS2]: element (j, c) at j * TS2 + (c & 3) * TG2 + (c >> 2)
 
-// combine over the four lane groups (lanes l, l^16, l^32, l^48): first the ^16 partner, then the ^32 one -- the order of the
-// lane tree's levels 4 and 8 for keys laid out 4 per lane (group_sum of mfma_tile.hpp alike)
-// (its own copy: vmax_raw, because this kernel is bit-exact to the oracle; reeval.hip's takes fmaxf)
-__device__ __forceinline__ float group_max(float v)
-{
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = vmax_raw(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return vmax_raw(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
 // Sum over the four lane groups of one chunk's partial sums in the canonical order: lane group G holds the nodes 4 t + G, i.e. the
 // chunk's position class (G - start) & 3, and Z_g = (P0 + P1) + (P2 + P3) over POSITION classes.  Even chunk start: the pairs are
-// the lane groups {G, G ^ 1} (group_sum).  Odd start: {G, G ^ 3} = lanes l and l ^ 48, then the two pair sums (partner l ^ 16).
+// the lane groups {G, G ^ 1} (lane_groups_sum).  Odd start: {G, G ^ 3} = lanes l and l ^ 48, then the two pair sums (partner l ^ 16).
 // (v_permlane32_swap(x, x): result 0 = x of the lower half in both halves, result 1 = the upper half's; v_permlane16_swap alike per row pair.)
 __device__ __forceinline__ float group_sum_odd(float v, int lane)
 {
@@ -78,33 +68,24 @@ __device__ __forceinline__ int group_min(int v)
     return min((int)b[0], (int)b[1]);
 }
 
-// Reductions over the 32 lanes of a half-wavefront (both halves at once): the four DPP levels inside a 16-lane row, then the two
+// Reductions over the 32 lanes of a half-wavefront (both halves at once): the four DPP levels inside a 16-lane row (row_*_dpp), then the two
 // rows of the half through v_permlane16_swap (result 0 = the even row's value, 1 = the odd row's, in both rows).
 __device__ __forceinline__ float half_max(float v)
 {
-    EAMRL_MAX_DPP(v, "quad_perm:[1,0,3,2]");
-    EAMRL_MAX_DPP(v, "quad_perm:[2,3,0,1]");
-    EAMRL_MAX_DPP(v, "row_half_mirror");
-    EAMRL_MAX_DPP(v, "row_mirror");
+    v = row_max_dpp(v);
     auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
     return vmax_raw(__uint_as_float(r[0]), __uint_as_float(r[1]));
 }
 // the lane tree over keys laid out four per lane: levels 4 .. 32 inside a row (one 64-key block per 16 lanes), then block 0 + block 1
 __device__ __forceinline__ float half_tree_sum(float v)
 {
-    v = v + dpp_f<DPP_XOR1>(v);
-    v = v + dpp_f<DPP_XOR2>(v);
-    v = v + dpp_f<DPP_HALF_MIRROR>(v);
-    v = v + dpp_f<DPP_MIRROR>(v);
+    v = row_sum_dpp(v);
     auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 __device__ __forceinline__ int half_min(int v)
 {
-    v = min(v, dpp_i<DPP_XOR1>(v));
-    v = min(v, dpp_i<DPP_XOR2>(v));
-    v = min(v, dpp_i<DPP_HALF_MIRROR>(v));
-    v = min(v, dpp_i<DPP_MIRROR>(v));
+    v = row_min_dpp(v);
     auto r = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
     return min((int)r[0], (int)r[1]);
 }
@@ -406,7 +387,7 @@ __global__ __launch_bounds__(512, 2) void k_rollout_ms_mfma(DecArgs a, int S, in
 #pragma unroll
                     for (int kt = 0; kt < RTT; ++kt) m = vmax5_raw(m, s[kt][0], s[kt][1], s[kt][2], s[kt][3]);
                 }
-                m = group_max(m);
+                m = lane_groups_max(m);
                 MSTAMP(2);
                 // softmax weights; a masked node has s = -inf and d_expf2_nonpos gives it exactly 0 (as the canonical select does)
 #pragma unroll
@@ -471,7 +452,7 @@ __global__ __launch_bounds__(512, 2) void k_rollout_ms_mfma(DecArgs a, int S, in
                                 cz = cz + wg;
                             }
                         }
-                        const float zg = (nlo & 1) ? group_sum_odd(cz, lane) : group_sum(cz);
+                        const float zg = (nlo & 1) ? group_sum_odd(cz, lane) : lane_groups_sum(cz);
                         tot_o = g == 0 ? co : tot_o + co;
                         tot_z = g == 0 ? zg : tot_z + zg;
                     }
@@ -494,7 +475,7 @@ __global__ __launch_bounds__(512, 2) void k_rollout_ms_mfma(DecArgs a, int S, in
                             const int c = cA + sub;
                             if (c <= cB) {                                                // (uniform)
                                 if (c != curc) {                                          // chunk curc is complete
-                                    const float zg = ((curc * C) & 1) ? group_sum_odd(cur_z, lane) : group_sum(cur_z);
+                                    const float zg = ((curc * C) & 1) ? group_sum_odd(cur_z, lane) : lane_groups_sum(cur_z);
                                     tot_o = first ? cur_o : tot_o + cur_o;
                                     tot_z = first ? zg : tot_z + zg;
                                     first = false; curc = c; cur_o = z4(); cur_z = 0.0f;
@@ -507,7 +488,7 @@ __global__ __launch_bounds__(512, 2) void k_rollout_ms_mfma(DecArgs a, int S, in
                     }
                 }
                 {
-                    const float zg = ((curc * C) & 1) ? group_sum_odd(cur_z, lane) : group_sum(cur_z);
+                    const float zg = ((curc * C) & 1) ? group_sum_odd(cur_z, lane) : lane_groups_sum(cur_z);
                     tot_o = first ? cur_o : tot_o + cur_o;
                     tot_z = first ? zg : tot_z + zg;
                 }

@@ -236,6 +236,16 @@ int eamrl_augment_xy(const float* xy, const float* cs, const int32_t* code, floa
  * [nn/attention.py:112-136 MultiHeadAttention.forward]. */
 int eamrl_mha_encoder(const float* qkv, float* out, int64_t B, int N, int E, int H, void* stream);
 
+/* Which kernel eamrl_mha_encoder runs for these arguments under the current debug keys (3 and 15): one of EAMRL_MHA_*, or
+ * EAMRL_E_ARG where eamrl_mha_encoder rejects the call.  Pure host arithmetic on the shape and the 16-byte alignment of qkv and
+ * out; no pointer is dereferenced and nothing is enqueued.  Results never depend on the variant. */
+#define EAMRL_MHA_X2 1        /* k_mha_encoder_x2: heads of 16 in groups of 4, up to 127 nodes, aligned qkv / out */
+#define EAMRL_MHA_MFMA 2      /* k_mha_encoder_mfma: E = 128, H = 8, 128 .. 1200 nodes (150 KiB of LDS), not under debug key 15 */
+#define EAMRL_MHA_TILED 3     /* k_mha_encoder_tiled: heads of 16 in groups of 4, any number of nodes, keys in LDS tiles of 128 */
+#define EAMRL_MHA_PLAIN16 4   /* k_mha_encoder<16>: debug key 3, unaligned qkv / out, H % 4 != 0; K and V of a head within 160 KiB */
+#define EAMRL_MHA_PLAIN32 5   /* k_mha_encoder<32>: heads of 32 */
+int eamrl_mha_encoder_variant(const float* qkv, const float* out, int64_t B, int N, int E, int H);
+
 /* Gradient of eamrl_mha_encoder for the training graph (MultiHeadAttention.forward under loss.backward(),
  * nn/attention.py:112-136): qkv [B][N][3E] as given to the forward, dout [B][N][E] -> dqkv [B][N][3E] (written).  The softmax
  * is recomputed (hardware exp; tile-order sums: held to 1e-5 of torch's scaled_dot_product_attention gradient, not part of
